@@ -3,7 +3,12 @@ r"""Headline benchmark: log_prob samples/s of NSF(features=64, context=0, transf
 hidden=[256]*3) at batch 2^20 per GPU (BASELINE.json configs[1]), fp32, synthetic N(0,1) inputs
 resident in HBM, random-init weights from torch.manual_seed(0) (the reference's constructor order).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-log2 20] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-log2 20] [--dump-outputs DIR] [--full] [--no-cpu-baseline]
+
+A plain run sets up, warms up, times the K steps, writes its outputs when `--dump-outputs DIR` is given and prints the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  Everything else this file measures or checks — the per-kernel
+table and the roofline, the bin-index report, the CPU and ATen baselines, the parity blocks, the side configurations and side
+paths, the detail file — runs only with `--full`.
 
 One "step" = one pass of the hot path over the rank's batch: flow().log_prob(x) for all 2^20 rows,
 the f64 reduction to the mean NLL, and (N > 1) ONE all-reduce of that scalar over RCCL.  Multi-GPU
@@ -15,7 +20,7 @@ GPU, rank -> device LOCAL_RANK, backend nccl = RCCL); under the driver's own tor
 ranks are used as they come.  It refuses to run N ranks on fewer than N visible GPUs unless the dry-run
 environment ZUKO_BENCH_SINGLE_DEVICE=1 ZUKO_BENCH_BACKEND=gloo is set (code-path check on a 1-GPU box).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, measured with events on the launch
+Prints ONE JSON line (rank 0); with `--full` it carries `roofline` (dominant kernel, measured with events on the launch
 stream; `achieved` counts the ALGORITHMIC = non-zero-weight FLOPs of SURVEY 8(d), so `frac` <= 1) and
 `cpu_baseline` (the CPU oracle = the reference's algorithm on PyTorch-CPU ops, bitwise-pinned to the
 reference in the build container, timed on this host's cores on a bounded sample).
@@ -61,6 +66,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch-log2", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: per-kernel table and roofline, bin-index report, CPU and ATen baselines, "
+                         "parity with the oracle, the side configurations and side paths, the detail file (a plain run times the steps and prints the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy: log_prob (float32, this rank's rows) and nll (float64, the mean "
+                         "NLL after the all-reduce); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-bin-report", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
@@ -74,7 +85,10 @@ def parse():
                     help="cfg2 = the headline NSF workload (default, the only graded line); cfg3 = MAF(64,T=8,H=256x3); "
                          "cfg4 = RealNVP(256,T=16,H=512x3); cfg5 = NSF(1024,T=12,K=16,H=1024x3) in bf16 (use --batch-log2 19) — "
                          "side measurements quoted in DESIGN.md")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------
@@ -597,7 +611,7 @@ def run_side_configs(args) -> dict:
     for cfg, (blog, warm, steps) in SIDE_RUNS.items():
         steps = args.side_steps or steps
         cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--gpus", "1", "--batch-log2", str(blog), "--warmup", str(warm), "--steps", str(steps),
-               "--no-bin-report", "--no-side-configs", "--full-line"]
+               "--no-bin-report", "--no-side-configs", "--full", "--full-line"]
         t0 = time.perf_counter()
         try:
             env = dict(os.environ)
@@ -986,6 +1000,19 @@ def run_side_paths() -> dict:
         return {"error": repr(exc)}
 
 
+def dump_outputs(directory: str, lp, nll) -> None:
+    """What the last timed step handed back, as .npy files: `log_prob` (this rank's rows, float32 — a bf16 flow's values widened exactly) and `nll`
+    (the mean negative log-likelihood after the all-reduce, float64).  2^20 rows are 4 MB; beyond 2^22 rows every 2^k-th row is kept (16 MB at most)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    lp = lp.detach().reshape(-1)
+    lp = lp[:: max(1, -(-lp.numel() // (1 << 22)))]
+    np.save(os.path.join(directory, "log_prob.npy"), lp.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(directory, "nll.npy"), nll.detach().to(torch.float64).cpu().numpy().reshape(-1))
+
+
 def model_flops(flow) -> dict:
     """Per sample, whole flow: dense conditioner FLOPs (SURVEY 8d column 2) and FLOPs on non-zero (unmasked) weights."""
     dense = nnz = 0
@@ -1177,9 +1204,13 @@ def main() -> None:
     if bf16:
         x = x.to(torch.bfloat16)
 
+    last = {} if args.dump_outputs else None  # --dump-outputs: the log_prob tensor of the latest step stays alive until it is written
+
     def step(collective: bool = True):
         with torch.no_grad():
             lp = flow().log_prob(x)
+            if last is not None:
+                last["log_prob"] = lp
             nll = ops.sum_f64(lp, -1.0 / (B * world))
             if dist is not None and collective:
                 dist.all_reduce(nll)  # the only collective: one f64 scalar over RCCL/xGMI
@@ -1225,12 +1256,16 @@ def main() -> None:
     ms = dt / args.steps * 1e3
     value = B * world / (dt / args.steps)
     nll_value = float(nll.item())  # the all-reduced mean NLL of the last timed step
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last["log_prob"], nll)
+        last = None
 
     # per-kernel durations over extra (profiled) steps: events on the launch stream
     roof = None
     kernels = {}
     extra = []
-    if rank == 0:
+    if rank == 0 and args.full:
         _C.PROFILE = {}
         for _ in range(min(3, args.steps)):
             step(collective=False)  # rank-0-only pass: must not enter a collective
@@ -1368,13 +1403,13 @@ def main() -> None:
             wall[name] = round(time.perf_counter() - tw, 1)
             tw = time.perf_counter()
 
-        if world == 1 and args.config == "cfg2" and not args.no_bin_report:
+        if args.full and world == 1 and args.config == "cfg2" and not args.no_bin_report:
             try:
                 out["bin_index"] = bin_report(flow, flow_cpu, x, dev)
             except Exception as exc:
                 out["bin_index"] = {"error": repr(exc)}
             lap("bin_index")
-        if world == 1 and not args.no_cpu_baseline and args.config == "cfg2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "cfg2":
             out["cpu_baseline"], sample = cpu_baseline(flow_cpu, args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_baseline_median"] = value / out["cpu_baseline"]["median_samples_per_s"]
@@ -1391,7 +1426,7 @@ def main() -> None:
             except Exception as exc:
                 out["gpu_aten_baseline"] = {"error": repr(exc)}
             lap("gpu_aten_baseline")
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 del x
                 torch.cuda.empty_cache()
@@ -1399,7 +1434,7 @@ def main() -> None:
             except Exception as exc:
                 out["parity"] = {"error": repr(exc), "ok": False}
             lap("parity")
-        if world == 1 and args.config == "cfg2" and args.batch_log2 == 20 and not args.no_side_configs and os.environ.get("ZUKO_BENCH_SINGLE_DEVICE") != "1":
+        if args.full and world == 1 and args.config == "cfg2" and args.batch_log2 == 20 and not args.no_side_configs and os.environ.get("ZUKO_BENCH_SINGLE_DEVICE") != "1":
             # BASELINE.json configs[2..4] at their per-GPU share, a few steps each, after the headline's timed region
             del flow, x
             torch.cuda.empty_cache()
@@ -1412,7 +1447,8 @@ def main() -> None:
         if args.full_line:
             print(json.dumps(out))
         else:
-            out["detail"] = write_detail(out)
+            if args.full:
+                out["detail"] = write_detail(out)
             sys.stdout.flush()
             print(json.dumps(headline_line(out)), flush=True)  # the LAST stdout line, <= LINE_BUDGET bytes
     if dist is not None:

@@ -9,7 +9,7 @@ done
 unset ZUKO_AMD_BF16_MAP
 for m in 0 default; do
   if [ $m = default ]; then unset ZUKO_AMD_BF16_MAP; else export ZUKO_AMD_BF16_MAP=$m; fi
-  timeout 600 python bench.py --config cfg5 --batch-log2 19 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg5_map_$m.json
+  timeout 600 python bench.py --config cfg5 --batch-log2 19 --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg5_map_$m.json
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_cfg5_map_$m.json"))

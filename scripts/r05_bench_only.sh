@@ -2,7 +2,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out/final5b; mkdir -p $OUT
 cd $ROOT
 date +%s > $OUT/bench_t0
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 date +%s > $OUT/bench_t1
 echo "bench seconds: $(( $(cat $OUT/bench_t1) - $(cat $OUT/bench_t0) ))"
 python - <<'PY'

@@ -46,7 +46,7 @@ def test_world_size_mismatch_is_an_error():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu():
-    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-log2", "14", "--no-cpu-baseline"],
+    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-log2", "14", "--full", "--no-cpu-baseline"],  # (--full: the roofline block)
                {"ZUKO_BENCH_SINGLE_DEVICE": "1", "ZUKO_BENCH_BACKEND": "gloo"}, 900)
     assert out["n_gpus"] == 2 and out["rccl_world_size"] == 2 and len(out["per_rank_ms_per_step"]) == 2
     assert out["config"]["global_batch"] == 2 << 14 and out["value"] > 0
