@@ -32,6 +32,15 @@
 #ifndef ARH_RELU_INT
 #define ARH_RELU_INT 0  // probe builds: 1 = ReLU as an integer max (one instruction; a NaN with the sign bit set would become 0)
 #endif
+#ifndef ARH_EPI_PINNED
+#define ARH_EPI_PINNED 1  // probe builds: 0 = the split and the ReLU as plain C++ (compare / select, convert back, subtract, convert)
+#endif
+#ifndef ARH_DESCALE_PK
+#define ARH_DESCALE_PK 1  // probe builds: 0 = the hidden layers' descale as one v_fma_f32 per value (1: one v_pk_fma_f32 per pair)
+#endif
+#ifndef ARH_PREFETCH
+#define ARH_PREFETCH 1  // probe builds: 0 = a tile's x rows and its log-derivative are requested where they are consumed
+#endif
 
 namespace zk {
 
@@ -45,7 +54,7 @@ struct ArhB {  // B operand of one pair of activation tiles
 // descale factor 2^-(ew + ea) (ew in [-25, 35]: zuko_amd/fused.py, half_scales) is a normal f32 number.  Beyond: a sample whose largest magnitude
 // exceeds 2^105 (4e31) overflows f16 and becomes NaN — as a non-finite value does (inf - inf in the low part) —, smaller ones than 2^-75 lose
 // relative precision (absolute error below 2^-100).  amax = 0: zeros stay zeros.
-__device__ __forceinline__ void arh_scale(float amax, float& s, float& inv_s) {
+__device__ __forceinline__ void arh_scale(float& amax, float& s, float& inv_s) {  // (amax returns as the SAMPLE's maximum)
   amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
   amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
   int e = __builtin_amdgcn_frexp_expf(amax);  // amax = f 2^e, f in [0.5, 1); 0 for zero / inf / NaN
@@ -55,11 +64,35 @@ __device__ __forceinline__ void arh_scale(float amax, float& s, float& inv_s) {
   inv_s = __builtin_amdgcn_ldexpf(1.0f, -ea);
 }
 
+// smallest sample maximum whose scaled value (ea = -90) rounds to an f16 infinity: from here on a sample is NaN (see above)
+#define ARH_AMAX_OVERFLOW (65520.f * 0x1p90f)
+
+typedef unsigned arh_u32x4 __attribute__((ext_vector_type(4)));
+typedef float arh_f32x2 __attribute__((ext_vector_type(2)));
+
 __device__ __forceinline__ void arh_split(const f32x4& lo, const f32x4& hi, float s, ArhB& b) {
   if (ARX_ABL == 6) {
     b.h = __builtin_bit_cast(f16x8, lo); b.l = __builtin_bit_cast(f16x8, hi);
     return;
   }
+#if ARH_EPI_PINNED
+  // TWO instructions per value, pinned (under -ffp-contract=off the compiler converts h back, subtracts and converts: four):
+  //   h = f16(fma(v, s, -0))   v s is exact (s is a power of two) and -0 keeps the sign of a zero: the bits of (_Float16)(v * s)
+  //   l = f16(fma(v, s, -h))   v s - h is exact in f32: the bits of (_Float16)(v * s - (float)h)
+  // (v s below the f32 normal range: |v s| < 2^-126 gives h = 0 and l = 0 either way.)  mixlo / mixhi write one half of the destination.
+  const float nz = -0.f;
+  arh_u32x4 h, l;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(h[e]) : "v"(e < 2 ? lo[2 * e] : hi[2 * e - 4]), "v"(s), "s"(nz));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) asm("v_fma_mixhi_f16 %0, %1, %2, %3" : "+v"(h[e]) : "v"(e < 2 ? lo[2 * e + 1] : hi[2 * e - 3]), "v"(s), "s"(nz));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l[e]) : "v"(e < 2 ? lo[2 * e] : hi[2 * e - 4]), "v"(s), "v"(h[e]));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l[e]) : "v"(e < 2 ? lo[2 * e + 1] : hi[2 * e - 3]), "v"(s), "v"(h[e]));
+  b.h = __builtin_bit_cast(f16x8, h); b.l = __builtin_bit_cast(f16x8, l);
+  return;
+#endif
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float v = (e < 4 ? lo[e] : hi[e - 4]) * s;
@@ -85,6 +118,37 @@ __device__ __forceinline__ void arh_block(const f32x4 (&a)[2], const ArhB& b, f3
 __device__ __forceinline__ void arh_touch(f32x4& v) { asm volatile("" : "+v"(v)); }  // a raw-read register becomes usable HERE (behind the counted wait that settled it)
 template <int N> __device__ __forceinline__ void arh_settle(f32x4& a0, f32x4& a1) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a0), "+v"(a1) : "n"(N)); }
 template <int N> __device__ __forceinline__ void arh_settle(f32x4& a0, f32x4& a1, f32x4& a2) { asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a0), "+v"(a1), "+v"(a2) : "n"(N)); }
+
+// The ring of fused_ar_static_impl.h with a counted wait that knows about XV vector-memory loads YOUNGER than the chunk requested last (the
+// next tile's x rows: arh_kernel).  Loads return in order: with the two youngest groups (XV loads, PER copies) still in flight, the chunk
+// this advance hands to the readers has landed.  XV must be the number of load INSTRUCTIONS every wavefront has issued since the last
+// advance, or fewer (a lower count only waits longer).
+template <int WAVES, int CH, int NR> struct ArhRing : ArRingS<WAVES, CH, NR> {
+  typedef ArRingS<WAVES, CH, NR> B;
+  template <int XV> __device__ __forceinline__ void advance_x() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NR - 2) * B::PER + XV) : "memory");
+    if (ARX_ABL != 4) __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    this->issue();
+    this->slot = (this->slot + 1 == NR) ? 0 : this->slot + 1;
+    this->cur_off = this->lds_off + (unsigned)(this->slot * CH * AR_TF * 4 + this->lane * 16);
+  }
+  template <int S, int XV = 0> __device__ __forceinline__ f32x4 read() {
+    if constexpr (XV != 0 && S % CH == 0) {
+      advance_x<XV>();
+      f32x4 v;
+      if (ARX_ABL == 5) {
+        asm volatile("v_mov_b32 %0, %1" : "=v"(v[0]) : "v"(this->cur_off));
+        v[1] = v[2] = v[3] = v[0];
+        return v;
+      }
+      asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(this->cur_off), "n"((S % CH) * AR_TF * 4));
+      return v;
+    } else {
+      return B::template read<S>();
+    }
+  }
+};
 
 // one hidden layer: out = fma(W' in', d, bias) over the blocks of the generated pattern (W', in': the scaled operands; d = 2^-(ew + ea))
 template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d) {
@@ -121,20 +185,41 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
       arh_block(a[cur], in[ip], acc);
       if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
       if constexpr (last_of_tile) {
+        if (ARH_DESCALE_PK) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[ot][r] = __builtin_fmaf(acc[r], d, bs[r]);
+          for (int r = 0; r < 4; r += 2) {
+            const arh_f32x2 o = __builtin_elementwise_fma(arh_f32x2{acc[r], acc[r + 1]}, arh_f32x2{d, d}, arh_f32x2{bs[r], bs[r + 1]});
+            out[ot][r] = o[0]; out[ot][r + 1] = o[1];
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) out[ot][r] = __builtin_fmaf(acc[r], d, bs[r]);
+        }
       }
     });
   }
 }
 
 template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden_stack(Ring& ring, const float* bias_lds, int q, ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], const ArArgs& a,
-                                                                                       float& inv_s) {
+                                                                                       float& inv_s, float& poison) {
   if constexpr (L < S::NH) {
     arh_hidden<S, L>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, a.wdescale[L] * inv_s);
     constexpr int HTL = S::HT[L];
     float amax = 0.f;
-    if constexpr (S::ACT == 1) {
+    if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
+      // ReLU as ONE v_max_f32 per value, the sample's maximum as one v_max3_f32 per pair.  The max turns a NaN into 0, so no NaN may
+      // reach a hidden value: x, weights and biases are finite (poison below; zuko_amd/fused.py: half_scales), products and sums of the
+      // f16 parts stay far inside f32, and the descale fma of finite operands gives a finite value or an infinity — which survives the
+      // max and is caught at the sample's maximum (arh_hidden_stack's poison: the next layer would compute inf - inf from it).
+#pragma unroll
+      for (int t = 0; t < HTL; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; r += 2) {
+          asm("v_max_f32 %0, 0, %0" : "+v"(out[t][r]));  // (pinned: behind a packed fma the compiler puts a canonicalising v_max in front of fmaxf)
+          asm("v_max_f32 %0, 0, %0" : "+v"(out[t][r + 1]));
+          asm("v_max3_f32 %0, %0, %1, %2" : "+v"(amax) : "v"(out[t][r]), "v"(out[t][r + 1]));
+        }
+    } else if constexpr (S::ACT == 1) {
 #pragma unroll
       for (int t = 0; t < HTL; ++t)
 #pragma unroll
@@ -160,16 +245,19 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
     }
     float s;
     arh_scale(amax, s, inv_s);
+    if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
+      if (!(amax < ARH_AMAX_OVERFLOW)) poison = __builtin_nanf("");  // a hidden value overflowed f32 (or f16 after the scaling): NaN for its sample
+    }
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int p = 0; p < (HTL + 1) / 2; ++p) arh_split(out[2 * p], 2 * p + 1 < HTL ? out[2 * p + 1] : zero, s, in[p]);
-    arh_hidden_stack<S, L + 1, Ring>(ring, bias_lds, q, in, out, a, inv_s);
+    arh_hidden_stack<S, L + 1, Ring>(ring, bias_lds, q, in, out, a, inv_s, poison);
   }
 }
 
 // DIAG: the diagnostic twin of the product launch (also writes the bin index the spline USED and the knots it searched), as arx_kernel's.
 template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arh_kernel(ArArgs a) {
-  typedef ArRingS<S::WAVES, S::CH, S::NR> Ring;
+  typedef ArhRing<S::WAVES, S::CH, S::NR> Ring;
   static_assert(S::WAVES == 8 && S::NR == 3 && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::OCC == 2, "two-part split kernels: widths <= 256, two wavefronts per SIMD");
   constexpr int NT = Uni::NT, FPL = Uni::FPL, TOTAL = Uni::TOTAL, WAVES = S::WAVES;
   constexpr int NG = S::NG;
@@ -191,6 +279,20 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
   ring.slot = S::NR - 1;
   ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
   ring.cur_off = ring.lds_off;
+
+  // x rows of a tile, 4 values of S::NIT 16-column groups per lane.  Every lane loads (a column group that ends beyond DIN is read at the
+  // row's last four columns and zeroed afterwards): the number of load instructions in flight is the same for every wavefront (ArhRing)
+  auto x_request = [&](int64_t tile, f32x4 (&xv)[S::NIT]) ARS_ALWAYS_INLINE {
+    const int64_t n = tile * (16 * WAVES) + wave * 16 + j;
+    const float* row = a.x + (n < a.N ? n : a.N - 1) * a.ldx;
+#pragma unroll
+    for (int it = 0; it < S::NIT; ++it) {
+      const int col = it * 16 + 4 * q;
+      xv[it] = *reinterpret_cast<const f32x4*>(row + ((it + 1) * 16 <= S::DIN || col < S::DIN ? col : S::DIN - 4));
+    }
+  };
+  f32x4 xnext[S::NIT];  // the NEXT tile's rows: requested a last layer ahead of the tile that consumes them
+  if (ARH_PREFETCH) x_request(blockIdx.x, xnext);  // (the first tile's: landed behind the barrier below)
 
   for (int i = tid; i < a.bias_floats; i += 64 * WAVES) bias_lds[i] = a.bias[i];
   int* fmap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);  // same LDS layout as the f32 kernels
@@ -222,7 +324,11 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
 #pragma unroll
       for (int it = 0; it < S::NIT; ++it) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = *reinterpret_cast<const f32x4*>(xrow + it * 16 + 4 * q);
+        if (ARH_PREFETCH) {
+          if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = xnext[it];
+        } else {
+          if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = *reinterpret_cast<const f32x4*>(xrow + it * 16 + 4 * q);
+        }
         xin[it] = v;
       }
       xin[S::NIT] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -248,12 +354,18 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
       }
       float s;
       arh_scale(amax, s, inv_s);
+      if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
+        if (!(amax < ARH_AMAX_OVERFLOW)) poison = __builtin_nanf("");  // (finite, but its f16 parts are not: the one-instruction ReLU would flatten the NaN they make)
+      }
 #pragma unroll
       for (int p = 0; p < (S::NIT + 1) / 2; ++p) arh_split(xin[2 * p], xin[2 * p + 1], s, in[p]);
     }
 
+    float ladj_in = 0.f;  // the running log-derivative this launch adds to: requested HERE, a whole tile ahead of the add
+    if (ARH_PREFETCH && a.ladj && a.accumulate && live && q == 0) ladj_in = a.ladj[n];
+
     // ---- hidden layers ---------------------------------------------------------------------------------------------
-    arh_hidden_stack<S, 0, Ring>(ring, bias_lds, q, in, out, a, inv_s);
+    arh_hidden_stack<S, 0, Ring>(ring, bias_lds, q, in, out, a, inv_s, poison);
 
     // ---- last layer + univariate transform, one group of 4 * FPL features at a time --------------------------------
     const float dl = a.wdescale[S::NH] * inv_s;
@@ -261,9 +373,18 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
     constexpr int NBL = NSTEP * NT;                          // blocks of the last layer
     constexpr int LOOKL = ARH_LOOK < NBL ? ARH_LOOK : NBL;
     f32x4 w[LOOKL + 1][2];
+    // the next tile of this workgroup: its rows travel during the last layer.  The LAST tile requests its own rows again, so that the
+    // count of loads in flight does not depend on the tile; XPOS is the one advance of the ring that finds them younger than its chunk
+    constexpr int XPOS = ARH_PREFETCH ? (S::LAST_BASE + S::CH - 1) / S::CH * S::CH : -1;
+    if (ARH_PREFETCH) {
+      asm volatile("" ::: "memory");
+      x_request(tile + gridDim.x < a.n_tiles ? tile + gridDim.x : tile, xnext);
+      asm volatile("" ::: "memory");
+    }
+#define ARH_READ_LAST(POS) ring.template read<(POS), ((POS) == XPOS ? S::NIT : 0)>()
     ars_for<LOOKL>([&](auto b_) ARS_ALWAYS_INLINE {
       constexpr int b = b_;
-      ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[b][p] = ring.template read<S::LAST_BASE + 2 * b + decltype(p)::value>(); });
+      ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[b][p] = ARH_READ_LAST(S::LAST_BASE + 2 * b + decltype(p)::value); });
     });
     ars_for<NG>([&](auto g_) ARS_ALWAYS_INLINE {
       constexpr int g = g_, ST0 = S::GOFF[g], GN = S::GOFF[g + 1] - S::GOFF[g];
@@ -293,7 +414,7 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
           }
           if constexpr (blk + LOOKL < NBL) {
             constexpr int nx = (blk + LOOKL) % (LOOKL + 1);
-            ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[nx][p] = ring.template read<S::LAST_BASE + 2 * (blk + LOOKL) + decltype(p)::value>(); });
+            ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[nx][p] = ARH_READ_LAST(S::LAST_BASE + 2 * (blk + LOOKL) + decltype(p)::value); });
           }
           constexpr int ahead = (blk + LOOKL < NBL ? LOOKL : NBL - 1 - blk);
           if constexpr (last_of_group) arh_settle<(blk + LOOKL < NBL ? 2 : 0)>(w[cur][0], w[cur][1]);
@@ -310,7 +431,12 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
       float p[4 * NT];
       ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) p[4 * t + r] = __builtin_fmaf(acc[t][r], dl, bs[t][r]);
+        for (int r = 0; r < 4; ++r) {
+          p[4 * t + r] = __builtin_fmaf(acc[t][r], dl, bs[t][r]);
+          // one fma per parameter, written where the spline wants it: left alone, the vectoriser pairs parameter j with parameter K + j (the
+          // spline's two axes) in FRONT of the fma and gathers accumulator and bias elements into register pairs for it (3 v_mov per pair)
+          if (ARH_POISON_ONE) asm("" : "+v"(p[4 * t + r]));
+        }
       });
 #pragma unroll
       for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
@@ -341,6 +467,15 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
         }
       }
     });
+#undef ARH_READ_LAST
+    auto ladj_out = [&]() ARS_ALWAYS_INLINE {
+      if (a.ladj) {
+        lacc += __shfl_xor(lacc, 16, 64);
+        lacc += __shfl_xor(lacc, 32, 64);
+        if (live && q == 0) a.ladj[n] = a.accumulate ? (ARH_PREFETCH ? ladj_in : a.ladj[n]) + lacc : lacc;
+      }
+    };
+    if (ARH_PREFETCH) ladj_out();  // in FRONT of the y rows: the wait for ladj_in (requested a tile ago) must not find stores it would have to sit out
     if constexpr (XLDS) {
       asm volatile("" ::: "memory");
       __builtin_amdgcn_wave_barrier();
@@ -350,11 +485,7 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
           if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(a.y + n * a.ldy + it * 16 + 4 * q) = *reinterpret_cast<const f32x4*>(xr + it * 16 + 4 * q);
       }
     }
-    if (a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
+    if (!ARH_PREFETCH) ladj_out();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }

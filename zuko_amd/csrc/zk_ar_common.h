@@ -11,6 +11,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define AR_WAVES 8
 #define AR_T 16   /* activation tiles (256 units) */
 #define ARS_ABI 9 /* contract between this library and the generated static-shape kernels (zuko_amd/static_ar.py): bump on any change of ArArgs */
+#ifndef ARH_POISON_ONE
+#define ARH_POISON_ONE 1  // probe builds: 0 = the NaN-or-zero is added to all K search-axis parameters of a spline (UniRqs::poison)
+#endif
 
 struct ArArgs {
   int64_t N;
@@ -109,10 +112,16 @@ template <int K, bool CIRC> struct UniRqs {
   // All-NaN parameters (reference: zuko/nn.py:217-218 on a non-finite input) leave knot 0 = -B finite and every other
   // knot NaN: values right of -B land in bin 0 with a NaN corner (y = NaN), values at or left of it, NaN and -inf keep
   // y = v, and log|dy/dx| is NaN everywhere.  NaN widths (heights for the inverse, which searches the other axis) give
-  // exactly that: the remaining parameters never reach an output that is not already NaN.
+  // exactly that: the remaining parameters never reach an output that is not already NaN.  ONE add is enough: the knots
+  // are a running sum (rqs_lean: acc += 2^(u_j r_j), cum[j] = acc) that turns NaN at j = 0 and stays NaN, and the
+  // normaliser 1 / acc is NaN with it, so knots 1 .. K come out NaN whatever parameters 1 .. K - 1 hold.
   template <bool INV> static __device__ __forceinline__ void poison(float* p, int base, float nan_or_zero) {
+#if ARH_POISON_ONE
+    p[base + (INV ? K : 0)] += nan_or_zero;
+#else
 #pragma unroll
     for (int j = 0; j < K; ++j) p[base + (INV ? K : 0) + j] += nan_or_zero;
+#endif
   }
   static constexpr int NKNOT = K + 1;
   // k / ks (diagnostic instantiation): bin index and search-axis knots of THIS evaluation

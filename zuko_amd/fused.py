@@ -461,13 +461,15 @@ def half_scales(linears):
         small = (nz & (a < big * 2.0 ** -HALF_SPREAD_LOG2)).sum() / nz.sum().clamp_min(1)
         rowmax = a.amax(dim=1)
         minrow = torch.where(rowmax > 0, rowmax, big).amin()
-        stats.append(torch.stack([big.float(), small.float(), minrow.float()]))
+        bias = getattr(m, "bias", None)  # (a non-finite bias keeps the three-part kernel: the two-part kernel's ReLU is a max, which would turn the NaN into 0)
+        bfin = torch.isfinite(bias.detach()).all() if bias is not None else torch.ones((), dtype=torch.bool, device=w.device)
+        stats.append(torch.stack([big.float(), small.float(), minrow.float(), bfin.float()]))
     out = []
-    for big, small, minrow in torch.stack(stats).tolist():
+    for big, small, minrow, bfin in torch.stack(stats).tolist():
         if big == 0.0:
-            out.append((True, 0))
+            out.append((bfin == 1.0, 0))
             continue
-        ok = math.isfinite(big) and 2.0 ** HALF_MIN_LOG2 <= big <= 2.0 ** HALF_MAX_LOG2 and small <= HALF_SMALL_FRACTION and minrow >= big * 2.0 ** -HALF_ROW_LOG2
+        ok = bfin == 1.0 and math.isfinite(big) and 2.0 ** HALF_MIN_LOG2 <= big <= 2.0 ** HALF_MAX_LOG2 and small <= HALF_SMALL_FRACTION and minrow >= big * 2.0 ** -HALF_ROW_LOG2
         out.append((bool(ok), 15 - math.frexp(big)[1] if math.isfinite(big) else 0))
     return out
 
