@@ -26,18 +26,14 @@
 // Host-side planning (permutations, stream order, skip masks): zuko_amd/fused.py.
 #include "../../include/zuko_amd.h"
 #include "zk_ar_common.h"
-#include <cstring>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 
-// -DZK_AR_TIMING=1 compiles in the s_memtime/printf phase probes (dbg bits 3 and 4); off in the product build
+// -DZK_AR_TIMING=1 compiles in the probes (ArArgs::dbg bit 0: no univariate math; bits 3 and 4: s_memtime / printf phases); off in the product build
 #ifndef ZK_AR_TIMING
 #define ZK_AR_TIMING 0
 #endif
 
 namespace zk {
-
 
 template <int CH, int NR> struct RingT {
   static constexpr int kChunk = CH, kSlots = NR;
@@ -122,41 +118,26 @@ __device__ __forceinline__ void hidden_layer(Src& ring, const uint32_t* __restri
 }
 
 template <typename Uni, bool INVERSE, class Src, bool XLDS, bool DIAG = false> __global__ __launch_bounds__(512, 2) void ar_kernel(ArArgs a) {
-  constexpr bool DIRECT = false;
   constexpr int NT = Uni::NT, FPL = Uni::FPL, TOTAL = Uni::TOTAL;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
-  float* ring_lds = ar_lds;
-  float* bias_lds = ar_lds;  // (DIRECT: the bias image is the only LDS user)
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
 
   Src ring;
-  if constexpr (DIRECT) {
-    ring.init(a.stream, lane, a.n_chunks);  // n_chunks == number of tile images (chunk size 1)
-  } else {
-    bias_lds = ar_lds + Src::kSlots * Src::kChunk * AR_TF;
-    ring.dbg = a.dbg; ring.lds = ring_lds; ring.stream = a.stream; ring.sched = a.sched; ring.n_chunks = a.sched ? a.n_sched : a.n_chunks; ring.wave = wave; ring.lane = lane;
-    ring.load_chunk = 0; ring.load_slot = 0;
+  ring.dbg = a.dbg; ring.lds = ar_lds; ring.stream = a.stream; ring.sched = a.sched; ring.n_chunks = a.sched ? a.n_sched : a.n_chunks; ring.wave = wave; ring.lane = lane;
+  ring.load_chunk = 0; ring.load_slot = 0;
 #pragma unroll
-    for (int i = 0; i < Src::kSlots - 1; ++i) ring.issue();
-    ring.slot = Src::kSlots - 1;
-    ring.pos = Src::kChunk;
-  }
+  for (int i = 0; i < Src::kSlots - 1; ++i) ring.issue();
+  ring.slot = Src::kSlots - 1;
+  ring.pos = Src::kChunk;
 
-  for (int i = tid; i < a.bias_floats; i += 512) bias_lds[i] = a.bias[i];
-  int* fmap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);  // feature map of the last layer
-  // wave-private [16 samples x D] tile: the epilogue's input values on the way in, the results on the
-  // way out.  Keeps the per-group operand fetch on the LDS (lgkmcnt) queue — a global load there would
-  // have to be waited for with vmcnt(0), i.e. behind the ring DMAs in flight (measured: 5 k cycles per
-  // group) — and turns 4-byte scattered result stores into coalesced 16-byte row stores.
   // skip words of the last layer's groups: read per group, so they must not come through a vector-memory
   // load (its s_waitcnt vmcnt(0) would also drain the ring DMAs in flight) — LDS copy, lgkmcnt queue
-  int* skip_lds = fmap_lds + 1024;
-  float* xr = reinterpret_cast<float*>(fmap_lds + 1024 + 256) + wave * 16 * a.xs + j * a.xs;
-  for (int i = tid; i < a.NG * 4 * FPL; i += 512) fmap_lds[i] = a.featmap[i];
-  for (int i = tid; i < a.NG; i += 512) skip_lds[i] = (int)a.skip[(a.L - 1) * 4 + i];
-  __syncthreads();
+  float* const bias_lds = ar_lds + Src::kSlots * Src::kChunk * AR_TF;
+  int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
+  const int* const skip_lds = ArLds::skip(fmap_lds);
+  float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  ArLds::stage<512>(a, tid, bias_lds, fmap_lds, a.NG * 4 * FPL, (a.L - 1) * 4, a.NG);
+  const ArFids<0, FPL, false> fids(fmap_lds, q);
 
   const float* bias_last = bias_lds + (a.L - 1) * 256;
 
@@ -177,20 +158,8 @@ template <typename Uni, bool INVERSE, class Src, bool XLDS, bool DIAG = false> _
       }
       in[it] = v;
     }
-    // The reference multiplies every input by (mask * W): a NaN or +-inf input therefore turns ALL
-    // parameters of its sample into NaN (x * 0 = NaN), including those whose mask excludes that input
-    // (zuko/nn.py:217-218).  Skipped tiles would not reproduce that, so the sample is flagged instead.
-    float poison = 0.f;
-    {
-      int bad = 0;
-#pragma unroll
-      for (int it = 0; it < AR_T; ++it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bad |= !(fabsf(in[it][r]) < __builtin_inff());
-      bad |= __shfl_xor(bad, 16, 64);
-      bad |= __shfl_xor(bad, 32, 64);
-      if (bad) poison = __builtin_nanf("");
-    }
+    const float poison = ar_poison_of<AR_T>(in);
+    const float* urow = INVERSE ? a.yin + nc * a.ldyin : xrow;  // the values the univariate map is applied to
     if (XLDS) {
 #pragma unroll
       for (int it = 0; it < AR_T; ++it) {
@@ -198,7 +167,7 @@ template <typename Uni, bool INVERSE, class Src, bool XLDS, bool DIAG = false> _
           const int i0 = it * 16 + 4 * q;
           if (i0 < a.D) {
             f32x4 v = in[it];
-            if (INVERSE) v = *reinterpret_cast<const f32x4*>(a.yin + nc * a.ldyin + i0);
+            if (INVERSE) v = *reinterpret_cast<const f32x4*>(urow + i0);
             *reinterpret_cast<f32x4*>(xr + i0) = v;
           }
         }
@@ -248,13 +217,7 @@ template <typename Uni, bool INVERSE, class Src, bool XLDS, bool DIAG = false> _
       // feature ids + bias from LDS, x[n, f] from global/L2 (one dependent load)
       int fid[FPL];
       float xin[FPL];
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) {
-        fid[fi] = fmap_lds[(g * 4 + q) * FPL + fi];
-        const int fc = fid[fi] < 0 ? 0 : fid[fi];
-        if (XLDS) xin[fi] = xr[fc];
-        else xin[fi] = INVERSE ? a.yin[nc * a.ldyin + fc] : xrow[fc];
-      }
+      fids.template fetch<XLDS>(g, xr, urow, fid, xin);
       f32x4 acc[NT];  // the accumulators start at the bias
       {
         const float* bg = bias_last + (g * NT) * 16 + 4 * q;
@@ -337,49 +300,46 @@ template <typename Uni, bool INVERSE, class Src, bool XLDS, bool DIAG = false> _
         printf("wave %d: L1 %llu  L2 %llu  L3 %llu  (+bias/act each)  last layer + 16 epilogues %llu   total %llu cycles\n", wave, tstamp[1] - tstamp[0],
                tstamp[2] - tstamp[1], tstamp[3] - tstamp[2], tstamp[5] - tstamp[3], tstamp[5] - tstamp[0]);
     }
-    if (!INVERSE && a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
+    if (!INVERSE) ar_ladj_store(a, lacc, n, live, q);
   }
   ring.drain();  // look-ahead DMAs must land before the LDS is released
 }
 
+// one gathered weight: 0 for a padding slot (k < 0) or a masked-out entry
+__device__ __forceinline__ float gather_one(const float* __restrict__ src, const uint8_t* __restrict__ mask, int32_t k) { return (k >= 0 && (!mask || mask[k])) ? src[k] : 0.f; }
+
+// Lane i of the operand-split weight stream (fused_ar_split_impl.h): its 8 weights as three bf16 parts h = bf16(w), m = bf16(w - h), l = bf16(w - h - m)
+// (round to nearest even; both differences are exact in f32), stored to the three 1 KiB images of its block of 64 lanes.
+__device__ __forceinline__ void gather_split_lane(const float* __restrict__ src, const uint8_t* __restrict__ mask, const int32_t* __restrict__ idx, int64_t i, uint4* __restrict__ dst) {
+  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+  const int4 k0 = *reinterpret_cast<const int4*>(idx + i * 8), k1 = *reinterpret_cast<const int4*>(idx + i * 8 + 4);
+  const int k[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
+  bf16x8 h, m, l;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float v = gather_one(src, mask, k[e]);
+    const __bf16 hh = (__bf16)v;
+    const float r1 = v - (float)hh;
+    const __bf16 mm = (__bf16)r1;
+    h[e] = hh; m[e] = mm; l[e] = (__bf16)(r1 - (float)mm);
+  }
+  const int64_t b = i >> 6;
+  const int lane = (int)(i & 63);
+  dst[(b * 3 + 0) * 64 + lane] = __builtin_bit_cast(uint4, h);
+  dst[(b * 3 + 1) * 64 + lane] = __builtin_bit_cast(uint4, m);
+  dst[(b * 3 + 2) * 64 + lane] = __builtin_bit_cast(uint4, l);
+}
+
 __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ src, const uint8_t* __restrict__ mask, const int32_t* __restrict__ idx, int64_t n, float* __restrict__ dst) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int32_t k = idx[i];
-    float v = 0.f;
-    if (k >= 0 && (!mask || mask[k])) v = src[k];
-    dst[i] = v;
+    dst[i] = gather_one(src, mask, idx[i]);
   }
 }
 
-// Weight stream of the operand-split kernels (fused_ar_split_impl.h): per block of 64 lanes x 8 weights, three 1 KiB bf16 images
-// h = bf16(w), m = bf16(w - h), l = bf16(w - h - m) (round to nearest even; both differences are exact in f32).
+// Weight stream of the operand-split kernels: per block of 64 lanes x 8 weights, three 1 KiB bf16 images (gather_split_lane).
 __global__ __launch_bounds__(256) void gather_split_kernel(const float* __restrict__ src, const uint8_t* __restrict__ mask, const int32_t* __restrict__ idx, int64_t n_lanes,
                                                            uint4* __restrict__ dst) {
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_lanes; i += (int64_t)gridDim.x * 256) {
-    const int4 k0 = *reinterpret_cast<const int4*>(idx + i * 8), k1 = *reinterpret_cast<const int4*>(idx + i * 8 + 4);
-    const int k[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
-    bf16x8 h, m, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float v = 0.f;
-      if (k[e] >= 0 && (!mask || mask[k[e]])) v = src[k[e]];
-      const __bf16 hh = (__bf16)v;
-      const float r1 = v - (float)hh;
-      const __bf16 mm = (__bf16)r1;
-      const float r2 = r1 - (float)mm;
-      h[e] = hh; m[e] = mm; l[e] = (__bf16)r2;
-    }
-    const int64_t b = i >> 6;
-    const int lane = (int)(i & 63);
-    dst[(b * 3 + 0) * 64 + lane] = __builtin_bit_cast(uint4, h);
-    dst[(b * 3 + 1) * 64 + lane] = __builtin_bit_cast(uint4, m);
-    dst[(b * 3 + 2) * 64 + lane] = __builtin_bit_cast(uint4, l);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_lanes; i += (int64_t)gridDim.x * 256) gather_split_lane(src, mask, idx, i, dst);
 }
 
 // Weight stream of the two-part split kernels (fused_ar_half_impl.h): per block two 1 KiB f16 images h = f16(w s), l = f16(w s - h), s a power of two.
@@ -392,8 +352,7 @@ __global__ __launch_bounds__(256) void gather_split_f16_kernel(const float* __re
     f16x8 h, l;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float v = 0.f;
-      if (k[e] >= 0 && (!mask || mask[k[e]])) v = src[k[e]] * scale;
+      const float v = gather_one(src, mask, k[e]) * scale;
       const _Float16 hh = (_Float16)v;
       h[e] = hh; l[e] = (_Float16)(v - (float)hh);
     }
@@ -412,7 +371,6 @@ struct GatherMulti {
   struct One { const float* src; const uint8_t* mask; const int32_t* idx; int64_t count; void* dst; int split; } g[8];
 };
 __global__ __launch_bounds__(256) void gather_multi_kernel(GatherMulti m) {
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
   const int b = (int)blockIdx.x;
   GatherMulti::One g = m.g[0];
   int base = 0;
@@ -421,32 +379,10 @@ __global__ __launch_bounds__(256) void gather_multi_kernel(GatherMulti m) {
     if (k < m.n && b >= m.start[k]) { g = m.g[k]; base = m.start[k]; }
   const int64_t i = (int64_t)(b - base) * 256 + threadIdx.x;
   if (!g.split) {
-    if (i >= g.count) return;
-    const int32_t k = g.idx[i];
-    float v = 0.f;
-    if (k >= 0 && (!g.mask || g.mask[k])) v = g.src[k];
-    reinterpret_cast<float*>(g.dst)[i] = v;
-    return;
+    if (i < g.count) reinterpret_cast<float*>(g.dst)[i] = gather_one(g.src, g.mask, g.idx[i]);
+  } else if (i < g.count * 64) {
+    gather_split_lane(g.src, g.mask, g.idx, i, reinterpret_cast<uint4*>(g.dst));
   }
-  if (i >= g.count * 64) return;
-  const int4 k0 = *reinterpret_cast<const int4*>(g.idx + i * 8), k1 = *reinterpret_cast<const int4*>(g.idx + i * 8 + 4);
-  const int k[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
-  bf16x8 h, mm_, l;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    float v = 0.f;
-    if (k[e] >= 0 && (!g.mask || g.mask[k[e]])) v = g.src[k[e]];
-    const __bf16 hh = (__bf16)v;
-    const float r1 = v - (float)hh;
-    const __bf16 mm = (__bf16)r1;
-    h[e] = hh; mm_[e] = mm; l[e] = (__bf16)(r1 - (float)mm);
-  }
-  const int64_t blk = i >> 6;
-  const int lane = (int)(i & 63);
-  uint4* dst = reinterpret_cast<uint4*>(g.dst);
-  dst[(blk * 3 + 0) * 64 + lane] = __builtin_bit_cast(uint4, h);
-  dst[(blk * 3 + 1) * 64 + lane] = __builtin_bit_cast(uint4, mm_);
-  dst[(blk * 3 + 2) * 64 + lane] = __builtin_bit_cast(uint4, l);
 }
 
 }  // namespace zk
@@ -510,8 +446,8 @@ int zk_gather_multi(int n, const zk_gather_desc_v1* descs, void* stream) {
 #define AR_NR 3
 #endif
 typedef RingT<AR_CH, AR_NR> Ring24x3;  // 3 x 24 KiB; 2 x 48 and 3 x 48 tiles measured within +-1 %
-static int ar_base_lds_floats(int bias_floats) { return AR_CH * AR_NR * AR_TF + bias_floats + 1024 + 256; }  // ring + bias + feature map + skip words
-int zk_ar_lds_bytes(int variant, int bias_floats) { return (ar_base_lds_floats(bias_floats) + 8 * 16 * 260) * (int)sizeof(float); }  // upper bound incl. x/y tiles
+static int ar_lds_bytes(int bias_floats, bool xlds, int xs) { return ArLds::bytes(AR_CH * AR_NR * AR_TF, bias_floats, xlds ? AR_WAVES : 0, xs); }
+int zk_ar_lds_bytes(int variant, int bias_floats) { return ar_lds_bytes(bias_floats, true, 260); }  // upper bound incl. x/y tiles
 
 // uni_kind: 0 = affine (total 2), 1 = RQS with 8 bins (total 23); contract in include/zuko_amd.h.
 struct ArPartial {  // optional: evaluate only last-layer groups [g0, g1) and the prefix of the network they depend on
@@ -538,7 +474,7 @@ static int ar_launch(const ArPartial& part, bool inverse, int uni_kind, int64_t 
                      void* ladj, int accumulate, const void* wstream, const void* bias, int bias_floats, const uint32_t* skip, const int32_t* featmap,
                      int n_layers, int n_groups, int n_chunks, int act, double bound, double slope, int variant, void* stream) {
   if (N <= 0) return 0;
-  if (n_groups * 8 > 1024 || n_groups > 256) return ZK_EINVAL;
+  if (n_groups * 8 > ArLds::FMAP_WORDS || n_groups > ArLds::SKIP_WORDS) return ZK_EINVAL;
   if (n_layers < 2 || DIN > (part.static_fn ? 512 : 256) || DIN < D || DIN % 4 || ldx % 4 || ((uintptr_t)x % 16) || n_chunks < 1) return ZK_EINVAL;
   ArArgs a{};
   a.N = N; a.D = D; a.DIN = DIN;
@@ -584,10 +520,9 @@ static int ar_launch(const ArPartial& part, bool inverse, int uni_kind, int64_t 
   // stage x / results through LDS when rows are float4-addressable and the tiles fit beside the ring
   a.xs = ((D + 3) / 4) * 4 + 4;  // +4 words: 16-byte aligned rows whose stride is not a multiple of 32 banks
   const bool vec_ok = (D % 4 == 0) && (ldy % 4 == 0) && ((uintptr_t)y % 16 == 0) && (!inverse || ((ldyin % 4 == 0) && ((uintptr_t)yin % 16 == 0)));
-  a.xlds = vec_ok && (ar_base_lds_floats(bias_floats) + 8 * 16 * a.xs) * 4 <= 160 * 1024;
-  const int lds = (ar_base_lds_floats(bias_floats) + (a.xlds ? 8 * 16 * a.xs : 0)) * (int)sizeof(float);
+  a.xlds = vec_ok && ar_lds_bytes(bias_floats, true, a.xs) <= 160 * 1024;
+  const int lds = ar_lds_bytes(bias_floats, a.xlds, a.xs);
   if (lds > 160 * 1024) return ZK_EINVAL;
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
   const void* fn = nullptr;
 #define ZK_AR_PICK(UNI)                                                                                                                     \
   (inverse ? (a.xlds ? (const void*)ar_kernel<UNI, true, Ring24x3, true> : (const void*)ar_kernel<UNI, true, Ring24x3, false>)            \
@@ -609,35 +544,10 @@ static int ar_launch(const ArPartial& part, bool inverse, int uni_kind, int64_t 
     else if (uni_kind == 3) fn = (const void*)ar_kernel<UniRqs16, false, Ring24x3, true, true>;
     else return ZK_EINVAL;
   }
-  hipError_t e = hipSuccess;
-  {  // the opt-in to > 64 KiB of dynamic LDS is per function: set it once (and again only if a larger size is asked for)
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      g = lds;
-    }
-  }
-  void* kargs[] = {&a};
-  e = hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds(fn, 256, 512, lds, a, stream);
 }
 
-// (argument block: include/zuko_amd.h — every entry point checks struct_size / version before it reads a field)
-// A caller compiled against the first layout of version 1 (which ended with gh3) passes a SHORTER block: it is accepted and the fields
-// it does not have (phi_packed, gl_nodes01, gl_weights01, eps) read as zero — the point of carrying struct_size.  A block longer than this
-// library knows, another version, or one cut inside the original fields is ZK_EINVAL.
-static bool ar_args_norm(const zk_ar_args_v1* p, zk_ar_args_v1* out) {
-  if (!p || p->version != 1 || p->struct_size < offsetof(zk_ar_args_v1, phi_packed) || p->struct_size > sizeof(zk_ar_args_v1)) return false;
-  std::memset(out, 0, sizeof(*out));
-  std::memcpy(out, p, p->struct_size);
-  out->struct_size = sizeof(zk_ar_args_v1);
-  return true;
-}
+// (argument block: zk_ar_common.h, ar_args_norm)
 #define AR_ARGS_OK(args) (ar_args_norm(args, &args##_norm_) ? ((args) = &args##_norm_, true) : false)
 
 static int ar_launch_v1(const ArPartial& part, bool inverse, const zk_ar_args_v1& p, void* stream) {
@@ -710,23 +620,31 @@ int zk_ar_forward_train(const zk_ar_args_v1* args, void* stream) {
 // hidden layer's pre-activations goes ([N, width_l], sorted unit order), y [N, D] (row stride ldy) = the gradient w.r.t. the
 // conditioner's input.  wstream = the kernel's weight stream (transposed masked weights in its tile order), n_chunks its length.
 typedef int (*ars_dgrad_fn)(const ArArgs* a, int abi, int args_bytes, void* stream);
-int zk_ar_dgrad_chain(const zk_ar_args_v1* args, void* stream) {
-  zk_ar_args_v1 args_norm_;
-  if (!AR_ARGS_OK(args) || !args->launcher || !args->x || !args->y || !args->wstream) return ZK_EINVAL;
-  const int n = args->n_layers;
-  if (n < 2 || n > 4 || args->N < 0 || args->N > 0x7fffffff) return ZK_EINVAL;
-  if (args->N == 0) return 0;
+// What the three backward entry points share: the checked block's common fields, then the launch of the generated kernel.  `gated` chain layers:
+// layer c gates with (and yields the gradient of) hidden layer gated - c (1-based): h / gh in reverse.
+static bool ar_chain_args_ok(const zk_ar_args_v1* args) {
+  return args->launcher && args->x && args->y && args->wstream && args->n_layers >= 2 && args->n_layers <= 4 && args->N >= 0 && args->N <= 0x7fffffff;
+}
+static ArArgs ar_chain_args(const zk_ar_args_v1* args, int chain_layers, int gated) {
   const void* hs[3] = {args->h1, args->h2, args->h3};
   void* gs[3] = {args->gh1, args->gh2, args->gh3};
   ArArgs a{};
-  a.x = (const float*)args->x; a.ldx = args->ldx; a.N = args->N; a.D = args->D; a.DIN = args->DIN; a.L = n - 1; a.n_chunks = args->n_chunks;
+  a.x = (const float*)args->x; a.ldx = args->ldx; a.N = args->N; a.D = args->D; a.DIN = args->DIN; a.L = chain_layers; a.n_chunks = args->n_chunks;
   a.stream = (const float*)args->wstream;
   a.phi_out = (float*)args->y; a.ldphi = args->ldy;
-  for (int c = 0; c + 2 < n; ++c) {  // chain layer c gates with (and yields the gradient of) hidden layer n - 2 - c (1-based)
-    a.gate[c] = (const float*)hs[n - 3 - c];
-    a.act_out[c] = (float*)gs[n - 3 - c];
+  for (int c = 0; c < gated; ++c) {
+    a.gate[c] = (const float*)hs[gated - 1 - c];
+    a.act_out[c] = (float*)gs[gated - 1 - c];
   }
-  return ((ars_dgrad_fn)args->launcher)(&a, ARS_ABI, (int)sizeof(ArArgs), stream);
+  return a;
+}
+static int ar_chain_launch(const zk_ar_args_v1* args, const ArArgs& a, void* stream) { return ((ars_dgrad_fn)args->launcher)(&a, ARS_ABI, (int)sizeof(ArArgs), stream); }
+
+int zk_ar_dgrad_chain(const zk_ar_args_v1* args, void* stream) {
+  zk_ar_args_v1 args_norm_;
+  if (!AR_ARGS_OK(args) || !ar_chain_args_ok(args)) return ZK_EINVAL;
+  if (args->N == 0) return 0;
+  return ar_chain_launch(args, ar_chain_args(args, args->n_layers - 1, args->n_layers - 2), stream);
 }
 
 // zk_ar_dgrad_chain extended to the LAST linear layer: x = gradient of the packed parameters phi [N, DIN = features * total] (row stride
@@ -735,21 +653,11 @@ int zk_ar_dgrad_chain(const zk_ar_args_v1* args, void* stream) {
 // (zuko_amd/static_ar.py: chain_split_tables), whose first layer streams x from global memory.
 int zk_ar_dgrad_full(const zk_ar_args_v1* args, void* stream) {
   zk_ar_args_v1 args_norm_;
-  if (!AR_ARGS_OK(args) || !args->launcher || !args->x || !args->y || !args->wstream) return ZK_EINVAL;
-  const int n = args->n_layers;
-  if (n < 2 || n > 4 || args->N < 0 || args->N > 0x7fffffff) return ZK_EINVAL;
+  if (!AR_ARGS_OK(args) || !ar_chain_args_ok(args)) return ZK_EINVAL;
   if (args->N == 0) return 0;
-  const void* hs[3] = {args->h1, args->h2, args->h3};
-  void* gs[3] = {args->gh1, args->gh2, args->gh3};
-  ArArgs a{};
-  a.x = (const float*)args->x; a.ldx = args->ldx; a.N = args->N; a.D = args->D; a.DIN = args->DIN; a.L = n; a.n_chunks = args->n_chunks;
-  a.stream = (const float*)args->wstream;
-  a.phi_out = (float*)args->y; a.ldphi = args->ldy; a.accumulate = args->accumulate;
-  for (int c = 0; c + 1 < n; ++c) {  // chain layer c gates with (and yields the gradient of) hidden layer n - 1 - c (1-based)
-    a.gate[c] = (const float*)hs[n - 2 - c];
-    a.act_out[c] = (float*)gs[n - 2 - c];
-  }
-  return ((ars_dgrad_fn)args->launcher)(&a, ARS_ABI, (int)sizeof(ArArgs), stream);
+  ArArgs a = ar_chain_args(args, args->n_layers, args->n_layers - 1);
+  a.accumulate = args->accumulate;
+  return ar_chain_launch(args, a, stream);
 }
 
 // The whole backward of one autoregressive transform (x = cat(features, context) as for the forward) up to the weight gradients, in one launch of a generated kernel
@@ -758,25 +666,16 @@ int zk_ar_dgrad_full(const zk_ar_args_v1* args, void* stream) {
 // runs from there through every linear layer (gh1 .. = gradients of the hidden pre-activations); y = d loss / dx = chain + direct term.
 int zk_ar_backward_full(const zk_ar_args_v1* args, void* stream) {
   zk_ar_args_v1 args_norm_;
-  if (!AR_ARGS_OK(args) || !args->launcher || !args->x || !args->y || !args->wstream || !args->phi || !args->x_out || !args->y_in || !args->ladj || !args->featmap) return ZK_EINVAL;
-  const int n = args->n_layers;
-  if (n < 2 || n > 4 || args->N < 0 || args->N > 0x7fffffff || args->uni_kind < 0 || args->uni_kind > 1 || args->DIN < args->D || args->D < 1) return ZK_EINVAL;
+  if (!AR_ARGS_OK(args) || !ar_chain_args_ok(args) || !args->phi || !args->x_out || !args->y_in || !args->ladj || !args->featmap) return ZK_EINVAL;
+  if (args->uni_kind < 0 || args->uni_kind > 1 || args->DIN < args->D || args->D < 1) return ZK_EINVAL;
   if (args->N == 0) return 0;
-  const void* hs[3] = {args->h1, args->h2, args->h3};
-  void* gs[3] = {args->gh1, args->gh2, args->gh3};
-  ArArgs a{};
-  a.x = (const float*)args->x; a.ldx = args->ldx; a.N = args->N; a.D = args->D; a.DIN = args->DIN; a.L = n; a.NG = args->n_groups; a.n_chunks = args->n_chunks;
-  a.stream = (const float*)args->wstream; a.featmap = args->featmap;
-  a.phi_out = (float*)args->y; a.ldphi = args->ldy; a.accumulate = args->accumulate;
+  ArArgs a = ar_chain_args(args, args->n_layers, args->n_layers - 1);
+  a.NG = args->n_groups; a.featmap = args->featmap; a.accumulate = args->accumulate;
   a.gy = (const float*)args->y_in; a.ldgy = args->ldo; a.gl = (const float*)args->ladj;
   a.phi_in = (const float*)args->phi; a.gphi_out = (float*)args->x_out; a.ldpin = args->ldphi; a.phi_packed = 1;
   a.bound = (float)args->bound; a.ls = (float)log(args->slope);
-  for (int c = 0; c + 1 < n; ++c) {
-    a.gate[c] = (const float*)hs[n - 2 - c];
-    a.act_out[c] = (float*)gs[n - 2 - c];
-  }
   a.amax[0] = args->amax0; a.amax[1] = args->amax1; a.amax[2] = args->amax2; a.amax[3] = args->amax3;
-  return ((ars_dgrad_fn)args->launcher)(&a, ARS_ABI, (int)sizeof(ArArgs), stream);
+  return ar_chain_launch(args, a, stream);
 }
 
 // One sweep of the autoregressive inverse (zuko/transforms.py:997-998): x_out = univariate(conditioner(x_cond)).inv(y).

@@ -17,10 +17,6 @@
 //   * per accumulator the blocks arrive in the same order (in-pairs ascending) as in a static-shape split kernel, and a block the static kernel drops
 //     (all zero) adds exact zeros here: the two are BIT-IDENTICAL (tests/test_gpu_flows.py::test_generic_split_kernel_equals_the_static_one).
 // Forward only (inverse sweeps and partial sweeps stay on fused_ar.hip's f32 instruction); the spline kinds have a diagnostic twin (DIAG).
-#include <cstring>
-#include <mutex>
-#include <unordered_map>
-
 #include "../../include/zuko_amd.h"
 #include "fused_ar_split_impl.h"
 
@@ -125,29 +121,24 @@ __device__ __forceinline__ void gs_hidden_layer(GsRing& ring, const uint32_t* __
 
 template <typename Uni, bool XLDS, bool DIAG = false> __global__ __launch_bounds__(512, 2) void ar_gsplit_kernel(ArArgs a) {
   constexpr int NT = Uni::NT, FPL = Uni::FPL, TOTAL = Uni::TOTAL;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
-  float* ring_lds = gs_lds;
-  float* bias_lds = gs_lds + GS_NR * GS_CH * AR_TF;
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
 
   GsRing ring;
-  ring.lds = ring_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ring_lds) + (unsigned)lane * 16u;
+  ring.lds = gs_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
+  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)gs_lds) + (unsigned)lane * 16u;
   ring.load_chunk = 0; ring.load_slot = 0;
 #pragma unroll
   for (int i = 0; i < GS_NR - 1; ++i) ring.issue();
   ring.slot = GS_NR - 1;
   ring.pos = GS_CH;
 
-  for (int i = tid; i < a.bias_floats; i += 512) bias_lds[i] = a.bias[i];
-  int* fmap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);  // feature map of the last layer
-  int* skip_lds = fmap_lds + 1024;                                   // skip words of every layer: LDS copies (a vector-memory load in the pass would wait behind the ring DMAs)
-  float* xr = reinterpret_cast<float*>(fmap_lds + 1024 + 256) + wave * 16 * a.xs + j * a.xs;  // wave-private [16 samples x D] tile (XLDS)
-  for (int i = tid; i < a.NG * 4 * FPL; i += 512) fmap_lds[i] = a.featmap[i];
-  for (int i = tid; i < (a.L - 1) * 4 + a.NG; i += 512) skip_lds[i] = (int)a.skip[i];
-  __syncthreads();
+  float* const bias_lds = gs_lds + GS_NR * GS_CH * AR_TF;
+  int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
+  const int* const skip_lds = ArLds::skip(fmap_lds);  // skip words of EVERY layer: LDS copies (a vector-memory load in the pass would wait behind the ring DMAs)
+  float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  ArLds::stage<512>(a, tid, bias_lds, fmap_lds, a.NG * 4 * FPL, 0, (a.L - 1) * 4 + a.NG);
+  const ArFids<0, FPL, false> fids(fmap_lds, q);
 
   const float* bias_last = bias_lds + (a.L - 1) * 256;
   const int* skip_last = skip_lds + (a.L - 1) * 4;
@@ -166,7 +157,7 @@ template <typename Uni, bool XLDS, bool DIAG = false> __global__ __launch_bounds
     // ---- input tile: xin[it][r] = input[16 it + 4 q + r], then its three-way split as the first layer's B operands ----------------
     ArxB in[AR_T / 2];
     f32x4 out[AR_T];
-    float poison = 0.f;
+    float poison;
     {
       f32x4 xin[AR_T];
 #pragma unroll
@@ -178,15 +169,7 @@ template <typename Uni, bool XLDS, bool DIAG = false> __global__ __launch_bounds
         }
         xin[it] = v;
       }
-      // a NaN / inf input makes every parameter of its sample NaN in the reference (x * (mask * W), zuko/nn.py:217-218): flag the sample (fused_ar.hip)
-      int bad = 0;
-#pragma unroll
-      for (int it = 0; it < AR_T; ++it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bad |= !(fabsf(xin[it][r]) < __builtin_inff());
-      bad |= __shfl_xor(bad, 16, 64);
-      bad |= __shfl_xor(bad, 32, 64);
-      if (bad) poison = __builtin_nanf("");
+      poison = ar_poison_of<AR_T>(xin);
       if (XLDS) {
 #pragma unroll
         for (int it = 0; it < AR_T; ++it) {
@@ -251,12 +234,7 @@ template <typename Uni, bool XLDS, bool DIAG = false> __global__ __launch_bounds
       const uint32_t pairs = (bits | (bits >> 1)) & 0x5555u;
       int fid[FPL];
       float xv[FPL];
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) {
-        fid[fi] = fmap_lds[(g * 4 + q) * FPL + fi];
-        const int fc = fid[fi] < 0 ? 0 : fid[fi];
-        xv[fi] = XLDS ? xr[fc] : xrow[fc];
-      }
+      fids.template fetch<XLDS>(g, xr, xrow, fid, xv);
       f32x4 acc[NT];  // the accumulators start at the bias
       {
         const float* bg = bias_last + (g * NT) * 16 + 4 * q;
@@ -330,11 +308,7 @@ template <typename Uni, bool XLDS, bool DIAG = false> __global__ __launch_bounds
         }
       }
     }
-    if (a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
+    ar_ladj_store(a, lacc, n, live, q);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
@@ -343,7 +317,7 @@ template <typename Uni, bool XLDS, bool DIAG = false> __global__ __launch_bounds
 
 using namespace zk;
 
-static int gs_base_lds_floats(int bias_floats) { return GS_CH * GS_NR * AR_TF + bias_floats + 1024 + 256; }  // ring + bias + feature map + skip words
+static int gs_lds_bytes(int bias_floats, bool xlds, int xs) { return ArLds::bytes(GS_CH * GS_NR * AR_TF, bias_floats, xlds ? AR_WAVES : 0, xs); }
 
 // y, ladj of one masked autoregressive layer on the generic operand-split kernel.  Arguments as zk_ar_forward (include/zuko_amd.h) except `wstream`:
 // the operand-split stream of zuko_amd/fused.py: gsplit_gather (3 bf16 images per 16 x 32 block, written by zk_gather_split_bf16) and `n_chunks` its length
@@ -351,11 +325,9 @@ static int gs_base_lds_floats(int bias_floats) { return GS_CH * GS_NR * AR_TF + 
 // bin_out + knots_out set (uni_kind 1-3, D % 4 == 0): its diagnostic twin, as zk_ar_forward_diag is the f32 kernel's.
 extern "C" int zk_ar_forward_split(const zk_ar_args_v1* p, void* stream) {
   zk_ar_args_v1 q;
-  if (!p || p->version != 1 || p->struct_size < offsetof(zk_ar_args_v1, phi_packed) || p->struct_size > sizeof(zk_ar_args_v1)) return ZK_EINVAL;
-  std::memset(&q, 0, sizeof(q));
-  std::memcpy(&q, p, p->struct_size);
+  if (!ar_args_norm(p, &q)) return ZK_EINVAL;
   if (q.N <= 0) return 0;
-  if (q.n_groups < 1 || q.n_groups * 8 > 1024 || q.n_layers < 2 || (q.n_layers - 1) * 4 + q.n_groups > 256) return ZK_EINVAL;  // (feature map: 1024 LDS words; skip words: 4 per hidden layer + one per group in 256)
+  if (q.n_groups < 1 || q.n_groups * 8 > ArLds::FMAP_WORDS || q.n_layers < 2 || (q.n_layers - 1) * 4 + q.n_groups > ArLds::SKIP_WORDS) return ZK_EINVAL;  // (skip words: 4 per hidden layer + one per group)
   if (q.bias_floats % 4 || q.bias_floats < (q.n_layers - 1) * 256 + q.n_groups * 16) return ZK_EINVAL;  // (256 per hidden layer + NT x 16 per group; 16-byte rows behind it)
   if (q.DIN > 256 || q.DIN < q.D || q.DIN % 4 || q.ldx % 4 || ((uintptr_t)q.x % 16) || q.n_chunks < 1 || !q.x || !q.y || !q.wstream || !q.bias || !q.skip || !q.featmap) return ZK_EINVAL;
   ArArgs a{};
@@ -369,8 +341,8 @@ extern "C" int zk_ar_forward_split(const zk_ar_args_v1* p, void* stream) {
   a.n_tiles = (q.N + 127) / 128;
   a.xs = ((q.D + 3) / 4) * 4 + 4;
   const bool vec_ok = (q.D % 4 == 0) && (q.ldy % 4 == 0) && ((uintptr_t)q.y % 16 == 0);
-  a.xlds = vec_ok && (gs_base_lds_floats(q.bias_floats) + 8 * 16 * a.xs) * 4 <= 160 * 1024;
-  const int lds = (gs_base_lds_floats(q.bias_floats) + (a.xlds ? 8 * 16 * a.xs : 0)) * (int)sizeof(float);
+  a.xlds = vec_ok && gs_lds_bytes(q.bias_floats, true, a.xs) <= 160 * 1024;
+  const int lds = gs_lds_bytes(q.bias_floats, a.xlds, a.xs);
   if (lds > 160 * 1024) return ZK_EINVAL;
   const void* fn = nullptr;
 #define GS_PICK(UNI) (a.xlds ? (const void*)ar_gsplit_kernel<UNI, true> : (const void*)ar_gsplit_kernel<UNI, false>)
@@ -390,21 +362,5 @@ extern "C" int zk_ar_forward_split(const zk_ar_args_v1* p, void* stream) {
     else if (q.uni_kind == 3) fn = (const void*)ar_gsplit_kernel<UniRqs16, true, true>;
     else return ZK_EINVAL;
   }
-  hipError_t e = hipSuccess;
-  {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      g = lds;
-    }
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
-  void* kargs[] = {&a};
-  e = hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds(fn, 256, 512, lds, a, stream);
 }

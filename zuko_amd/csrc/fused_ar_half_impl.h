@@ -22,7 +22,8 @@
 // weights whose magnitudes spread over more than the f16 range WITHIN a layer keep the three-part kernel (zuko_amd/fused.py: eligibility).
 // A hidden value that overflows f32 becomes NaN for its sample, as in fused_ar_split_impl.h (inf - inf in the low part).
 //
-// Layout, ring, raw reads and counted waits are those of fused_ar_split_impl.h with TWO 1 KiB images (h, l) per block.
+// Stream layout, ring, raw reads and counted waits are those of fused_ar_split_impl.h with TWO 1 KiB images (h, l) per block; the frame around the
+// matrix part (LDS carve-up, input stage, epilogue) is zk_ar_common.h's.
 #pragma once
 #include "fused_ar_split_impl.h"
 
@@ -229,15 +230,7 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
           amax = fmaxf(amax, out[t][r]);                  // (non-negative after the ReLU; a NaN is skipped here and poisons through the split)
         }
     } else {
-      if constexpr (S::ACT != 0) {
-#pragma unroll 1
-        for (int rep = 0; rep < 1; ++rep) {
-#pragma unroll
-          for (int t = 0; t < HTL; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out[t][r] = act_f32(out[t][r], S::ACT);
-        }
-      }
+      ar_activate<S::ACT, HTL>(out, out);
 #pragma unroll
       for (int t = 0; t < HTL; ++t)
 #pragma unroll
@@ -263,15 +256,12 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
   constexpr int NG = S::NG;
   constexpr int NSTEP = S::GOFF[NG];  // (group, in pair) steps of the last layer, NT blocks each
   constexpr bool XLDS = S::XLDS;
-  constexpr bool FID_REGS = NG * FPL <= 32;
-  constexpr int DT = (S::D + 15) / 16;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
 
   Ring ring;
-  float* bias_lds = ars_lds + S::NR * S::CH * AR_TF;
+  // (ArRingS::start written out: called as the member, this kernel's first two requests come out with scalar base addresses and the loop's vector
+  //  base is built a second time — one vector instruction more, profiles/ar_frame/census.md)
   ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
   ring.load_chunk = 0; ring.load_slot = 0;
 #pragma unroll
@@ -294,20 +284,13 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
   f32x4 xnext[S::NIT];  // the NEXT tile's rows: requested a last layer ahead of the tile that consumes them
   if (ARH_PREFETCH) x_request(blockIdx.x, xnext);  // (the first tile's: landed behind the barrier below)
 
-  for (int i = tid; i < a.bias_floats; i += 64 * WAVES) bias_lds[i] = a.bias[i];
-  int* fmap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);  // same LDS layout as the f32 kernels
-  float* xr = reinterpret_cast<float*>(fmap_lds + 1024 + 256) + wave * 16 * a.xs + j * a.xs;
-  for (int i = tid; i < NG * 4 * FPL; i += 64 * WAVES) fmap_lds[i] = a.featmap[i];
-  __syncthreads();
+  float* const bias_lds = ars_lds + S::NR * S::CH * AR_TF;
+  int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
+  float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  ArLds::stage<64 * WAVES>(a, tid, bias_lds, fmap_lds, NG * 4 * FPL);
   const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
   const unsigned bias_last_addr = arx_lds_addr(bias_last + 4 * q);
-  int fids[FID_REGS ? NG * FPL : 1];
-  if constexpr (FID_REGS) {
-#pragma unroll
-    for (int i = 0; i < NG; ++i)
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) fids[i * FPL + fi] = fmap_lds[(i * 4 + q) * FPL + fi];
-  }
+  const ArFids<NG, FPL, (NG * FPL <= 32)> fids(fmap_lds, q);
 
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int64_t n = tile * (16 * WAVES) + wave * 16 + j;
@@ -317,7 +300,7 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
 
     ArhB in[S::TMAX / 2];
     f32x4 out[S::TMAX];
-    float poison = 0.f;
+    float poison;
     float inv_s;  // 2^-ea of the operands `in` currently holds
     {
       f32x4 xin[S::NIT + 1];
@@ -332,26 +315,13 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
         xin[it] = v;
       }
       xin[S::NIT] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // a NaN / inf input turns ALL parameters of its sample into NaN in the reference (x * 0 = NaN, zuko/nn.py:217-218)
-      int bad = 0;
+      poison = ar_poison_of<S::NIT>(xin);
       float amax = 0.f;
 #pragma unroll
       for (int it = 0; it < S::NIT; ++it)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          bad |= !(fabsf(xin[it][r]) < __builtin_inff());
-          amax = fmaxf(amax, fabsf(xin[it][r]));
-        }
-      bad |= __shfl_xor(bad, 16, 64);
-      bad |= __shfl_xor(bad, 32, 64);
-      if (bad) poison = __builtin_nanf("");
-      if constexpr (XLDS) {
-#pragma unroll
-        for (int it = 0; it < DT; ++it)
-          if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(xr + it * 16 + 4 * q) = xin[it];
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-      }
+        for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(xin[it][r]));
+      if constexpr (XLDS) ar_rows_in<S::D>(xr, q, xin);
       float s;
       arh_scale(amax, s, inv_s);
       if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
@@ -390,14 +360,7 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
       constexpr int g = g_, ST0 = S::GOFF[g], GN = S::GOFF[g + 1] - S::GOFF[g];
       int fid[FPL];
       float xin[FPL];
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) {
-        if constexpr (FID_REGS) fid[fi] = fids[g * FPL + fi];
-        else fid[fi] = fmap_lds[(g * 4 + q) * FPL + fi];
-        const int fc = fid[fi] < 0 ? 0 : fid[fi];
-        if constexpr (XLDS) xin[fi] = xr[fc];
-        else xin[fi] = xrow[fc];
-      }
+      fids.template fetch<XLDS>(g, xr, xrow, fid, xin);
       f32x4 acc[NT], bs[NT];  // the group's bias tiles: raw reads in front of the look-ahead request of the group's LAST block, whose counted wait settles them
       if constexpr (GN == 0) {
         const float* bg = bias_last + (g * NT) * 16 + 4 * q;
@@ -438,54 +401,12 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
           if (ARH_POISON_ONE) asm("" : "+v"(p[4 * t + r]));
         }
       });
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
-      auto ld = [&](int i) { return p[i]; };
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) {
-        const int f = fid[fi];
-        if (f >= 0) {
-          float yv, lj;
-          if (ARX_ABL == 3) {
-            yv = p[fi * TOTAL] + xin[fi]; lj = p[fi * TOTAL + 1];
-#pragma unroll
-            for (int i = 2; i < TOTAL; ++i) lj += p[fi * TOTAL + i];
-          } else if constexpr (DIAG) {
-            int kb = 0;
-            float ks[Uni::NKNOT];
-            Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj, &kb, ks);
-            if (live) {
-              a.bin_out[n * S::D + f] = kb;
-#pragma unroll
-              for (int jj = 0; jj < Uni::NKNOT; ++jj) a.knots_out[(n * S::D + f) * Uni::NKNOT + jj] = ks[jj];
-            }
-          } else
-          Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj);
-          if constexpr (XLDS) xr[f] = yv;
-          else if (live) a.y[n * a.ldy + f] = yv;
-          lacc += lj;
-        }
-      }
+      ar_uni_epilogue<Uni, DIAG, XLDS>(p, a, fid, xin, poison, xr, n, live, S::D, lacc);
     });
 #undef ARH_READ_LAST
-    auto ladj_out = [&]() ARS_ALWAYS_INLINE {
-      if (a.ladj) {
-        lacc += __shfl_xor(lacc, 16, 64);
-        lacc += __shfl_xor(lacc, 32, 64);
-        if (live && q == 0) a.ladj[n] = a.accumulate ? (ARH_PREFETCH ? ladj_in : a.ladj[n]) + lacc : lacc;
-      }
-    };
-    if (ARH_PREFETCH) ladj_out();  // in FRONT of the y rows: the wait for ladj_in (requested a tile ago) must not find stores it would have to sit out
-    if constexpr (XLDS) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      if (live) {
-#pragma unroll
-        for (int it = 0; it < DT; ++it)
-          if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(a.y + n * a.ldy + it * 16 + 4 * q) = *reinterpret_cast<const f32x4*>(xr + it * 16 + 4 * q);
-      }
-    }
-    if (!ARH_PREFETCH) ladj_out();
+    if (ARH_PREFETCH) ar_ladj_store<true>(a, lacc, n, live, q, ladj_in);  // in FRONT of the y rows: the wait for ladj_in (requested a tile ago) must not find stores it would have to sit out
+    if constexpr (XLDS) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
+    if (!ARH_PREFETCH) ar_ladj_store(a, lacc, n, live, q);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
@@ -501,7 +422,7 @@ template <class S, typename Uni> static int arh_launch(const ArArgs* in, int abi
   const bool vec_ok = (S::D % 4 == 0) && (a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0);
   if (S::XLDS != 0 && !vec_ok) return ZK_EINVAL;
   a.xlds = S::XLDS;
-  const int lds = (S::NR * S::CH * AR_TF + a.bias_floats + 1024 + 256 + (S::XLDS ? S::WAVES * 16 * a.xs : 0)) * (int)sizeof(float);
+  const int lds = ArLds::bytes(S::NR * S::CH * AR_TF, a.bias_floats, S::XLDS ? S::WAVES : 0, a.xs);
   if (lds > 160 * 1024) return ZK_EINVAL;
   const void* fn = nullptr;
   if ((a.bin_out != nullptr) != (a.knots_out != nullptr)) return ZK_EINVAL;
@@ -511,23 +432,7 @@ template <class S, typename Uni> static int arh_launch(const ArArgs* in, int abi
     fn = (const void*)arh_kernel<S, Uni, false>;
   }
   if (!fn) return ZK_EINVAL;
-  hipError_t e = hipSuccess;
-  {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      g = lds;
-    }
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
-  void* kargs[] = {&a};
-  e = hipLaunchKernel(fn, dim3(grid), dim3(64 * S::WAVES), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds(fn, 256, 64 * S::WAVES, lds, a, stream);
 }
 
 }  // namespace zk

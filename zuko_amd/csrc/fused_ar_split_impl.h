@@ -160,21 +160,7 @@ template <class S, int L, class Ring, bool TRAIN> __device__ __forceinline__ voi
   if constexpr (L < S::NH) {
     arx_hidden<S, L>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out);
     constexpr int HTL = S::HT[L];
-    if constexpr (S::ACT == 1) {
-#pragma unroll
-      for (int t = 0; t < HTL; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) out[t][r] = out[t][r] < 0.f ? 0.f : out[t][r];  // NaN stays NaN, as torch.relu
-    } else if constexpr (S::ACT != 0) {
-      // (a loop the compiler must not unroll over the activation's inline expansion, as in fused_ar_static_impl.h)
-#pragma unroll 1
-      for (int rep = 0; rep < 1; ++rep) {
-#pragma unroll
-        for (int t = 0; t < HTL; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) out[t][r] = act_f32(out[t][r], S::ACT);
-      }
-    }
+    ar_activate<S::ACT, HTL>(out, out);
     if constexpr (TRAIN) {
       if (live) {
 #pragma unroll
@@ -208,37 +194,18 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
   constexpr int NG = S::NG;
   constexpr int NSTEP = S::GOFF[NG];  // (group, in pair) steps of the last layer, NT blocks each
   constexpr bool XLDS = S::XLDS;
-  constexpr bool FID_REGS = NG * FPL <= 32 && !TRAIN;  // (the training instantiation holds phi for its stores as well: the feature ids stay in LDS there)
-  constexpr int DT = (S::D + 15) / 16;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
 
   Ring ring;
-  float* bias_lds = ars_lds + S::NR * S::CH * AR_TF;
-  ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
-#pragma unroll
-  for (int i = 0; i < S::NR - 1; ++i) ring.issue();
-  ring.slot = S::NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
-  ring.cur_off = ring.lds_off;
-
-  for (int i = tid; i < a.bias_floats; i += 64 * WAVES) bias_lds[i] = a.bias[i];
-  int* fmap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);  // same LDS layout as the f32 kernels
-  float* xr = reinterpret_cast<float*>(fmap_lds + 1024 + 256) + wave * 16 * a.xs + j * a.xs;
-  for (int i = tid; i < NG * 4 * FPL; i += 64 * WAVES) fmap_lds[i] = a.featmap[i];
-  __syncthreads();
+  ring.start(ars_lds, a.stream, a.n_chunks, wave, lane);
+  float* const bias_lds = ars_lds + S::NR * S::CH * AR_TF;
+  int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
+  float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  ArLds::stage<64 * WAVES>(a, tid, bias_lds, fmap_lds, NG * 4 * FPL);
   const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
   const unsigned bias_last_addr = arx_lds_addr(bias_last + 4 * q);
-  int fids[FID_REGS ? NG * FPL : 1];
-  if constexpr (FID_REGS) {
-#pragma unroll
-    for (int i = 0; i < NG; ++i)
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) fids[i * FPL + fi] = fmap_lds[(i * 4 + q) * FPL + fi];
-  }
+  const ArFids<NG, FPL, (NG * FPL <= 32 && !TRAIN)> fids(fmap_lds, q);  // (the training instantiation holds phi for its stores as well: the feature ids stay in LDS there)
 
   const bool uni_on = !TRAIN || a.y != nullptr;  // (training launch: y, ladj beside phi and the activations when the caller passes y)
   float mx[4] = {0.f, 0.f, 0.f, 0.f};
@@ -250,7 +217,7 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
 
     ArxB in[S::TMAX / 2];
     f32x4 out[S::TMAX];
-    float poison = 0.f;
+    float poison;
     {
       f32x4 xin[S::NIT + 1];
 #pragma unroll
@@ -266,7 +233,8 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
         }
       }
       xin[S::NIT] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // a NaN / inf input turns ALL parameters of its sample into NaN in the reference (x * 0 = NaN, zuko/nn.py:217-218)
+      // (the non-finite flag of zk_ar_common.h: ar_poison_of, written out — called as the helper, the training instantiation computes two |x| twice)
+      poison = 0.f;
       int bad = 0;
 #pragma unroll
       for (int it = 0; it < S::NIT; ++it)
@@ -275,13 +243,7 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
       bad |= __shfl_xor(bad, 16, 64);
       bad |= __shfl_xor(bad, 32, 64);
       if (bad) poison = __builtin_nanf("");
-      if constexpr (XLDS) {
-#pragma unroll
-        for (int it = 0; it < DT; ++it)
-          if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(xr + it * 16 + 4 * q) = xin[it];
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-      }
+      if constexpr (XLDS) ar_rows_in<S::D>(xr, q, xin);
 #pragma unroll
       for (int p = 0; p < (S::NIT + 1) / 2; ++p) arx_split(xin[2 * p], xin[2 * p + 1], in[p]);
     }
@@ -302,14 +264,7 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
       constexpr int g = g_, ST0 = S::GOFF[g], GN = S::GOFF[g + 1] - S::GOFF[g];
       int fid[FPL];
       float xin[FPL];
-#pragma unroll
-      for (int fi = 0; fi < FPL; ++fi) {
-        if constexpr (FID_REGS) fid[fi] = fids[g * FPL + fi];
-        else fid[fi] = fmap_lds[(g * 4 + q) * FPL + fi];
-        const int fc = fid[fi] < 0 ? 0 : fid[fi];
-        if constexpr (XLDS) xin[fi] = xr[fc];
-        else xin[fi] = xrow[fc];
-      }
+      fids.template fetch<XLDS>(g, xr, xrow, fid, xin);
       f32x4 acc[NT];  // the accumulators start at the bias (raw reads, older than every image requested below: the first block's wait settles them all)
       if constexpr (GN > 0) {
         ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = arx_lds_raw<(g * NT + decltype(t)::value) * 64>(bias_last_addr); });
@@ -361,51 +316,10 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
           }
         }
       }
-      if (uni_on) {
-#pragma unroll
-        for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
-        auto ld = [&](int i) { return p[i]; };
-#pragma unroll
-        for (int fi = 0; fi < FPL; ++fi) {
-          const int f = fid[fi];
-          if (f >= 0) {
-            float yv, lj;
-            if (ARX_ABL == 3) {
-              yv = p[fi * TOTAL] + xin[fi]; lj = p[fi * TOTAL + 1];
-#pragma unroll
-              for (int i = 2; i < TOTAL; ++i) lj += p[fi * TOTAL + i];
-            } else if constexpr (DIAG) {
-              int kb = 0;
-              float ks[Uni::NKNOT];
-              Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj, &kb, ks);
-              if (live) {
-                a.bin_out[n * S::D + f] = kb;
-#pragma unroll
-                for (int jj = 0; jj < Uni::NKNOT; ++jj) a.knots_out[(n * S::D + f) * Uni::NKNOT + jj] = ks[jj];
-              }
-            } else
-            Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj);
-            if constexpr (XLDS) xr[f] = yv;
-            else if (live) a.y[n * a.ldy + f] = yv;
-            lacc += lj;
-          }
-        }
-      }
+      if (uni_on) ar_uni_epilogue<Uni, DIAG, XLDS>(p, a, fid, xin, poison, xr, n, live, S::D, lacc);
     });
-    if constexpr (XLDS) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      if (live && uni_on) {
-#pragma unroll
-        for (int it = 0; it < DT; ++it)
-          if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(a.y + n * a.ldy + it * 16 + 4 * q) = *reinterpret_cast<const f32x4*>(xr + it * 16 + 4 * q);
-      }
-    }
-    if (uni_on && a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
+    if constexpr (XLDS) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live && uni_on);
+    if (uni_on) ar_ladj_store(a, lacc, n, live, q);
   }
   if constexpr (TRAIN) arx_amax_flush(a, mx, blockIdx.x * WAVES + wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
@@ -518,20 +432,11 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arxd_stack
 template <class S> __global__ __launch_bounds__(512, 2) void arxd_kernel(ArArgs a) {
   typedef ArRingS<8, S::CH> Ring;
   static_assert(S::NH >= 2 && S::NH <= 4 && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::WAVES == 8, "dgrad chain: the last layer + up to three gated layers, widths <= 256");
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
+  const ArLane ln;
+  const int lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
   Ring ring;
-  ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
-#pragma unroll
-  for (int i = 0; i < ARS_NR - 1; ++i) ring.issue();
-  ring.slot = ARS_NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
-  ring.cur_off = ring.lds_off;
-  float* zero_lds = ars_lds + ARS_NR * S::CH * AR_TF;  // "bias image" of a layer without bias
-  for (int i = tid; i < S::TMAX * 16 + 16; i += 512) zero_lds[i] = 0.f;
+  ring.start(ars_lds, a.stream, a.n_chunks, wave, lane);
+  float* zero_lds = ArChainLds<S::CH, S::TMAX>::template zero_fill<512>(ars_lds, ln.tid);
   __syncthreads();
   float mx[4] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
@@ -655,26 +560,19 @@ __device__ __forceinline__ void arxb_first(Ring& ring, const ArArgs& a, const in
   });
 }
 
+template <class S, typename Uni> using ArxbLds = ArChainLds<S::CH, S::TMAX, ((S::NG * 4 * Uni::FPL + 3) / 4) * 4>;  // (feature map rounded up to 16-byte rows)
+
 template <class S, typename Uni> __global__ __launch_bounds__(512, 2) void arxb_kernel(ArArgs a) {
   typedef ArRingS<8, S::CH> Ring;
   static_assert(S::NH >= 2 && S::NH <= 4 && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::WAVES == 8, "dgrad chain: the last layer + up to three gated layers, widths <= 256");
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
+  typedef ArxbLds<S, Uni> Lds;
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
   Ring ring;
-  ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
-#pragma unroll
-  for (int i = 0; i < ARS_NR - 1; ++i) ring.issue();
-  ring.slot = ARS_NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
-  ring.cur_off = ring.lds_off;
-  constexpr int NFMAP = ((S::NG * 4 * Uni::FPL + 3) / 4) * 4;
-  float* zero_lds = ars_lds + ARS_NR * S::CH * AR_TF;
-  int* fmap_lds = reinterpret_cast<int*>(zero_lds + S::TMAX * 16 + 16);
-  float* xr = reinterpret_cast<float*>(fmap_lds + NFMAP) + (wave * 16 + j) * a.xs;
-  for (int i = tid; i < S::TMAX * 16 + 16; i += 512) zero_lds[i] = 0.f;
+  ring.start(ars_lds, a.stream, a.n_chunks, wave, lane);
+  int* fmap_lds = Lds::fmap(ars_lds);
+  float* xr = Lds::rows(ars_lds) + (wave * 16 + j) * a.xs;
+  float* zero_lds = Lds::template zero_fill<512>(ars_lds, tid);
   for (int i = tid; i < S::NG * 4 * Uni::FPL; i += 512) fmap_lds[i] = a.featmap[i];
   __syncthreads();
   float mx[4] = {0.f, 0.f, 0.f, 0.f};
@@ -709,21 +607,9 @@ template <class S, typename Uni> static int arxb_launch(const ArArgs* in, int ab
     if (!a.gate[l] || !a.act_out[l] || ((uintptr_t)a.gate[l] % 16) || ((uintptr_t)a.act_out[l] % 16)) return ZK_EINVAL;
   a.n_tiles = (a.N + 127) / 128;
   a.xs = ((S::DOUT + 3) / 4) * 4 + 4;
-  constexpr int NFMAP = ((S::NG * 4 * Uni::FPL + 3) / 4) * 4;
-  const int lds = (ARS_NR * S::CH * AR_TF + S::TMAX * 16 + 16 + NFMAP + 8 * 16 * a.xs) * (int)sizeof(float);
+  const int lds = ArxbLds<S, Uni>::bytes(8 * 16 * a.xs);
   if (lds > 160 * 1024 || a.ldpin % 4 || ((uintptr_t)a.phi_in % 16) || ((uintptr_t)a.gphi_out % 16)) return ZK_EINVAL;
-  const void* fn = (const void*)arxb_kernel<S, Uni>;
-  static bool granted = false;
-  if (!granted) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    granted = true;
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
-  void* kargs[] = {&a};
-  hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds((const void*)arxb_kernel<S, Uni>, 256, 512, lds, a, stream);
 }
 
 template <class S> static int arxd_launch(const ArArgs* in, int abi, int args_bytes, void* stream) {
@@ -735,19 +621,7 @@ template <class S> static int arxd_launch(const ArArgs* in, int abi, int args_by
   for (int l = 0; l + 1 < S::NH; ++l)
     if (!a.gate[l] || !a.act_out[l] || ((uintptr_t)a.gate[l] % 16) || ((uintptr_t)a.act_out[l] % 16)) return ZK_EINVAL;
   a.n_tiles = (a.N + 127) / 128;
-  const int lds = (ARS_NR * S::CH * AR_TF + S::TMAX * 16 + 16) * (int)sizeof(float);
-  const void* fn = (const void*)arxd_kernel<S>;
-  static bool granted = false;
-  if (!granted) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    granted = true;
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
-  void* kargs[] = {&a};
-  hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds((const void*)arxd_kernel<S>, 256, 512, ArChainLds<S::CH, S::TMAX>::bytes(0), a, stream);
 }
 
 template <class S, typename Uni> static int arx_launch(const ArArgs* in, int abi, int args_bytes, int train, void* stream) {
@@ -760,7 +634,7 @@ template <class S, typename Uni> static int arx_launch(const ArArgs* in, int abi
   const bool vec_ok = (S::D % 4 == 0) && ((train && !a.y) || ((a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0)));
   if (S::XLDS != 0 && !vec_ok) return ZK_EINVAL;
   a.xlds = S::XLDS;
-  const int lds = (S::NR * S::CH * AR_TF + a.bias_floats + 1024 + 256 + (S::XLDS ? S::WAVES * 16 * a.xs : 0)) * (int)sizeof(float);
+  const int lds = ArLds::bytes(S::NR * S::CH * AR_TF, a.bias_floats, S::XLDS ? S::WAVES : 0, a.xs);
   if (lds > 160 * 1024) return ZK_EINVAL;
   const void* fn = nullptr;
   if ((a.bin_out != nullptr) != (a.knots_out != nullptr) || (a.bin_out && train)) return ZK_EINVAL;
@@ -772,24 +646,8 @@ template <class S, typename Uni> static int arx_launch(const ArArgs* in, int abi
     fn = (const void*)arx_kernel<S, Uni, false>;
   }
   if (!fn) return ZK_EINVAL;
-  hipError_t e = hipSuccess;
-  {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      g = lds;
-    }
-  }
   constexpr int MAXG = (S::WAVES == 4 && S::OCC == 2) ? 512 : 256;  // 4 wavefronts at two per SIMD: two independent workgroups per CU (one wavefront per SIMD each)
-  const unsigned grid = (unsigned)(a.n_tiles < MAXG ? a.n_tiles : MAXG);
-  void* kargs[] = {&a};
-  e = hipLaunchKernel(fn, dim3(grid), dim3(64 * S::WAVES), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds(fn, MAXG, 64 * S::WAVES, lds, a, stream);
 }
 
 }  // namespace zk

@@ -28,18 +28,13 @@
 //                                 one per SIMD); whether x / y rows are staged through a wave-private LDS image
 #pragma once
 #include "zk_ar_common.h"
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 #include <utility>
 
 namespace zk {
 
 #define ARS_CH 24
 #define ARS_NR 3
-#ifndef ARX_ABL
-#define ARX_ABL 0  // timing ablations of the operand-split kernel (scripts/split_ablate.py): 1 no DMA, 2 no MFMA, 3 no epilogue, 4 no barrier, 5 no LDS reads, 6 no conversions
-#endif
 #define ARS_ALWAYS_INLINE __attribute__((always_inline))
 
 template <class F, int... I> __device__ __forceinline__ void ars_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -78,6 +73,16 @@ template <int WAVES, int CH = ARS_CH, int NR = ARS_NR> struct ArRingS {
   unsigned cur_off;  // LDS byte address of the slot being read + lane * 16
   unsigned lds_off;  // LDS byte address of the ring
   int n_chunks, slot, load_chunk, load_slot, wave, lane;
+  // the first NR - 1 chunks are requested; the first read (position 0) advances onto slot 0
+  __device__ __forceinline__ void start(float* lds_, const float* stream_, int n_chunks_, int wave_, int lane_) {
+    lds = lds_; stream = stream_; n_chunks = n_chunks_; wave = wave_; lane = lane_;
+    load_chunk = 0; load_slot = 0;
+#pragma unroll
+    for (int i = 0; i < NR - 1; ++i) issue();
+    slot = NR - 1;
+    lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)lds);
+    cur_off = lds_off;
+  }
   template <int I> __device__ __forceinline__ void dma(const float* g, float* l) {
     if constexpr (I < PER) {
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, (I - PIVOT) * AR_TF * 4, 0);
@@ -134,6 +139,19 @@ template <int N, int NT> __device__ __forceinline__ void ars_settle_tiles(f32x4 
 }
 
 extern __shared__ __attribute__((aligned(16))) float ars_lds[];
+
+// LDS of a backward (dgrad chain) kernel:  ring | zero image ("bias" of layers without bias) | feature map (NFMAP words) | wave-private rows.
+// One definition for ars_dgrad_kernel, arxd_kernel (ring and zero image only) and arxb_kernel, and for their launchers.
+template <int CH, int TMAX, int NFMAP = 0> struct ArChainLds {
+  static constexpr int RING = ARS_NR * CH * AR_TF, ZERO = TMAX * 16 + 16;
+  static constexpr int bytes(int row_floats) { return (RING + ZERO + NFMAP + row_floats) * (int)sizeof(float); }
+  template <int THREADS> static __device__ __forceinline__ float* zero_fill(float* lds, int tid) {  // (the caller's workgroup barrier follows)
+    for (int i = tid; i < ZERO; i += THREADS) lds[RING + i] = 0.f;
+    return lds + RING;
+  }
+  static __device__ __forceinline__ int* fmap(float* lds) { return reinterpret_cast<int*>(lds + RING + ZERO); }
+  static __device__ __forceinline__ float* rows(float* lds) { return reinterpret_cast<float*>(fmap(lds) + NFMAP); }
+};
 
 // one hidden layer: out = W in + bias over the steps of the generated pattern
 template <class S, int L, class Ring> __device__ __forceinline__ void ars_hidden(Ring& ring, const float* bias_q, const f32x4 (&in)[S::TMAX], f32x4 (&out)[S::TMAX], bool rev) {
@@ -197,26 +215,7 @@ template <class S, int L, class Ring, bool TRAIN> __device__ __forceinline__ voi
   if constexpr (L < S::NH) {
     ars_hidden<S, L>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, rev);
     constexpr int HTL = S::HT[L], TO = 4 * ((HTL + 3) / 4);
-    if constexpr (S::ACT == 1) {
-#pragma unroll
-      for (int t = 0; t < TO; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) in[t][r] = out[t][r] < 0.f ? 0.f : out[t][r];  // NaN stays NaN, as torch.relu
-    } else if constexpr (S::ACT == 0) {
-#pragma unroll
-      for (int t = 0; t < TO; ++t) in[t] = out[t];
-    } else {
-      // ELU / tanh / SiLU / GELU / sigmoid / leaky ReLU: the same expressions as the generic kernel (act_f32), inside a loop the compiler
-      // must not unroll over the activation's inline expansion (64-128 copies of tanhf / erff made the generic kernel's epilogue
-      // instruction-cache bound)
-#pragma unroll 1
-      for (int rep = 0; rep < 1; ++rep) {
-#pragma unroll
-        for (int t = 0; t < TO; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) in[t][r] = act_f32(out[t][r], S::ACT);
-      }
-    }
+    ar_activate<S::ACT, TO>(in, out);  // (the same expressions as the generic kernel)
     if constexpr (TRAIN) {
       if (live) {
 #pragma unroll
@@ -236,16 +235,13 @@ template <class S, typename Uni, bool TRAIN> __global__ __launch_bounds__(64 * S
   constexpr int NG = S::NG;
   constexpr int NSTEP = P::n_last_steps();
   constexpr bool XLDS = S::XLDS;
-  constexpr bool FID_REGS = NG * FPL <= 32;
-  constexpr int DT = (S::D + 15) / 16;  // tiles that hold features
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
   const bool rev = a.l1rev != 0;
 
+  // (ring start-up and feature ids written out in this kernel: as ArRingS::start / ArFids its training instantiation gains vector moves,
+  //  profiles/ar_frame/census.md)
   Ring ring;
-  float* bias_lds = ars_lds + ARS_NR * ARS_CH * AR_TF;
   ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
   ring.load_chunk = 0; ring.load_slot = 0;
 #pragma unroll
@@ -253,15 +249,13 @@ template <class S, typename Uni, bool TRAIN> __global__ __launch_bounds__(64 * S
   ring.slot = ARS_NR - 1;
   ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
   ring.cur_off = ring.lds_off;
-
-  for (int i = tid; i < a.bias_floats; i += 64 * WAVES) bias_lds[i] = a.bias[i];
-  int* fmap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);  // same LDS layout as the generic kernel (fused_ar.hip)
-  float* xr = reinterpret_cast<float*>(fmap_lds + 1024 + 256) + wave * 16 * a.xs + j * a.xs;
-  for (int i = tid; i < NG * 4 * FPL; i += 64 * WAVES) fmap_lds[i] = a.featmap[i];
-  __syncthreads();
+  float* const bias_lds = ars_lds + ARS_NR * ARS_CH * AR_TF;
+  int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
+  float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  ArLds::stage<64 * WAVES>(a, tid, bias_lds, fmap_lds, NG * 4 * FPL);
   const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
-  // feature ids of this lane's slots in every group: constant over the launch, kept in registers when they fit (a per-group LDS read
-  // puts one exposed LDS round trip in front of the read of x that depends on it)
+  // feature ids of this lane's slots in every group: constant over the launch, kept in registers when they fit
+  constexpr bool FID_REGS = NG * FPL <= 32;
   int fids[FID_REGS ? NG * FPL : 1];
   if constexpr (FID_REGS) {
 #pragma unroll
@@ -283,25 +277,8 @@ template <class S, typename Uni, bool TRAIN> __global__ __launch_bounds__(64 * S
       if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = *reinterpret_cast<const f32x4*>(xrow + it * 16 + 4 * q);
       in[it] = v;
     }
-    // a NaN / inf input turns ALL parameters of its sample into NaN in the reference (x * 0 = NaN, zuko/nn.py:217-218)
-    float poison = 0.f;
-    {
-      int bad = 0;
-#pragma unroll
-      for (int it = 0; it < S::NIT; ++it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bad |= !(fabsf(in[it][r]) < __builtin_inff());
-      bad |= __shfl_xor(bad, 16, 64);
-      bad |= __shfl_xor(bad, 32, 64);
-      if (bad) poison = __builtin_nanf("");
-    }
-    if constexpr (XLDS) {
-#pragma unroll
-      for (int it = 0; it < DT; ++it)
-        if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(xr + it * 16 + 4 * q) = in[it];
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-    }
+    const float poison = ar_poison_of<S::NIT>(in);
+    if constexpr (XLDS) ar_rows_in<S::D>(xr, q, in);
 
     // ---- hidden layers ---------------------------------------------------------------------------------------------
     ars_hidden_stack<S, 0, Ring, TRAIN>(ring, bias_lds, q, in, out, rev, a, n, live);
@@ -314,7 +291,6 @@ template <class S, typename Uni, bool TRAIN> __global__ __launch_bounds__(64 * S
     }
     ars_for<NG>([&](auto g_) ARS_ALWAYS_INLINE {
       constexpr int g = g_, ST0 = S::GOFF[g], GN = S::GOFF[g + 1] - S::GOFF[g];
-      // operands of the epilogue are requested before the group's MFMAs: feature ids, x values and the bias from LDS
       int fid[FPL];
       float xin[FPL];
 #pragma unroll
@@ -361,36 +337,11 @@ template <class S, typename Uni, bool TRAIN> __global__ __launch_bounds__(64 * S
           }
         }
       } else {
-#pragma unroll
-        for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
-        auto ld = [&](int i) { return p[i]; };
-#pragma unroll
-        for (int fi = 0; fi < FPL; ++fi) {
-          const int f = fid[fi];
-          if (f >= 0) {
-            float yv, lj;
-            Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj);
-            if constexpr (XLDS) xr[f] = yv;
-            else if (live) a.y[n * a.ldy + f] = yv;
-            lacc += lj;
-          }
-        }
+        ar_uni_epilogue<Uni, false, XLDS, false>(p, a, fid, xin, poison, xr, n, live, S::D, lacc);
       }
     });
-    if constexpr (XLDS && !TRAIN) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      if (live) {
-#pragma unroll
-        for (int it = 0; it < DT; ++it)
-          if ((it + 1) * 16 <= S::D || it * 16 + 4 * q < S::D) *reinterpret_cast<f32x4*>(a.y + n * a.ldy + it * 16 + 4 * q) = *reinterpret_cast<const f32x4*>(xr + it * 16 + 4 * q);
-      }
-    }
-    if (!TRAIN && a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
+    if constexpr (XLDS && !TRAIN) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
+    if constexpr (!TRAIN) ar_ladj_store(a, lacc, n, live, q);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
@@ -432,20 +383,12 @@ template <class S, int L, class Ring> __device__ __forceinline__ void ars_dgrad_
 template <class S> __global__ __launch_bounds__(512, 2) void ars_dgrad_kernel(ArArgs a) {
   typedef ArRingS<8> Ring;
   static_assert(S::NH >= 1 && S::NH <= 4 && S::TMAX <= 16, "dgrad chain: up to three gated layers + the input layer, widths <= 256");
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, q = lane >> 4;
+  typedef ArChainLds<ARS_CH, S::TMAX> Lds;
+  const ArLane ln;
+  const int wave = ln.wave, j = ln.j, q = ln.q;
   Ring ring;
-  ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
-#pragma unroll
-  for (int i = 0; i < ARS_NR - 1; ++i) ring.issue();
-  ring.slot = ARS_NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
-  ring.cur_off = ring.lds_off;
-  float* zero_lds = ars_lds + ARS_NR * ARS_CH * AR_TF;  // "bias image" of a layer without bias
-  for (int i = tid; i < S::TMAX * 16 + 16; i += 512) zero_lds[i] = 0.f;
+  ring.start(ars_lds, a.stream, a.n_chunks, wave, ln.lane);
+  float* zero_lds = Lds::template zero_fill<512>(ars_lds, ln.tid);
   __syncthreads();
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int64_t n = tile * 128 + wave * 16 + j;
@@ -469,19 +412,7 @@ template <class S> static int ars_dgrad_launch(const ArArgs* in, int abi, int ar
   for (int l = 0; l + 1 < S::NH; ++l)
     if (!a.gate[l] || !a.act_out[l] || ((uintptr_t)a.gate[l] % 16) || ((uintptr_t)a.act_out[l] % 16)) return ZK_EINVAL;
   a.n_tiles = (a.N + 127) / 128;
-  const int lds = (ARS_NR * ARS_CH * AR_TF + S::TMAX * 16 + 16) * (int)sizeof(float);
-  const void* fn = (const void*)ars_dgrad_kernel<S>;
-  static bool granted = false;
-  if (!granted) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    granted = true;
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
-  void* kargs[] = {&a};
-  hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(512), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds((const void*)ars_dgrad_kernel<S>, 256, 512, ArChainLds<ARS_CH, S::TMAX>::bytes(0), a, stream);
 }
 
 // Launch of one instantiation; `a` arrives filled by the main library's argument checks (csrc/fused_ar.hip: zk_ar_forward_static).
@@ -497,7 +428,7 @@ template <class S, typename Uni> static int ars_launch(const ArArgs* in, int abi
   const bool vec_ok = (S::D % 4 == 0) && (train || ((a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0)));
   if (S::XLDS != 0 && !vec_ok) return ZK_EINVAL;
   a.xlds = S::XLDS;
-  const int lds = (ARS_NR * ARS_CH * AR_TF + a.bias_floats + 1024 + 256 + (S::XLDS ? S::WAVES * 16 * a.xs : 0)) * (int)sizeof(float);  // ring | bias | feature map | (skip words) | row tiles
+  const int lds = ArLds::bytes(ARS_NR * ARS_CH * AR_TF, a.bias_floats, S::XLDS ? S::WAVES : 0, a.xs);
   if (lds > 160 * 1024) return ZK_EINVAL;
   const void* fn = nullptr;
   if (train) {
@@ -506,23 +437,7 @@ template <class S, typename Uni> static int ars_launch(const ArArgs* in, int abi
     fn = (const void*)ars_kernel<S, Uni, false>;
   }
   if (!fn) return ZK_EINVAL;
-  hipError_t e = hipSuccess;
-  {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-      g = lds;
-    }
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
-  void* kargs[] = {&a};
-  e = hipLaunchKernel(fn, dim3(grid), dim3(64 * S::WAVES), kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  return ZK_LAUNCH_CHECK();
+  return ar_launch_dyn_lds(fn, 256, 64 * S::WAVES, lds, a, stream);
 }
 
 }  // namespace zk

@@ -1,7 +1,13 @@
-// zuko_amd — pieces shared by the fused autoregressive kernels (fused_ar.hip: generic tile-skipping kernel, inverse sweeps;
-// fused_ar_static.hip: the static-shape density kernel): launch arguments, activations, univariate epilogues.
+// zuko_amd — the FRAME shared by the fused autoregressive kernels (fused_ar.hip, fused_ar_gsplit.hip: the generic kernels; fused_ar_static_impl.h,
+// fused_ar_split_impl.h, fused_ar_half_impl.h: the templates of the generated static-shape kernels): launch arguments, LDS layout, lane
+// decomposition, table staging, the input stage (non-finite flag, row tiles), activations, the per-group operand fetch, the univariate epilogue,
+// the running log-derivative and the host's grant-and-launch tail.  The kernel files hold their matrix parts (block loops, operand split, waits).
 #pragma once
 #include "zk_univariate.h"
+#include <cstddef>
+#include <cstring>
+#include <mutex>
+#include <unordered_map>
 
 namespace zk {
 
@@ -11,6 +17,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define AR_WAVES 8
 #define AR_T 16   /* activation tiles (256 units) */
 #define ARS_ABI 9 /* contract between this library and the generated static-shape kernels (zuko_amd/static_ar.py): bump on any change of ArArgs */
+#ifndef ARX_ABL
+#define ARX_ABL 0  // timing ablations of the operand-split kernel (scripts/split_ablate.py): 1 no DMA, 2 no MFMA, 3 no epilogue, 4 no barrier, 5 no LDS reads, 6 no conversions
+#endif
 #ifndef ARH_POISON_ONE
 #define ARH_POISON_ONE 1  // probe builds: 0 = the NaN-or-zero is added to all K search-axis parameters of a spline (UniRqs::poison)
 #endif
@@ -170,5 +179,199 @@ typedef UniRqs<8, false> UniRqs8;
 typedef UniRqs<4, false> UniRqs4;
 typedef UniRqs<16, false> UniRqs16;
 typedef UniRqs<8, true> UniCircRqs8;
+
+
+// ---- the frame ------------------------------------------------------------------------------------
+// LDS of a forward kernel:  ring | bias image | feature map | skip words | wave-private row tiles (16 samples x xs words per wavefront, XLDS only).
+// ONE definition for the kernels (the carved pointers) and their launchers (the size; the limits on feature groups and skip words).
+struct ArLds {
+  static constexpr int FMAP_WORDS = 1024, SKIP_WORDS = 256;  // (1024 + 256 words between the bias image and the row tiles)
+  static constexpr int bytes(int ring_floats, int bias_floats, int row_waves, int xs) {  // row_waves: wavefronts that stage rows (0: none)
+    return (ring_floats + bias_floats + FMAP_WORDS + SKIP_WORDS + row_waves * 16 * xs) * (int)sizeof(float);
+  }
+  // the carved pointers, each from the one before it (the bias image starts right behind the ring)
+  static __device__ __forceinline__ int* fmap(float* bias, int bias_floats) { return reinterpret_cast<int*>(bias + bias_floats); }
+  static __device__ __forceinline__ int* skip(int* fmap_) { return fmap_ + FMAP_WORDS; }
+  static __device__ __forceinline__ float* row(int* fmap_, int wave, int j, int xs) {  // this lane's sample row of its wavefront's tile
+    return reinterpret_cast<float*>(fmap_ + FMAP_WORDS + SKIP_WORDS) + wave * 16 * xs + j * xs;
+  }
+  // cooperative copy of the launch's tables (n_skip words of a.skip from skip0 on: the generic kernels), then the workgroup barrier
+  template <int THREADS> static __device__ __forceinline__ void stage(const ArArgs& a, int tid, float* bias, int* fmap_, int n_fmap, int skip0 = 0, int n_skip = 0) {
+    for (int i = tid; i < a.bias_floats; i += THREADS) bias[i] = a.bias[i];
+    for (int i = tid; i < n_fmap; i += THREADS) fmap_[i] = a.featmap[i];
+    for (int i = tid; i < n_skip; i += THREADS) skip(fmap_)[i] = (int)a.skip[skip0 + i];
+    __syncthreads();
+  }
+};
+
+// a wavefront owns 16 samples: lane (j, q) holds units 4 q .. 4 q + 3 of every 16-unit tile of sample j
+struct ArLane {
+  int tid, lane, wave, j, q;
+  __device__ __forceinline__ ArLane() : tid(threadIdx.x), lane(tid & 63), wave(__builtin_amdgcn_readfirstlane(tid >> 6)), j(lane & 15), q(lane >> 4) {}
+};
+
+// A NaN / inf input turns ALL parameters of its sample into NaN in the reference (it multiplies every input by mask * W: x * 0 = NaN, zuko/nn.py:217-218),
+// including those whose mask excludes that input.  Skipped tiles would not reproduce that, so the sample is flagged: NaN for such a sample, else 0.
+template <int NIT, int M> __device__ __forceinline__ float ar_poison_of(const f32x4 (&v)[M]) {
+  int bad = 0;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bad |= !(fabsf(v[it][r]) < __builtin_inff());
+  bad |= __shfl_xor(bad, 16, 64);
+  bad |= __shfl_xor(bad, 32, 64);
+  return bad ? __builtin_nanf("") : 0.f;
+}
+
+// The wave-private [16 samples x D] row tile: the epilogue's input values on the way in, the results on the way out.  It keeps the per-group operand
+// fetch on the LDS (lgkmcnt) queue — a global load there would wait behind the ring DMAs in flight — and turns 4-byte scattered result stores into
+// 16-byte row stores.  (Static-shape kernels: D at compile time.  The two generic kernels bound the columns by the run-time a.D in place: as shared
+// helpers these loops moved their register allocation, profiles/ar_frame/census.md.)
+template <int D, int M> __device__ __forceinline__ void ar_rows_in(float* xr, int q, const f32x4 (&v)[M]) {
+#pragma unroll
+  for (int it = 0; it < (D + 15) / 16; ++it)
+    if ((it + 1) * 16 <= D || it * 16 + 4 * q < D) *reinterpret_cast<f32x4*>(xr + it * 16 + 4 * q) = v[it];
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+template <int D> __device__ __forceinline__ void ar_rows_out(const float* xr, int q, float* yrow, bool live) {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  if (live) {
+#pragma unroll
+    for (int it = 0; it < (D + 15) / 16; ++it)
+      if ((it + 1) * 16 <= D || it * 16 + 4 * q < D) *reinterpret_cast<f32x4*>(yrow + it * 16 + 4 * q) = *reinterpret_cast<const f32x4*>(xr + it * 16 + 4 * q);
+  }
+}
+// Activation between the layers of a static-shape kernel, dst = act(src) over N tiles (dst may be src; the generic kernels switch on the run-time id).  ELU / tanh / SiLU / GELU / sigmoid / leaky ReLU sit inside a loop the
+// compiler must not unroll over the activation's inline expansion (64-128 copies of tanhf / erff made the epilogue instruction-cache bound).
+template <int ACT, int N, int M> __device__ __forceinline__ void ar_activate(f32x4 (&dst)[M], const f32x4 (&src)[M]) {
+  if constexpr (ACT == 1) {
+#pragma unroll
+    for (int t = 0; t < N; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dst[t][r] = src[t][r] < 0.f ? 0.f : src[t][r];  // NaN stays NaN, as torch.relu
+  } else if constexpr (ACT == 0) {
+#pragma unroll
+    for (int t = 0; t < N; ++t) dst[t] = src[t];
+  } else {
+#pragma unroll 1
+    for (int rep = 0; rep < 1; ++rep) {
+#pragma unroll
+      for (int t = 0; t < N; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[t][r] = act_f32(src[t][r], ACT);
+    }
+  }
+}
+// Feature ids of this lane's slots in every group of the last layer.  REGS: constant over the launch, kept in registers when they fit (a per-group
+// LDS read puts one exposed LDS round trip in front of the read of x that depends on it).
+template <int NG, int FPL, bool REGS> struct ArFids {
+  int r[REGS ? NG * FPL : 1];
+  const int* fmap;
+  int q;
+  __device__ __forceinline__ ArFids(const int* fmap_lds, int q_) : fmap(fmap_lds), q(q_) {
+    if constexpr (REGS) {
+#pragma unroll
+      for (int i = 0; i < NG; ++i)
+#pragma unroll
+        for (int fi = 0; fi < FPL; ++fi) r[i * FPL + fi] = fmap[(i * 4 + q) * FPL + fi];
+    }
+  }
+  // operands of group g's epilogue, requested before the group's matrix instructions: feature ids, then x from the row tile (XLDS) or the global row
+  template <bool XLDS> __device__ __forceinline__ void fetch(int g, const float* xr, const float* xrow, int (&fid)[FPL], float (&xin)[FPL]) const {
+#pragma unroll
+    for (int fi = 0; fi < FPL; ++fi) {
+      if constexpr (REGS) fid[fi] = r[g * FPL + fi];
+      else fid[fi] = fmap[(g * 4 + q) * FPL + fi];
+      const int fc = fid[fi] < 0 ? 0 : fid[fi];
+      if constexpr (XLDS) xin[fi] = xr[fc];
+      else xin[fi] = xrow[fc];
+    }
+  }
+};
+
+// The univariate map on the group's parameters p (registers) in the static-shape kernels: y to the row tile (XLDS) or straight to global memory,
+// log|dy/dx| added to lacc.  ABL: the kernel honours the ARX_ABL == 3 ablation (the operand-split kernels; not the f32 one).  (The two generic kernels
+// keep their epilogue in place — inverse branch, partial-sweep stores, timing probe — for the same reason as their row loops.)
+// A sample with a non-finite input has NaN parameters throughout in the reference; making the parameters of the SEARCH axis NaN reproduces every
+// output of that case (Uni::poison) at a third of the additions.  DIAG: the diagnostic twin — the bin index the spline USED and the knots it
+// searched are stored as well (bin_out [N, D], knots_out [N, D, NKNOT]).
+template <typename Uni, bool DIAG, bool XLDS, bool ABL = true>
+__device__ __forceinline__ void ar_uni_epilogue(float (&p)[4 * Uni::NT], const ArArgs& a, const int (&fid)[Uni::FPL], const float (&xin)[Uni::FPL], float poison, float* xr, int64_t n,
+                                                bool live, int D, float& lacc) {
+  constexpr int FPL = Uni::FPL, TOTAL = Uni::TOTAL;
+#pragma unroll
+  for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
+  auto ld = [&](int i) { return p[i]; };
+#pragma unroll
+  for (int fi = 0; fi < FPL; ++fi) {
+    const int f = fid[fi];
+    if (f >= 0) {
+      float yv, lj;
+      if (ABL && ARX_ABL == 3) {
+        yv = p[fi * TOTAL] + xin[fi]; lj = p[fi * TOTAL + 1];
+#pragma unroll
+        for (int i = 2; i < TOTAL; ++i) lj += p[fi * TOTAL + i];
+      } else if constexpr (DIAG) {
+        int kb = 0;
+        float ks[Uni::NKNOT];
+        Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj, &kb, ks);
+        if (live) {
+          a.bin_out[n * D + f] = kb;
+#pragma unroll
+          for (int jj = 0; jj < Uni::NKNOT; ++jj) a.knots_out[(n * D + f) * Uni::NKNOT + jj] = ks[jj];
+        }
+      } else Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj);
+      if constexpr (XLDS) xr[f] = yv;
+      else if (live) a.y[n * a.ldy + f] = yv;
+      lacc += lj;
+    }
+  }
+}
+
+// the sample's log|dy/dx|: summed over q with two shuffles, stored (or added to what the buffer holds — ladj_in when the caller requested it ahead)
+template <bool PREFETCHED = false> __device__ __forceinline__ void ar_ladj_store(const ArArgs& a, float lacc, int64_t n, bool live, int q, float ladj_in = 0.f) {
+  if (a.ladj) {
+    lacc += __shfl_xor(lacc, 16, 64);
+    lacc += __shfl_xor(lacc, 32, 64);
+    if (live && q == 0) a.ladj[n] = a.accumulate ? (PREFETCHED ? ladj_in : a.ladj[n]) + lacc : lacc;
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------
+// Grant, launch, check.  The opt-in to > 64 KiB of dynamic LDS is per function: set once, and again only if a larger size is asked for.  (static:
+// every translation unit — the library's two, each generated kernel's shared object — keeps its own map.)
+static inline int ar_launch_dyn_lds(const void* fn, int max_grid, int block, int lds_bytes, ArArgs& a, void* stream) {
+  hipError_t e = hipSuccess;
+  {
+    static std::mutex mu;
+    static std::unordered_map<const void*, int> granted;
+    std::lock_guard<std::mutex> lock(mu);
+    int& g = granted[fn];
+    if (g < lds_bytes) {
+      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+      if (e != hipSuccess) return (int)e;
+      g = lds_bytes;
+    }
+  }
+  const unsigned grid = (unsigned)(a.n_tiles < max_grid ? a.n_tiles : max_grid);
+  void* kargs[] = {&a};
+  e = hipLaunchKernel(fn, dim3(grid), dim3((unsigned)block), kargs, lds_bytes, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  return ZK_LAUNCH_CHECK();
+}
+
+// Versioned argument block (include/zuko_amd.h: zk_ar_args_v1 — every entry point checks struct_size / version before it reads a field).  A caller
+// compiled against the first layout of version 1 (which ended with gh3) passes a SHORTER block: it is accepted and the fields it does not have
+// (phi_packed, gl_nodes01, gl_weights01, eps) read as zero — the point of carrying struct_size.  A block longer than this library knows, another
+// version, or one cut inside the original fields is refused.
+template <class Args> static inline bool ar_args_norm(const Args* p, Args* out) {
+  if (!p || p->version != 1 || p->struct_size < offsetof(Args, phi_packed) || p->struct_size > sizeof(Args)) return false;
+  std::memset(out, 0, sizeof(*out));
+  std::memcpy(out, p, p->struct_size);
+  out->struct_size = sizeof(Args);
+  return true;
+}
 
 }  // namespace zk
