@@ -174,7 +174,7 @@ int zk_linear_bf16_rqs_lanes(int64_t N, int in_features, int panels, const void*
  * ints is a silent wrong answer; a mis-named field is a compile error / a Python KeyError): set struct_size = sizeof(the struct)
  * and version = 1, fill the fields the entry point reads (listed per function), leave the rest zero.  The library rejects a
  * version it does not know, and a struct_size larger than its own, with hipErrorInvalidValue.  zk_ar_args_v1 GREW within version 1
- * (phi_packed .. eps were appended after gh3): a block of the earlier size — struct_size == offsetof(zk_ar_args_v1, phi_packed) or anything
+ * (phi_packed .. base_scale were appended after gh3): a block of the earlier size — struct_size == offsetof(zk_ar_args_v1, phi_packed) or anything
  * between that and sizeof — is accepted and the fields it lacks read as zero, so callers built against the earlier header keep working.
  * Behaviour change that came with the growth: zk_ar_forward_train used to ignore y / ladj / bound / slope / accumulate and now honours
  * them when y != NULL (y == NULL keeps the conditioner-only launch).  zuko_amd/_C.py builds its ctypes.Structure classes by
@@ -237,6 +237,9 @@ typedef struct zk_ar_args_v1 {
   uint32_t* amax1;         /* caller — forward: the maximum of h1 / h2 / h3 is folded into amax0 / 1 / 2 and of x into amax3; backward: of gh_l into amax_{l-1}... in the order the kernel */
   uint32_t* amax2;         /* writes them (amax_c for chain layer c: the gradient of hidden layer n - 1 - c) and of the packed parameter gradient x_out into amax3.  They let */
   uint32_t* amax3;         /* zk_wgrad_multi form its products from two-part f16 operands (zk_wgrad_layer_v1.g_amax / h_amax) */
+  const void* base_loc;    /* zk_ar_forward_static on an operand-split kernel, the LAST transform of a log_prob (both set, or both NULL = not terminal; a block that */
+  const void* base_scale;  /* ends before them reads as not terminal): DEVICE fp32 [D] loc / scale of a diagonal-normal base.  y is then NOT written (may be NULL) and */
+                           /* ladj [N] (required) receives (accumulate ? ladj : 0) + log|dy/dx| + sum_f log N(y_f; loc_f, scale_f): the flow's log-density */
 } zk_ar_args_v1;
 
 /* y, ladj of one layer on the generic tile-skipping kernel.  Reads: uni_kind, N, D, DIN, x, ldx, y, ldy, ladj, accumulate, wstream,
@@ -415,7 +418,9 @@ int zk_ar_lds_bytes(int variant, int bias_floats);
 /* Reads: launcher, rev, uni_kind, N, D, DIN, x, ldx, y, ldy, ladj, accumulate, wstream, bias, bias_floats, featmap, n_layers, n_groups,
  * n_chunks, bound, slope; bin_out + knots_out (both or neither): the DIAGNOSTIC twin of an operand-split kernel — same arithmetic as the
  * product launch plus the bin index used and the knots searched, as zk_ar_forward_diag (the f32-instruction static kernels return
- * hipErrorInvalidValue for it: they are bit-identical to zk_ar_forward, whose twin serves). */
+ * hipErrorInvalidValue for it: they are bit-identical to zk_ar_forward, whose twin serves); base_loc + base_scale (both or neither): the
+ * TERMINAL launch of an operand-split kernel for the last transform of a log_prob, see the fields (not with bin_out; the f32-instruction
+ * static kernels return hipErrorInvalidValue for it). */
 int zk_ar_forward_static(const zk_ar_args_v1* args, void* stream);
 /* Conditioner-only launch of a generated static-shape kernel for the training forward (zuko_amd/train.py): phi [N, D * total] =
  * net(x) in module order (what the last MaskedLinear of zuko/nn.py:221-318 returns) and the hidden activations h_l [N, width_l]

@@ -464,6 +464,8 @@ struct ArPartial {  // optional: evaluate only last-layer groups [g0, g1) and th
   float* knots_out = nullptr;
   double wdescale[4] = {0.0, 0.0, 0.0, 0.0};  // two-part split kernels: 1 / (the power of two every layer's weights were stored with)
   unsigned* amax[4] = {nullptr, nullptr, nullptr, nullptr};  // training launches: maxima of the stored tensors (ArArgs::amax)
+  const float* base_loc = nullptr;    // terminal launch of a log_prob (operand-split static-shape kernels): the diagonal-normal base (ArArgs::base_loc)
+  const float* base_scale = nullptr;
   const int* sched = nullptr;
   int n_sched = 0;
   const int* olim = nullptr;  // host array, one entry per hidden layer
@@ -515,6 +517,8 @@ static int ar_launch(const ArPartial& part, bool inverse, int uni_kind, int64_t 
     a.eps = (float)(part.eps > 0.0 ? part.eps : 1e-6);
     for (int l = 0; l < 4; ++l) a.wdescale[l] = (float)part.wdescale[l];
     for (int l = 0; l < 4; ++l) a.amax[l] = part.amax[l];
+    if ((part.base_loc != nullptr) != (part.base_scale != nullptr) || (part.base_loc && (!ladj || part.phi_out || part.bin_out))) return ZK_EINVAL;
+    a.base_loc = part.base_loc; a.base_scale = part.base_scale;
     return ((ars_launch_fn)part.static_fn)(&a, ARS_ABI, (int)sizeof(ArArgs), part.phi_out != nullptr, stream);
   }
   // stage x / results through LDS when rows are float4-addressable and the tiles fit beside the ring
@@ -587,6 +591,7 @@ int zk_ar_forward_static(const zk_ar_args_v1* args, void* stream) {
   part.gl_nodes01 = args->gl_nodes01; part.gl_weights01 = args->gl_weights01; part.eps = args->eps;
   part.bin_out = args->bin_out; part.knots_out = args->knots_out;  // both set: the kernel's diagnostic twin (operand-split kernels only)
   part.wdescale[0] = args->wdescale0; part.wdescale[1] = args->wdescale1; part.wdescale[2] = args->wdescale2; part.wdescale[3] = args->wdescale3;
+  part.base_loc = (const float*)args->base_loc; part.base_scale = (const float*)args->base_scale;  // both set: the kernel's terminal instantiation
   zk_ar_args_v1 p = *args;
   p.skip = nullptr;  // (act: checked by the kernel against the activation it was generated for)
   return ar_launch_v1(part, false, p, stream);

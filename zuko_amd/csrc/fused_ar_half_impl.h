@@ -248,8 +248,10 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
   }
 }
 
-// DIAG: the diagnostic twin of the product launch (also writes the bin index the spline USED and the knots it searched), as arx_kernel's.
-template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arh_kernel(ArArgs a) {
+// The kernel's body.  DIAG: the diagnostic twin of the product launch (also writes the bin index the spline USED and the knots it searched), as
+// arx_kernel's.  TERM: the terminal launch of a log_prob (arht_kernel): the base's tables staged behind the feature map, no y rows written, the
+// log-density in the ladj buffer (zk_ar_common.h: ArArgs::base_loc).
+template <class S, typename Uni, bool DIAG, bool TERM> __device__ __forceinline__ void arh_body(const ArArgs& a) {
   typedef ArhRing<S::WAVES, S::CH, S::NR> Ring;
   static_assert(S::WAVES == 8 && S::NR == 3 && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::OCC == 2, "two-part split kernels: widths <= 256, two wavefronts per SIMD");
   constexpr int NT = Uni::NT, FPL = Uni::FPL, TOTAL = Uni::TOTAL, WAVES = S::WAVES;
@@ -287,6 +289,8 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
   float* const bias_lds = ars_lds + S::NR * S::CH * AR_TF;
   int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
   float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  float* const base = ArLds::base(fmap_lds, NG * 4 * FPL);
+  if constexpr (TERM) ArLds::stage_base<64 * WAVES>(a, tid, base, S::D);
   ArLds::stage<64 * WAVES>(a, tid, bias_lds, fmap_lds, NG * 4 * FPL);
   const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
   const unsigned bias_last_addr = arx_lds_addr(bias_last + 4 * q);
@@ -361,6 +365,8 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
       int fid[FPL];
       float xin[FPL];
       fids.template fetch<XLDS>(g, xr, xrow, fid, xin);
+      float bv[3 * FPL];
+      if constexpr (TERM) fids.fetch_base(fid, base, S::D, bv);
       f32x4 acc[NT], bs[NT];  // the group's bias tiles: raw reads in front of the look-ahead request of the group's LAST block, whose counted wait settles them
       if constexpr (GN == 0) {
         const float* bg = bias_last + (g * NT) * 16 + 4 * q;
@@ -401,15 +407,19 @@ template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__
           if (ARH_POISON_ONE) asm("" : "+v"(p[4 * t + r]));
         }
       });
-      ar_uni_epilogue<Uni, DIAG, XLDS>(p, a, fid, xin, poison, xr, n, live, S::D, lacc);
+      ar_uni_epilogue<Uni, DIAG, XLDS, true, TERM>(p, a, fid, xin, poison, xr, n, live, S::D, lacc, bv);
     });
 #undef ARH_READ_LAST
     if (ARH_PREFETCH) ar_ladj_store<true>(a, lacc, n, live, q, ladj_in);  // in FRONT of the y rows: the wait for ladj_in (requested a tile ago) must not find stores it would have to sit out
-    if constexpr (XLDS) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
+    if constexpr (XLDS && !TERM) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
     if (!ARH_PREFETCH) ar_ladj_store(a, lacc, n, live, q);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
+
+template <class S, typename Uni, bool DIAG = false> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arh_kernel(ArArgs a) { arh_body<S, Uni, DIAG, false>(a); }
+// (a name of its own: tests/test_codegen_half.py counts and bounds the arh_kernel instantiations of a generated unit)
+template <class S, typename Uni> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arht_kernel(ArArgs a) { arh_body<S, Uni, false, true>(a); }
 
 template <class S, typename Uni> static int arh_launch(const ArArgs* in, int abi, int args_bytes, int train, void* stream) {
   if (abi != ARS_ABI || args_bytes != (int)sizeof(ArArgs)) return ZK_EINVAL;  // kernel built against another version of the library
@@ -419,14 +429,18 @@ template <class S, typename Uni> static int arh_launch(const ArArgs* in, int abi
     if (!(a.wdescale[l] > 0.f) || !(a.wdescale[l] < __builtin_inff())) return ZK_EINVAL;  // the stream's per-layer scales must come with it
   a.n_tiles = (a.N + 16 * S::WAVES - 1) / (16 * S::WAVES);
   a.xs = ((S::D + 3) / 4) * 4 + 4;
-  const bool vec_ok = (S::D % 4 == 0) && (a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0);
+  const bool term = a.base_loc != nullptr;  // terminal launch of a log_prob: y is not written
+  if (term && (!a.base_scale || !a.ladj || a.bin_out || a.knots_out || !ArLds::base_fits(S::NG * 4 * Uni::FPL, S::D))) return ZK_EINVAL;
+  const bool vec_ok = (S::D % 4 == 0) && (term || ((a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0)));
   if (S::XLDS != 0 && !vec_ok) return ZK_EINVAL;
   a.xlds = S::XLDS;
   const int lds = ArLds::bytes(S::NR * S::CH * AR_TF, a.bias_floats, S::XLDS ? S::WAVES : 0, a.xs);
   if (lds > 160 * 1024) return ZK_EINVAL;
   const void* fn = nullptr;
   if ((a.bin_out != nullptr) != (a.knots_out != nullptr)) return ZK_EINVAL;
-  if (a.bin_out) {
+  if (term) {
+    fn = (const void*)arht_kernel<S, Uni>;
+  } else if (a.bin_out) {
     if constexpr (Uni::NKNOT > 1) fn = (const void*)arh_kernel<S, Uni, true>;  // (the diagnostic twin exists for the spline maps only)
   } else {
     fn = (const void*)arh_kernel<S, Uni, false>;

@@ -186,7 +186,9 @@ template <class S, int L, class Ring, bool TRAIN> __device__ __forceinline__ voi
 // zk_ar_forward_diag does for the generic kernel — the parity bar on the bin index is asserted on the product path (tests/test_gpu_bins.py).
 // Shape::OCC = wavefronts per SIMD the registers are budgeted for: 2 (widths <= 256: 16 activation tiles + 8 operand pairs per wavefront), 1 for
 // conditioners 257 - 512 wide (32 tiles + 16 pairs = 320 registers; four wavefronts per workgroup, one workgroup per CU).
-template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arx_kernel(ArArgs a) {
+// TERM: the terminal launch of a log_prob (arxt_kernel): the base's tables staged behind the feature map, no y rows written, the log-density in
+// the ladj buffer (zk_ar_common.h: ArArgs::base_loc).
+template <class S, typename Uni, bool TRAIN, bool DIAG, bool TERM> __device__ __forceinline__ void arx_body(const ArArgs& a) {
   typedef ArRingS<S::WAVES, S::CH, S::NR> Ring;
   static_assert((S::WAVES == 8 || S::WAVES == 4) && (S::NR == 2 || S::NR == 3) && (S::TMAX <= 16 || (S::TMAX <= 32 && S::OCC == 1 && S::WAVES == 4)) && S::TMAX % 2 == 0,
                 "operand-split kernels: widths <= 256 with two wavefronts per SIMD, <= 512 with one");
@@ -202,6 +204,8 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
   float* const bias_lds = ars_lds + S::NR * S::CH * AR_TF;
   int* const fmap_lds = ArLds::fmap(bias_lds, a.bias_floats);
   float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  float* const base = ArLds::base(fmap_lds, NG * 4 * FPL);
+  if constexpr (TERM) ArLds::stage_base<64 * WAVES>(a, tid, base, S::D);
   ArLds::stage<64 * WAVES>(a, tid, bias_lds, fmap_lds, NG * 4 * FPL);
   const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
   const unsigned bias_last_addr = arx_lds_addr(bias_last + 4 * q);
@@ -265,6 +269,8 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
       int fid[FPL];
       float xin[FPL];
       fids.template fetch<XLDS>(g, xr, xrow, fid, xin);
+      float bv[3 * FPL];
+      if constexpr (TERM) fids.fetch_base(fid, base, S::D, bv);
       f32x4 acc[NT];  // the accumulators start at the bias (raw reads, older than every image requested below: the first block's wait settles them all)
       if constexpr (GN > 0) {
         ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = arx_lds_raw<(g * NT + decltype(t)::value) * 64>(bias_last_addr); });
@@ -316,14 +322,17 @@ template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __lau
           }
         }
       }
-      if (uni_on) ar_uni_epilogue<Uni, DIAG, XLDS>(p, a, fid, xin, poison, xr, n, live, S::D, lacc);
+      if (uni_on) ar_uni_epilogue<Uni, DIAG, XLDS, true, TERM>(p, a, fid, xin, poison, xr, n, live, S::D, lacc, bv);
     });
-    if constexpr (XLDS) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live && uni_on);
+    if constexpr (XLDS && !TERM) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live && uni_on);
     if (uni_on) ar_ladj_store(a, lacc, n, live, q);
   }
   if constexpr (TRAIN) arx_amax_flush(a, mx, blockIdx.x * WAVES + wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
+
+template <class S, typename Uni, bool TRAIN, bool DIAG = false> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arx_kernel(ArArgs a) { arx_body<S, Uni, TRAIN, DIAG, false>(a); }
+template <class S, typename Uni> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arxt_kernel(ArArgs a) { arx_body<S, Uni, false, false, true>(a); }
 
 // ---- the backward twin: dgrad through EVERY linear layer of the conditioner in one launch -------------------------------------------
 // g_{l-1} = (g_l (W_l * mask_l)) * relu'(h_{l-1}) from the gradient of the packed parameters phi down to the conditioner's input (what
@@ -631,7 +640,9 @@ template <class S, typename Uni> static int arx_launch(const ArArgs* in, int abi
   if (train && (!S::TRAIN_OK || !a.phi_out || (a.phi_packed && (a.ldphi % 4 || a.ldphi < (int64_t)S::NG * Uni::NT * 16 || ((uintptr_t)a.phi_out % 16))))) return ZK_EINVAL;
   a.n_tiles = (a.N + 16 * S::WAVES - 1) / (16 * S::WAVES);
   a.xs = ((S::D + 3) / 4) * 4 + 4;
-  const bool vec_ok = (S::D % 4 == 0) && ((train && !a.y) || ((a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0)));
+  const bool term = a.base_loc != nullptr;  // terminal launch of a log_prob: y is not written
+  if (term && (train || !a.base_scale || !a.ladj || a.bin_out || a.knots_out || !ArLds::base_fits(S::NG * 4 * Uni::FPL, S::D))) return ZK_EINVAL;
+  const bool vec_ok = (S::D % 4 == 0) && ((train && !a.y) || term || ((a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0)));
   if (S::XLDS != 0 && !vec_ok) return ZK_EINVAL;
   a.xlds = S::XLDS;
   const int lds = ArLds::bytes(S::NR * S::CH * AR_TF, a.bias_floats, S::XLDS ? S::WAVES : 0, a.xs);
@@ -640,6 +651,8 @@ template <class S, typename Uni> static int arx_launch(const ArArgs* in, int abi
   if ((a.bin_out != nullptr) != (a.knots_out != nullptr) || (a.bin_out && train)) return ZK_EINVAL;
   if (train) {
     if constexpr (S::TRAIN_OK) fn = (const void*)arx_kernel<S, Uni, true>;
+  } else if (term) {
+    fn = (const void*)arxt_kernel<S, Uni>;
   } else if (a.bin_out) {
     if constexpr (Uni::NKNOT > 1) fn = (const void*)arx_kernel<S, Uni, false, true>;  // (the diagnostic twin exists for the spline maps only)
   } else {

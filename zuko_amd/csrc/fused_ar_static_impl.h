@@ -422,6 +422,7 @@ template <class S, typename Uni> static int ars_launch(const ArArgs* in, int abi
   if (a.D != S::D || a.DIN != S::DIN || a.L != S::NH + 1 || a.act != S::ACT || a.sched || a.NG != S::NG || a.n_chunks != S::NCHUNK) return ZK_EINVAL;
   if (a.l1rev && !S::HAS_ALT) return ZK_EINVAL;
   if (a.bin_out || a.knots_out) return ZK_EINVAL;  // (no diagnostic instantiation: these kernels are bit-identical to the generic one, whose twin serves)
+  if (a.base_loc) return ZK_EINVAL;                // (no terminal instantiation: the base's log-density stays a launch of its own behind these kernels)
   if (train && (!S::TRAIN_OK || !a.phi_out)) return ZK_EINVAL;
   a.n_tiles = (a.N + 16 * S::WAVES - 1) / (16 * S::WAVES);
   a.xs = ((S::D + 3) / 4) * 4 + 4;

@@ -16,7 +16,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define AR_TF 256 /* floats per tile image */
 #define AR_WAVES 8
 #define AR_T 16   /* activation tiles (256 units) */
-#define ARS_ABI 9 /* contract between this library and the generated static-shape kernels (zuko_amd/static_ar.py): bump on any change of ArArgs */
+#define ARS_ABI 10 /* contract between this library and the generated static-shape kernels (zuko_amd/static_ar.py): bump on any change of ArArgs */
 #ifndef ARX_ABL
 #define ARX_ABL 0  // timing ablations of the operand-split kernel (scripts/split_ablate.py): 1 no DMA, 2 no MFMA, 3 no epilogue, 4 no barrier, 5 no LDS reads, 6 no conversions
 #endif
@@ -76,6 +76,10 @@ struct ArArgs {
   // gradients (zk_half.h: 64 slots) — forward: amax[l] for act_out[l]; backward: amax[l] for act_out[l] (gradient of a hidden layer), amax[3] for
   // gphi_out.  null = not wanted.  With them the weight gradients run on two-part f16 operands (csrc/train.hip: wgrad_split_body<true>).
   unsigned* amax[4];
+  // terminal launch of a log_prob (operand-split static-shape kernels: arht_kernel, arxt_kernel): loc [D] and scale [D] of the diagonal-normal base.
+  // base_loc != null: y is NOT written, and ladj receives (ladj +) log|dy/dx| + sum_f log N(y_f; loc_f, scale_f) — the log-density itself
+  const float* base_loc;
+  const float* base_scale;
 };
 
 __device__ __forceinline__ float act_f32(float v, int act) {
@@ -202,6 +206,19 @@ struct ArLds {
     for (int i = tid; i < n_skip; i += THREADS) skip(fmap_)[i] = (int)a.skip[skip0 + i];
     __syncthreads();
   }
+  // Terminal launch: three D-float tables behind the feature map's n_fmap words, indexed by FEATURE id — loc_f, 1 / (2 s_f^2) and
+  // -log s_f - log sqrt(2 pi) — from the base's device buffers (they may change between calls: nothing is kept on the host).  Call in front of
+  // stage(), whose barrier publishes them.  n_fmap + 3 D <= FMAP_WORDS is the launcher's to check (base_fits).
+  static constexpr bool base_fits(int n_fmap, int D) { return n_fmap + 3 * D <= FMAP_WORDS; }
+  static __device__ __forceinline__ float* base(int* fmap_, int n_fmap) { return reinterpret_cast<float*>(fmap_ + n_fmap); }
+  template <int THREADS> static __device__ __forceinline__ void stage_base(const ArArgs& a, int tid, float* tab, int D) {
+    for (int i = tid; i < D; i += THREADS) {
+      const float s = a.base_scale[i];
+      tab[i] = a.base_loc[i];
+      tab[D + i] = 1.f / (2.f * (s * s));
+      tab[2 * D + i] = -t_log(s) - 0.91893853320467274178f;
+    }
+  }
 };
 
 // a wavefront owns 16 samples: lane (j, q) holds units 4 q .. 4 q + 3 of every 16-unit tile of sample j
@@ -289,6 +306,15 @@ template <int NG, int FPL, bool REGS> struct ArFids {
       else xin[fi] = xrow[fc];
     }
   }
+  // terminal launch: the base's table entries (ArLds::stage_base, D floats each) of the group's features, requested with the operands above
+  __device__ __forceinline__ void fetch_base(const int (&fid)[FPL], const float* base, int D, float (&bv)[3 * FPL]) const {
+#pragma unroll
+    for (int fi = 0; fi < FPL; ++fi) {
+      const int fc = fid[fi] < 0 ? 0 : fid[fi];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) bv[3 * fi + k] = base[k * D + fc];
+    }
+  }
 };
 
 // The univariate map on the group's parameters p (registers) in the static-shape kernels: y to the row tile (XLDS) or straight to global memory,
@@ -296,10 +322,11 @@ template <int NG, int FPL, bool REGS> struct ArFids {
 // keep their epilogue in place — inverse branch, partial-sweep stores, timing probe — for the same reason as their row loops.)
 // A sample with a non-finite input has NaN parameters throughout in the reference; making the parameters of the SEARCH axis NaN reproduces every
 // output of that case (Uni::poison) at a third of the additions.  DIAG: the diagnostic twin — the bin index the spline USED and the knots it
-// searched are stored as well (bin_out [N, D], knots_out [N, D, NKNOT]).
-template <typename Uni, bool DIAG, bool XLDS, bool ABL = true>
+// searched are stored as well (bin_out [N, D], knots_out [N, D, NKNOT]).  TERM: the terminal launch of a log_prob — y is not stored; the base's
+// log-density of y_f (bv: loc_f, 1 / (2 s_f^2), -log s_f - log sqrt(2 pi) per slot, ArFids::fetch_base) joins log|dy/dx| in lacc.  A poisoned sample has lj = NaN for every feature, so its sum is NaN.
+template <typename Uni, bool DIAG, bool XLDS, bool ABL = true, bool TERM = false>
 __device__ __forceinline__ void ar_uni_epilogue(float (&p)[4 * Uni::NT], const ArArgs& a, const int (&fid)[Uni::FPL], const float (&xin)[Uni::FPL], float poison, float* xr, int64_t n,
-                                                bool live, int D, float& lacc) {
+                                                bool live, int D, float& lacc, const float* bv = nullptr) {
   constexpr int FPL = Uni::FPL, TOTAL = Uni::TOTAL;
 #pragma unroll
   for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
@@ -323,9 +350,15 @@ __device__ __forceinline__ void ar_uni_epilogue(float (&p)[4 * Uni::NT], const A
           for (int jj = 0; jj < Uni::NKNOT; ++jj) a.knots_out[(n * D + f) * Uni::NKNOT + jj] = ks[jj];
         }
       } else Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj);
-      if constexpr (XLDS) xr[f] = yv;
-      else if (live) a.y[n * a.ldy + f] = yv;
-      lacc += lj;
+      if constexpr (TERM) {
+        const float df = yv - bv[3 * fi];
+        lacc += lj;
+        lacc += __builtin_fmaf(-(df * df), bv[3 * fi + 1], bv[3 * fi + 2]);
+      } else {
+        if constexpr (XLDS) xr[f] = yv;
+        else if (live) a.y[n * a.ldy + f] = yv;
+        lacc += lj;
+      }
     }
   }
 }

@@ -2,10 +2,14 @@ r"""`NormalizingFlow` and `DiagNormal`: the caller of the transform hot path.
 
 Mirrors zuko/distributions.py:39-138 and :337-363.  `log_prob` feeds z and the accumulated
 log|det J| to one HIP kernel that evaluates the diagonal-normal log-density, reduces over features
-and adds the ladj (zk_diag_normal_log_prob) when the base is a `DiagNormal`.
+and adds the ladj (zk_diag_normal_log_prob) when the base is a `DiagNormal` — or, when the last transform runs on an
+operand-split static-shape autoregressive kernel, hands (loc, scale) to that transform's own launch, which then returns
+the log-density and writes no z (ZUKO_AMD_NO_FUSED_BASE=1 keeps the separate launch).
 """
 
 from __future__ import annotations
+
+import os
 
 import torch
 from torch import Size, Tensor
@@ -13,6 +17,7 @@ from torch.distributions import Distribution, Independent, Normal, Transform, Un
 from torch.distributions.utils import _sum_rightmost
 
 from . import ops
+from .transforms import ComposedTransform
 
 __all__ = ["BoxUniform", "DiagNormal", "NormalizingFlow"]
 
@@ -101,11 +106,18 @@ class NormalizingFlow(Distribution):
         return None
 
     def log_prob(self, x: Tensor) -> Tensor:
-        z, ladj = self.transform.call_and_ladj(x)
-        ladj = _sum_rightmost(ladj, self.reinterpreted)
         fused = self._fusable_base()
         if fused is not None and torch.is_grad_enabled() and (fused[0].requires_grad or fused[1].requires_grad):
             fused = None  # trainable base: its gradient flows through torch's Normal.log_prob, as in the reference
+        if (fused is not None and isinstance(self.transform, ComposedTransform) and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and os.environ.get("ZUKO_AMD_NO_FUSED_BASE", "0") != "1"):
+            # a last transform on an operand-split static-shape kernel adds the base's log-density in its own launch: T launches, no z
+            z, ladj = self.transform.call_and_ladj(x, base=fused)
+            if z is None:
+                return ladj
+        else:
+            z, ladj = self.transform.call_and_ladj(x)
+        ladj = _sum_rightmost(ladj, self.reinterpreted)
         if fused is not None and z.is_cuda and torch.is_tensor(ladj) and ladj.shape == z.shape[:-1]:
             return ops.diag_normal_log_prob(z, fused[0], fused[1], ladj)
         return self.base.log_prob(z) + ladj

@@ -463,7 +463,25 @@ class FusedAutoregressiveTransform(AutoregressiveTransform):
             return None
         return self._run_fused(st, x, total)[0]
 
-    def _run_fused(self, st, x: Tensor, total):
+    def call_and_log_prob(self, x: Tensor, total: Tensor | None, loc: Tensor, scale: Tensor):
+        """As the LAST transform of a flow's log_prob over a diagonal-normal base (loc [D], scale [D]): log N(y; loc, scale) + log|dy/dx| (+ `total`, the
+        running log-determinant, whose buffer then holds the result) from the one launch that evaluates the transform — y never leaves the kernel.
+        Returns None when this call does not run on an operand-split static-shape kernel or `total` cannot be accumulated into in place: the caller
+        then evaluates the transform and the base separately."""
+        if torch.is_grad_enabled() and (x.requires_grad or (total is not None and total.requires_grad)):
+            return None
+        st = self._fused(x)
+        if st is None:
+            return None
+        D = self.lazy.features
+        batch = x.shape[:-1] if self.c is None else torch.broadcast_shapes(x.shape[:-1], self.c.shape[:-1])
+        if total is not None and (total.dtype != x.dtype or total.device != x.device or tuple(total.shape) != tuple(batch) or not total.is_contiguous()):
+            return None
+        if any(v.dtype != torch.float32 or v.device != x.device or tuple(v.shape) != (D,) for v in (loc, scale)):
+            return None
+        return self._run_fused(st, x, total, base=(loc.contiguous(), scale.contiguous()))
+
+    def _run_fused(self, st, x: Tensor, total, base=None):
         self._check_widths(x, st)
         lazy, c = self.lazy, self.c
         D = lazy.features
@@ -482,9 +500,14 @@ class FusedAutoregressiveTransform(AutoregressiveTransform):
             inp[:, :D] = x2
             if cb is not None:
                 inp[:, D:din] = cb.reshape(-1, cb.shape[-1])
-        y = torch.empty((x2.shape[0], D), dtype=x.dtype, device=x.device)
-        ladj = torch.empty(x2.shape[0], dtype=x.dtype, device=x.device) if total is None else total.view(-1)
         st.refresh([m for m in lazy.hyper if isinstance(m, MaskedLinear)])
+        if base is not None and not st.serves_terminal():
+            return None
+        ladj = torch.empty(x2.shape[0], dtype=x.dtype, device=x.device) if total is None else total.view(-1)
+        if base is not None:  # terminal launch: the log-density, no y
+            st.run(inp, None, ladj, total is not None, base=base)
+            return ladj.reshape(batch)
+        y = torch.empty((x2.shape[0], D), dtype=x.dtype, device=x.device)
         st.run(inp, y, ladj, total is not None)
         return y.reshape(batch + (D,)), ladj.reshape(batch)
 

@@ -604,10 +604,24 @@ class FusedAR:
                        bias_floats=self.bias_floats, featmap=_ptr(self.featmap), n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=self.half_n_chunks, act=self.act,
                        bound=self.bound, slope=self.slope, wdescale0=d[0], wdescale1=d[1], wdescale2=d[2], wdescale3=d[3], **io)
 
-    def _half_serves(self, y: Tensor) -> bool:
-        """Whether this inference launch goes to the two-part kernel: one is held, the mode allows it, the current weights are eligible and gathered."""
+    def _half_serves(self, y: Tensor | None) -> bool:
+        """Whether this inference launch goes to the two-part kernel: one is held, the mode allows it, the current weights are eligible and gathered.
+        (y None: a terminal launch, which writes no rows.)"""
         return (self.half is not None and self.half_ok and self._half_stamp is not None and self._half_stamp == self._seen_stamp and matmul_precision() == "f16x2"
-                and self.gs_mode != "force" and (not self.half.meta["XLDS"] or (y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0)))
+                and self.gs_mode != "force" and (y is None or not self.half.meta["XLDS"] or (y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0)))
+
+    def serves_terminal(self) -> bool:
+        """Whether run(..., base=) can be served, after refresh(): the launch would go to an operand-split static-shape kernel (two-part or three-part) —
+        the kernels with a terminal instantiation — and the base's three tables fit behind the feature map (csrc/zk_ar_common.h: ArLds::base_fits)."""
+        p = self.plan
+        if p.n_groups * 4 * p.layout.fpl + 3 * p.features > 1024:
+            return False
+        if self._half_serves(None):
+            return True
+        gs = self._gsplit()
+        if gs is not None and self._gs_stamp is not None and self._gs_stamp == self._seen_stamp:
+            return False  # (run() would take the generic operand-split kernel)
+        return self.static is not None and bool(self.static[0].meta.get("split")) and p.layout.kind not in (5, 6)
 
     def ready(self, rows: int) -> bool:
         """Whether run() can be served: always for plans the generic kernel covers; for wider ones only with a static-shape kernel
@@ -682,13 +696,28 @@ class FusedAR:
         if want_gs:
             self._gs_stamp = stamp
 
-    def run(self, inp: Tensor, y: Tensor, ladj: Tensor | None, accumulate: bool) -> None:
-        """inp [N, DINP] (cat(x, c), zero-padded to a multiple of 4 columns), y [N, D], ladj [N]."""
+    def run(self, inp: Tensor, y: Tensor | None, ladj: Tensor | None, accumulate: bool, base=None) -> None:
+        """inp [N, DINP] (cat(x, c), zero-padded to a multiple of 4 columns), y [N, D], ladj [N].
+        base = (loc [D], scale [D]) of a diagonal-normal base, contiguous fp32 on the device: the TERMINAL launch of a log_prob — y is None (no rows
+        are written) and ladj receives the log-density (serves_terminal() must hold)."""
         from . import _C
         from .ops import _ptr, _stream
 
         p = self.plan
         N = inp.shape[0]
+        if base is not None:
+            if y is not None or ladj is None or not self.serves_terminal():
+                raise RuntimeError("zuko_amd: terminal launch requested of a conditioner without an operand-split static-shape kernel (FusedAR.serves_terminal() was not consulted)")
+            io = dict(N=N, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate), base_loc=_ptr(base[0]), base_scale=_ptr(base[1]))
+            if self._half_serves(None):
+                a = self._half_args(**io)
+            else:
+                kern, rev = self.static
+                a = _C.args("zk_ar_args_v1", launcher=kern.launcher, rev=rev, uni_kind=p.layout.kind, D=p.features, wstream=_ptr(self.fine_stream), bias=_ptr(self.bias),
+                            bias_floats=self.bias_floats, featmap=_ptr(self.featmap), n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=self.fine_n_chunks, act=self.act,
+                            bound=self.bound, slope=self.slope, **io)
+            _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
+            return
         if self._half_serves(y):
             a = self._half_args(N=N, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate))
             _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")

@@ -375,11 +375,19 @@ class ComposedTransform(Transform):
     def log_abs_det_jacobian(self, x, y):
         return self.call_and_ladj(x)[1]
 
-    def call_and_ladj(self, x):
+    def call_and_ladj(self, x, base=None):
+        """(y, log|det dy/dx|).  base = (loc, scale) of a diagonal-normal base over the last axis (NormalizingFlow.log_prob): when the LAST transform can
+        fold the base's log-density into its own launch (call_and_log_prob) the result is (None, log_prob) instead — y is never written."""
         dim = self.domain_dim
         total = None
         owned = False  # `total` is a tensor this loop may write: allocated by a fused transform for this call, or the result of `total + ladj`
+        last = self.transforms[-1]
         for t in self.transforms:
+            if base is not None and t is last and (owned or total is None) and dim == t.domain.event_dim == t.codomain.event_dim == 1:
+                term = getattr(t, "call_and_log_prob", None)
+                lp = term(x, total, *base) if term is not None else None
+                if lp is not None:
+                    return None, lp
             acc = getattr(t, "call_and_accumulate_ladj", None)
             y = acc(x, total) if (acc is not None and owned and dim == t.domain.event_dim) else None  # the kernel adds its log-determinant to `total`
             if y is not None:
