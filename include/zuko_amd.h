@@ -592,6 +592,62 @@ int zk_coupling_split(int64_t N, int D, int C, const void* x, int64_t ldx, const
 int zk_coupling_merge(int64_t N, int D, const void* base, int64_t ldbase, const void* b, int nb, const void* add, int64_t ldadd, const int32_t* half, void* out,
                       void* stream);
 
+/* ---- monotone neural network of the neural autoregressive flow (NAF; fp32) ------------------------------------------------------------
+ * Every feature f owns a small monotone network (1 + S) -> width0 [-> width1 [-> width2]] -> 1 with weights |W| and the two-way ELU
+ * (zuko/nn.py:321-392: units below ceil(width / 2) take ELU(p), the others -ELU(-p)); its input is cat(x, signal) with the S signal
+ * values the conditioner's last layer emitted for that element (zuko/flows/neural.py:56-60).
+ *
+ * zk_mnn_forward replaces MNN.f + MonotonicTransform.call_and_ladj (zuko/flows/neural.py:56-71, zuko/transforms.py:623-637): y = f(x) and
+ * ladj = log df/dx, the derivative carried in forward mode next to the value (the reference: torch.autograd.grad through stacked einsums).
+ * zk_mnn_inverse replaces MonotonicTransform._inverse + Bisection.forward (zuko/transforms.py:609-617, zuko/utils.py:170-178): a = -bound,
+ * b = bound, n_bisect times c = (a + b) / 2, f(c) < target ? a = c : b = c, result (a + b) / 2, all in fp32; the signal's share of the first
+ * layer is computed once per element.  Products run on v_mfma_f32_16x16x4_f32 (exact fp32); no atomics: the same inputs give the same bits,
+ * and an element's result depends on its own x, signal and feature only (not on N, Dsel or the other columns of the call).
+ *
+ *   x         [N, Dsel], row stride ldx (elements): the inputs (zk_mnn_inverse: the targets); column j belongs to feature feat[j]
+ *   signal    [N, Dsel, S] packed as the conditioner emits it, row stride ld_signal >= Dsel * S
+ *   y         [N, Dsel], row stride ldy: the outputs (zk_mnn_inverse: the solutions)
+ *   ladj      zk_mnn_forward: [N, Dsel] contiguous, or with ladj_reduced != 0 [N] = the columns of a row added left to right; `work`
+ *             ([N, Dsel] floats of scratch) must then be given
+ *   feat      DEVICE int32 [Dsel] or NULL (= the identity): the network of column j, in [0, n_features)
+ *   image     n_features weight images of image_floats floats each (zuko_amd/mnn_plan.py: |W_l| in matrix-instruction tile order with every
+ *             `in` dimension padded to the instruction's K step of 4, and b_l), gathered on the device by zk_gather_f32
+ *   limits    1 <= S <= 63; 1 to 3 hidden layers, every width a multiple of 16 and <= 128; one image must fit 128 KiB of LDS, i.e.
+ *             zk_mnn_image_floats(...) * 4 <= 131072 (all one- and two-layer shapes fit; of the three-layer ones at S = 16 e.g. (128, 128, 64) does and
+ *             (128, 128, 128) does not).  zk_mnn_image_floats returns the image's size in floats, or -1 for an unsupported shape.
+ * The block follows the ARGUMENT BLOCK conventions above: a foreign struct_size or version is rejected with hipErrorInvalidValue, as is an
+ * unsupported shape, before anything touches the device. */
+typedef struct zk_mnn_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_mnn_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t S;               /* signal features */
+  int32_t n_hidden;        /* hidden layers, 1..3 */
+  int32_t width0;          /* hidden widths; 0 behind n_hidden */
+  int32_t width1;
+  int32_t width2;
+  int32_t n_features;      /* images in `image` */
+  int32_t image_floats;    /* floats per image = zk_mnn_image_floats(S, n_hidden, width0, width1, width2) */
+  int32_t ladj_reduced;    /* zk_mnn_forward: != 0: ladj is [N] */
+  int32_t n_bisect;        /* zk_mnn_inverse: bisection steps (the reference: ceil(log2(2 bound / eps)) = 25) */
+  int32_t reserved;        /* 0 */
+  int64_t N;
+  int64_t Dsel;
+  int64_t ldx;
+  int64_t ld_signal;
+  int64_t ldy;
+  double bound;            /* zk_mnn_inverse: the search interval is [-bound, bound] */
+  const void* x;
+  const void* signal;
+  const void* image;
+  const int32_t* feat;     /* or NULL */
+  void* y;
+  void* ladj;              /* zk_mnn_forward */
+  void* work;              /* zk_mnn_forward with ladj_reduced */
+} zk_mnn_args_v1;
+int zk_mnn_forward(const zk_mnn_args_v1* args, void* stream);
+int zk_mnn_inverse(const zk_mnn_args_v1* args, void* stream);
+int zk_mnn_image_floats(int S, int n_hidden, int width0, int width1, int width2);
+
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *
  * out[n] = sum_d Normal(loc[d], scale[d]).log_prob(z[n, d]) (+ ladj[n] if ladj != NULL). */
 int zk_diag_normal_log_prob(int dtype, int64_t N, int64_t D, const void* z, const void* loc, const void* scale,

@@ -1,0 +1,333 @@
+// zuko_amd — monotone neural network of the neural autoregressive flow (NAF): value, derivative and bisection inverse.
+//
+// Replaces MNN.f + MonotonicTransform.call_and_ladj (zuko/flows/neural.py:56-71, zuko/transforms.py:623-637, zuko/nn.py:321-392):
+//     y = MonotonicMLP_f(cat(x, signal));  ladj = log dy/dx          (the reference: stacked einsums + torch.autograd.grad)
+// and MonotonicTransform._inverse + Bisection.forward (zuko/transforms.py:609-617, zuko/utils.py:170-178).  Every feature f owns a
+// small network (1 + S) -> H1 [-> H2 [-> H3]] -> 1 with weights |W| and the two-way ELU; it runs once per element (n, d).
+//
+// Execution model (gfx950):
+//   * a wavefront owns 16 elements of ONE feature for the whole network.  Every layer is computed transposed, H^T = |W| X^T, on
+//     v_mfma_f32_16x16x4_f32 (exact fp32): A = a 16 x 4 slice of |W| (rows = out units), B = a 4 x 16 slice of the activations
+//     (columns = elements).  Lane (j, q) = (lane & 15, lane >> 4) of the D fragment holds out units 16 t + 4 q + r (r = 0..3) of
+//     element j — which is what the next layer wants as its B operand once its K axis is enumerated as k-step r <-> units
+//     {r, 4 + r, 8 + r, 12 + r} of a 16-unit tile (the trick of csrc/fused_ar.hip): the weight image is laid out in that order, so
+//     activations stay in registers from the signal load to log dy/dx.
+//   * the derivative is carried in forward mode: the tangent enters as the column |w0[:, 0]| (no product needed), later layers
+//     multiply it by the same |W_l| fragment as the value (two accumulators per A operand) and scale by act'(pre).
+//   * the signal's share of the first layer, |W0[:, 1:]| signal + b0, is one short product per element; the bisection re-uses it
+//     in every one of its steps.
+//   * one feature's weight image (zuko_amd/mnn_plan.py: layout) sits in LDS, shared by the block's 4 wavefronts; a block covers
+//     rows_per_block rows x feats_per_block consecutive columns and walks its columns one image at a time, so the lines of x and
+//     of the signal a block touches are consumed by that block.  Nothing is staged through LDS besides the image.
+//   * the two-way ELU and its derivative run on the vector unit; the last layer (H -> 1) is a per-lane dot product and two
+//     cross-lane adds in a fixed order.  No atomics: ladj[N] is a second launch that adds the columns of a row in order.
+//
+// An element's y / ladj depends on its own x, signal and feature only: not on N, Dsel, the launch geometry or its neighbours.
+#include "../../include/zuko_amd.h"
+#include "zk_common.h"
+#include <mutex>
+#include <unordered_map>
+#include <utility>
+
+namespace zk {
+
+typedef float mnn_f4 __attribute__((ext_vector_type(4)));
+
+#define MNN_INLINE __attribute__((always_inline))
+#define MNN_LDS_MAX (128 * 1024)  // bound on one feature's image (two blocks of the default network's 21 KiB share a CU many times over)
+#define MNN_THREADS 256
+
+template <class F, int... I> __device__ __forceinline__ void mnn_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void mnn_for(F&& f) { mnn_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// Offsets (floats) of one feature's image; the same arithmetic as zuko_amd/mnn_plan.py: layout.
+struct MnnLayout {
+  int nh, S, ks;  // hidden layers, signal features, k-steps of the signal product = ceil(S / 4)
+  int T[3];       // 16-unit tiles per hidden layer
+  int o_w0s, o_w0x, o_b0, o_w[3], o_b[3], o_wl, o_bl, total;
+};
+
+static inline bool mnn_layout(int S, int nh, const int* widths, MnnLayout* L) {
+  if (S < 1 || S > 63 || nh < 1 || nh > 3) return false;
+  for (int l = 0; l < 3; ++l) {
+    const int h = l < nh ? widths[l] : 0;
+    if (l < nh ? (h < 16 || h > 128 || h % 16 != 0) : h != 0) return false;
+    L->T[l] = h / 16;
+  }
+  L->nh = nh; L->S = S; L->ks = (S + 3) / 4;
+  int o = 0;
+  L->o_w0s = o; o += L->T[0] * L->ks * 64;
+  L->o_w0x = o; o += L->T[0] * 16;
+  L->o_b0 = o; o += L->T[0] * 16;
+  L->o_w[0] = L->o_b[0] = 0;
+  for (int l = 1; l < 3; ++l) {
+    L->o_w[l] = o; if (l < nh) o += L->T[l] * L->T[l - 1] * 256;
+    L->o_b[l] = o; if (l < nh) o += L->T[l] * 16;
+  }
+  L->o_wl = o; o += L->T[nh - 1] * 16;
+  L->o_bl = o; o += 4;
+  L->total = o;
+  return o * 4 <= MNN_LDS_MAX;
+}
+
+struct MnnArgs {
+  const float* x;       // forward: x; inverse: the targets
+  const float* signal;
+  const float* image;
+  const int* feat;
+  float* y;             // forward: y; inverse: the solutions
+  float* ladj;          // [N, Dsel] (the per-element buffer, also when the caller asked for the row sums)
+  long long N, ldx, lds, ldy;
+  int Dsel, n_features, rows_per_block, feats_per_block, n_bisect;
+  float bound;
+  MnnLayout L;
+};
+
+// two-way ELU (zuko/nn.py:335-353): units below `half` take ELU(p), the others -ELU(-p); d = its derivative
+__device__ __forceinline__ void mnn_act(float p, bool first, float& v, float& d) {
+  const float s = first ? p : -p;
+  const float a = s > 0.f ? s : expm1f(s);
+  d = s > 0.f ? 1.f : expf(s);
+  v = first ? a : -a;
+}
+__device__ __forceinline__ float mnn_act(float p, bool first) {
+  const float s = first ? p : -p;
+  const float a = s > 0.f ? s : expm1f(s);
+  return first ? a : -a;
+}
+
+// c0 = |W0[:, 1:]| signal + b0 in the D layout (T1 tiles)
+template <int TM> __device__ __forceinline__ void mnn_signal(const MnnLayout& L, const float* lds, const float* __restrict__ sp, int lane, int q, mnn_f4 (&c0)[TM]) {
+  float sig[16];
+  mnn_for<16>([&](auto s) MNN_INLINE {
+    sig[s] = 0.f;
+    if (s < L.ks) sig[s] = (4 * s + q < L.S) ? sp[4 * s + q] : 0.f;
+  });
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < L.T[0]) c0[o] = *reinterpret_cast<const mnn_f4*>(lds + L.o_b0 + o * 16 + q * 4);
+  });
+  const float* const pw = lds + L.o_w0s + lane;  // (tile o, k-step s at o * ostride + 64 s: the k-step is an immediate offset of the read)
+  const int ostride = L.ks * 64;
+  mnn_for<16>([&](auto s) MNN_INLINE {
+    if (s < L.ks) {
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        if (o < L.T[0]) c0[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[o * ostride + s * 64], sig[s], c0[o], 0, 0, 0);
+      });
+    }
+  });
+}
+
+// one hidden-to-hidden layer: v <- act(|W| v + b), t <- act'(.) * (|W| t); tin / tout tiles, `half` = ceil(width / 2)
+template <int TM, bool TAN>
+__device__ __forceinline__ void mnn_hidden(const float* W, const float* B, int tin, int tout, int half, int lane, int q, mnn_f4 (&v)[TM], mnn_f4 (&t)[TM]) {
+  mnn_f4 ov[TM], ot[TM];
+  const int rowstride = tin * 256;  // the tiles of one out tile are consecutive: the in tile is an immediate offset of the read
+  mnn_for<TM / 2>([&](auto P) MNN_INLINE {
+    constexpr int o0 = 2 * P, o1 = o0 + 1;
+    if (o0 < tout) {
+      const bool two = o1 < tout;
+      const float* const p0 = W + o0 * rowstride + lane * 4;
+      const float* const p1 = p0 + rowstride;
+      ov[o0] = *reinterpret_cast<const mnn_f4*>(B + o0 * 16 + q * 4);
+      ov[o1] = two ? *reinterpret_cast<const mnn_f4*>(B + o1 * 16 + q * 4) : mnn_f4{0.f, 0.f, 0.f, 0.f};
+      ot[o0] = mnn_f4{0.f, 0.f, 0.f, 0.f};
+      ot[o1] = mnn_f4{0.f, 0.f, 0.f, 0.f};
+      mnn_for<TM>([&](auto it) MNN_INLINE {
+        if (it < tin) {
+          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(p0 + it * 256);
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            ov[o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], v[it][(int)r], ov[o0], 0, 0, 0);
+            if constexpr (TAN) ot[o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], t[it][(int)r], ot[o0], 0, 0, 0);
+          });
+          if (two) {
+            const mnn_f4 a1 = *reinterpret_cast<const mnn_f4*>(p1 + it * 256);
+            mnn_for<4>([&](auto r) MNN_INLINE {
+              ov[o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], v[it][(int)r], ov[o1], 0, 0, 0);
+              if constexpr (TAN) ot[o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], t[it][(int)r], ot[o1], 0, 0, 0);
+            });
+          }
+        }
+      });
+    }
+  });
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < tout) {
+      mnn_for<4>([&](auto r) MNN_INLINE {
+        const bool first = o * 16 + q * 4 + r < half;
+        if constexpr (TAN) {
+          float a, d;
+          mnn_act(ov[o][(int)r], first, a, d);
+          v[o][(int)r] = a;
+          t[o][(int)r] = d * ot[o][(int)r];
+        } else {
+          v[o][(int)r] = mnn_act(ov[o][(int)r], first);
+        }
+      });
+    }
+  });
+}
+
+// sum over the four lanes (j, 0..3) that hold one element: the same value in all four, the same order everywhere
+__device__ __forceinline__ float mnn_sum_q(float p) {
+  p += __shfl_xor(p, 16, 64);
+  p += __shfl_xor(p, 32, 64);
+  return p;
+}
+
+// the network behind the first layer's pre-activation: (y[, dy/dx]) of the element this lane belongs to
+template <int TM, bool TAN>
+__device__ __forceinline__ void mnn_tail(const MnnLayout& L, const float* lds, int lane, int q, float x, const mnn_f4 (&c0)[TM], float& y, float& dy) {
+  mnn_f4 v[TM], t[TM];
+  const int half0 = (L.T[0] * 16 + 1) / 2;
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < L.T[0]) {
+      const mnn_f4 w = *reinterpret_cast<const mnn_f4*>(lds + L.o_w0x + o * 16 + q * 4);
+      mnn_for<4>([&](auto r) MNN_INLINE {
+        const float pre = fmaf(w[(int)r], x, c0[o][(int)r]);
+        const bool first = o * 16 + q * 4 + r < half0;
+        if constexpr (TAN) {
+          float a, d;
+          mnn_act(pre, first, a, d);
+          v[o][(int)r] = a;
+          t[o][(int)r] = d * w[(int)r];
+        } else {
+          v[o][(int)r] = mnn_act(pre, first);
+        }
+      });
+    }
+  });
+  if (L.nh > 1) mnn_hidden<TM, TAN>(lds + L.o_w[1], lds + L.o_b[1], L.T[0], L.T[1], (L.T[1] * 16 + 1) / 2, lane, q, v, t);
+  if (L.nh > 2) mnn_hidden<TM, TAN>(lds + L.o_w[2], lds + L.o_b[2], L.T[1], L.T[2], (L.T[2] * 16 + 1) / 2, lane, q, v, t);
+  const int tl = L.T[L.nh - 1];
+  float py = 0.f, pd = 0.f;
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < tl) {
+      const mnn_f4 w = *reinterpret_cast<const mnn_f4*>(lds + L.o_wl + o * 16 + q * 4);
+      mnn_for<4>([&](auto r) MNN_INLINE {
+        py = fmaf(w[(int)r], v[o][(int)r], py);
+        if constexpr (TAN) pd = fmaf(w[(int)r], t[o][(int)r], pd);
+      });
+    }
+  });
+  y = mnn_sum_q(py) + lds[L.o_bl];
+  if constexpr (TAN) dy = mnn_sum_q(pd);
+}
+
+extern __shared__ __attribute__((aligned(16))) float mnn_lds[];
+
+template <int TM, bool INVERSE> __global__ __launch_bounds__(MNN_THREADS, 2) void mnn_kernel(MnnArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
+  const MnnLayout& L = a.L;
+  const long long row0 = (long long)blockIdx.x * a.rows_per_block;
+  for (int fc = 0; fc < a.feats_per_block; ++fc) {
+    const int col = blockIdx.y * a.feats_per_block + fc;
+    if (col >= a.Dsel) break;  // (uniform over the block)
+    int f = a.feat ? a.feat[col] : col;
+    f = f < 0 ? 0 : (f >= a.n_features ? a.n_features - 1 : f);  // (a memory guard only: the caller checks the range, zuko_amd/ops.py: _mnn_feat)
+    const float* img = a.image + (size_t)f * L.total;
+    __syncthreads();  // the previous column's image is no longer read
+    for (int i = tid * 4; i < L.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(mnn_lds + i) = *reinterpret_cast<const mnn_f4*>(img + i);
+    __syncthreads();
+    for (int tile = wave; tile * 16 < a.rows_per_block && row0 + tile * 16 < a.N; tile += MNN_THREADS / 64) {
+      const long long row = row0 + tile * 16 + j;
+      const long long rc = row < a.N ? row : a.N - 1;  // rows behind the end compute on the last row and store nothing
+      const float xin = a.x[rc * a.ldx + col];
+      mnn_f4 c0[TM];
+      mnn_signal<TM>(L, mnn_lds, a.signal + rc * a.lds + (size_t)col * L.S, lane, q, c0);
+      if constexpr (!INVERSE) {
+        float y, dy;
+        mnn_tail<TM, true>(L, mnn_lds, lane, q, xin, c0, y, dy);
+        if (q == 0 && row < a.N) {
+          a.y[row * a.ldy + col] = y;
+          a.ladj[row * a.Dsel + col] = logf(dy);
+        }
+      } else {
+        // zuko/utils.py:170-178 in fp32: n times c = (a + b) / 2, f(c) < y ? a = c : b = c; the answer is the last midpoint
+        float lo = -a.bound, hi = a.bound;
+        for (int it = 0; it < a.n_bisect; ++it) {
+          const float c = (lo + hi) / 2;
+          float fy, unused;
+          mnn_tail<TM, false>(L, mnn_lds, lane, q, c, c0, fy, unused);
+          const bool below = fy < xin;
+          lo = below ? c : lo;
+          hi = below ? hi : c;
+        }
+        if (q == 0 && row < a.N) a.y[row * a.ldy + col] = (lo + hi) / 2;
+      }
+    }
+  }
+}
+
+// ladj[n] = the columns of row n added left to right
+__global__ __launch_bounds__(256) void mnn_rowsum_kernel(const float* __restrict__ e, float* __restrict__ out, long long N, int D) {
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float s = 0.f;
+  for (int d = 0; d < D; ++d) s += e[n * D + d];
+  out[n] = s;
+}
+
+// Grant, launch, check — as ar_launch_dyn_lds of csrc/zk_ar_common.h (whose signature is tied to ArArgs and a one-dimensional grid): the opt-in to
+// more than 64 KiB of dynamic LDS is per function, set under a lock, once, and again only if a larger size is asked for.
+static int mnn_launch_dyn_lds(const void* fn, dim3 grid, int lds_bytes, MnnArgs& a, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  {
+    static std::mutex mu;
+    static std::unordered_map<const void*, int> granted;
+    std::lock_guard<std::mutex> lock(mu);
+    int& g = granted[fn];
+    if (g < lds_bytes) {
+      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+      if (e != hipSuccess) return (int)e;
+      g = lds_bytes;
+    }
+  }
+  void* kargs[] = {&a};
+  e = hipLaunchKernel(fn, grid, dim3(MNN_THREADS), kargs, lds_bytes, st);
+  if (e != hipSuccess) return (int)e;
+  return ZK_LAUNCH_CHECK();
+}
+
+template <bool INVERSE> static int mnn_launch(const zk_mnn_args_v1* p, void* stream) {
+  if (!p || p->struct_size != sizeof(zk_mnn_args_v1) || p->version != 1) return ZK_EINVAL;  // (argument block: include/zuko_amd.h)
+  MnnArgs a;
+  const int widths[3] = {p->width0, p->width1, p->width2};
+  if (!mnn_layout(p->S, p->n_hidden, widths, &a.L)) return ZK_EINVAL;
+  if (p->image_floats != a.L.total || p->n_features < 1 || p->N < 0 || p->Dsel < 1 || p->Dsel > (1 << 20)) return ZK_EINVAL;
+  if (p->ldx < 1 || p->ldy < p->Dsel || p->ld_signal < (int64_t)p->Dsel * p->S) return ZK_EINVAL;
+  if (INVERSE && (p->n_bisect < 0 || p->n_bisect > 64 || !(p->bound > 0))) return ZK_EINVAL;
+  if (p->N == 0) return 0;
+  if (!p->x || !p->signal || !p->image || !p->y) return ZK_EINVAL;
+  if (!INVERSE && (!p->ladj || (p->ladj_reduced && !p->work))) return ZK_EINVAL;
+  a.x = (const float*)p->x; a.signal = (const float*)p->signal; a.image = (const float*)p->image; a.feat = (const int*)p->feat;
+  a.y = (float*)p->y; a.ladj = (float*)(p->ladj_reduced ? p->work : p->ladj);
+  a.N = p->N; a.ldx = p->ldx; a.lds = p->ld_signal; a.ldy = p->ldy;
+  a.Dsel = (int)p->Dsel; a.n_features = p->n_features; a.n_bisect = p->n_bisect; a.bound = (float)p->bound;
+  // launch geometry (results do not depend on it): enough blocks for 256 CUs first, then longer runs per image load
+  const long long t64 = (a.N + 63) / 64;
+  a.feats_per_block = t64 * ((a.Dsel + 3) / 4) >= 512 ? 4 : 1;
+  const long long cols = (a.Dsel + a.feats_per_block - 1) / a.feats_per_block;
+  a.rows_per_block = 256;
+  while (a.rows_per_block > 64 && ((a.N + a.rows_per_block - 1) / a.rows_per_block) * cols < 1024) a.rows_per_block /= 2;
+  const long long gx = (a.N + a.rows_per_block - 1) / a.rows_per_block;
+  if (gx > 0x7fffffffLL || cols > 65535) return ZK_EINVAL;
+  const dim3 grid((unsigned)gx, (unsigned)cols);
+  const int lds_bytes = a.L.total * 4;
+  hipStream_t st = (hipStream_t)stream;
+  const bool small = a.L.T[0] <= 4 && a.L.T[1] <= 4 && a.L.T[2] <= 4;
+  const void* fn = small ? (const void*)mnn_kernel<4, INVERSE> : (const void*)mnn_kernel<8, INVERSE>;
+  int err = mnn_launch_dyn_lds(fn, grid, lds_bytes, a, st);
+  if (err != 0 || INVERSE || !p->ladj_reduced) return err;
+  hipLaunchKernelGGL(mnn_rowsum_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, (const float*)p->work, (float*)p->ladj, a.N, a.Dsel);
+  return ZK_LAUNCH_CHECK();
+}
+
+}  // namespace zk
+
+extern "C" int zk_mnn_forward(const zk_mnn_args_v1* args, void* stream) { return zk::mnn_launch<false>(args, stream); }
+extern "C" int zk_mnn_inverse(const zk_mnn_args_v1* args, void* stream) { return zk::mnn_launch<true>(args, stream); }
+extern "C" int zk_mnn_image_floats(int S, int n_hidden, int width0, int width1, int width2) {
+  zk::MnnLayout L;
+  const int widths[3] = {width0, width1, width2};
+  return zk::mnn_layout(S, n_hidden, widths, &L) ? L.total : -1;
+}

@@ -1,15 +1,18 @@
 r"""Flow factories of the hot path: MAF / NSF (autoregressive), NICE / RealNVP (coupling),
-SOSPF / BPF (polynomial).  Same constructor signatures and module trees as zuko.flows."""
+SOSPF / BPF (polynomial), NAF (monotone networks).  Same constructor signatures and module trees as zuko.flows."""
 
 from .autoregressive import MAF, MaskedAutoregressiveTransform
 from .coupling import NICE, GeneralCouplingTransform, RealNVP
 from .elementwise import ElementWiseTransform
+from .neural import MNN, NAF
 from .polynomial import BPF, SOSPF
 from .spline import NCSF, NSF
 
 __all__ = [
     "BPF",
     "MAF",
+    "MNN",
+    "NAF",
     "NCSF",
     "NICE",
     "NSF",

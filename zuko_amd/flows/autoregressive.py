@@ -611,6 +611,8 @@ class FusedAutoregressiveTransform(AutoregressiveTransform):
         lazy, c = self.lazy, self.c
         mods = list(lazy.hyper) if isinstance(lazy.hyper, torch.nn.Sequential) else []
         grad = torch.is_grad_enabled() and (y.requires_grad or (c is not None and c.requires_grad) or any(p.requires_grad for p in lazy.hyper.parameters()))
+        per_feature = isinstance(lazy.univariate, nn.Module) and getattr(lazy.univariate, "per_feature", False)  # (NAF: one monotone network per feature)
+        grad = grad or (torch.is_grad_enabled() and isinstance(lazy.univariate, nn.Module) and any(p.requires_grad for p in lazy.univariate.parameters()))
         if lazy.order is None or grad or not mods or type(mods[-1]) is not MaskedLinear or not y.is_cuda or y.dtype not in (torch.float32, torch.float64) or os.environ.get("ZUKO_AMD_FULL_SWEEPS", "0") == "1":
             return super()._inverse(y)  # free-form adjacency / a graph for autograd / a residual conditioner: the loop as the reference writes it
         from .. import ops
@@ -629,16 +631,20 @@ class FusedAutoregressiveTransform(AutoregressiveTransform):
                 return ops.linear(h, w, b, m, code or 0)
             return act_module(ops.linear(h, w, b, m))
 
-        x2 = wavefront_inverse(lazy, y2, c2, self.passes, linear, lambda phi, ys: lazy.univariate(*unpack(phi, lazy.shapes)).inv(ys))
+        if per_feature:  # the map's own parameters are stacked over the features: it must know which ones a sweep evaluates
+            x2 = wavefront_inverse(lazy, y2, c2, self.passes, linear, lambda phi, ys, idx: lazy.univariate(*unpack(phi, lazy.shapes), features=idx).inv(ys), with_features=True)
+        else:
+            x2 = wavefront_inverse(lazy, y2, c2, self.passes, linear, lambda phi, ys: lazy.univariate(*unpack(phi, lazy.shapes)).inv(ys))
         return x2.reshape(batch + (lazy.features,))
 
 
-def wavefront_inverse(lazy: "MaskedAutoregressiveTransform", y2: Tensor, c2: Tensor | None, passes: int, linear, inverse_of, stack=None) -> Tensor:
+def wavefront_inverse(lazy: "MaskedAutoregressiveTransform", y2: Tensor, c2: Tensor | None, passes: int, linear, inverse_of, stack=None, with_features: bool = False) -> Tensor:
     """The sweep loop of FusedAutoregressiveTransform._ordered_inverse on y2 [N, D] / c2 [N, C] | None; `linear(h, weight, bias, mask, activation
     module | None)` evaluates act(h (mask * weight)^T + bias) and `inverse_of(phi [N, k, total], y [N, k])` inverts the univariate maps of k
     features — the product passes the HIP kernels (ops.linear, the univariate transform's inv), tests/test_wavefront_inverse.py torch / oracle
     stand-ins to check the schedule on the CPU against the reference's loop.  `stack(modules, h)` evaluates the hidden layers as a whole when
-    the conditioner has no per-unit schedule (default: nn.apply_stack, the HIP layer kernels)."""
+    the conditioner has no per-unit schedule (default: nn.apply_stack, the HIP layer kernels).  `with_features=True`: `inverse_of` is called with a
+    third argument, the sweep's features — a (lo, hi) run or an index tensor on y2's device — for univariate maps whose own parameters are per feature."""
     from ..nn import apply_stack
 
     stack = apply_stack if stack is None else stack
@@ -682,7 +688,8 @@ def wavefront_inverse(lazy: "MaskedAutoregressiveTransform", y2: Tensor, c2: Ten
         else:
             rows, k = (idx[:, None] * total + torch.arange(total, device=dev)[None, :]).reshape(-1), idx.numel()
             w, b, m, ys = last.weight.index_select(0, rows), None if last.bias is None else last.bias.index_select(0, rows), last.mask.index_select(0, rows), y2.index_select(1, idx)
-        xs = inverse_of(linear(h, w, b, m, None).unflatten(-1, (k, total)), ys)
+        phi = linear(h, w, b, m, None).unflatten(-1, (k, total))
+        xs = inverse_of(phi, ys, idx) if with_features else inverse_of(phi, ys)
         if isinstance(idx, tuple):
             x2[:, idx[0] : idx[1]] = xs
         else:

@@ -17,7 +17,7 @@ from torch import BoolTensor, Tensor
 
 from . import ops
 
-__all__ = ["MLP", "Linear", "MaskedLinear", "MaskedMLP", "Residual"]
+__all__ = ["MLP", "Linear", "MaskedLinear", "MaskedMLP", "MonotonicLinear", "MonotonicMLP", "Residual", "TwoWayELU"]
 
 
 def _act_code(module: nn.Module | None) -> int | None:
@@ -35,15 +35,16 @@ def _act_code(module: nn.Module | None) -> int | None:
 
 
 class Linear(nn.Module):
-    r"""y = x W^T + b with U(-1/sqrt(in), 1/sqrt(in)) init.  Mirrors zuko/nn.py:51-119
-    (the `stack=` variant of the reference is outside the hot path and not provided)."""
+    r"""y = x W^T + b with U(-1/sqrt(in), 1/sqrt(in)) init.  Mirrors zuko/nn.py:51-119.  With `stack=S` the module holds S
+    independent operators, weight [S, out, in] and bias [S, out], applied to a stack of input vectors [*, S, in] (zuko/nn.py:13-22):
+    the per-feature networks of the neural autoregressive flow.  The stacked form is plain torch ops — the kernel that evaluates
+    those networks (csrc/mnn.hip) reads the parameters through its own weight image."""
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, stack: int | None = None) -> None:
         super().__init__()
-        if stack is not None:
-            raise NotImplementedError("zuko_amd.nn.Linear: stacked operators are outside the hot path")
-        self.weight = nn.Parameter(torch.empty(out_features, in_features))
-        self.bias = nn.Parameter(torch.empty(out_features)) if bias else None
+        shape = () if stack is None else (stack,)
+        self.weight = nn.Parameter(torch.empty(*shape, out_features, in_features))
+        self.bias = nn.Parameter(torch.empty(*shape, out_features)) if bias else None
         self.in_features = in_features
         self.out_features = out_features
         self.reset_parameters()
@@ -55,10 +56,36 @@ class Linear(nn.Module):
             nn.init.uniform_(self.bias, -bound, bound)
 
     def extra_repr(self) -> str:
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+        text = f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+        return text if self.weight.dim() == 2 else text + f", stack={self.weight.shape[0]}"
 
     def forward(self, x: Tensor, act: int = 0) -> Tensor:
+        if self.weight.dim() == 3:
+            return _stacked_linear(x, self.weight, self.bias)
         return ops.linear(x, self.weight, self.bias, None, act)
+
+
+def _stacked_linear(x: Tensor, W: Tensor, b: Tensor | None) -> Tensor:
+    """zuko/nn.py:13-22 for a stack of operators."""
+    y = torch.einsum("...ij,...j->...i", W, x)
+    return y if b is None else y + b
+
+
+class MonotonicLinear(Linear):
+    r"""y = x |W|^T + b.  Mirrors zuko/nn.py:321-332 (torch ops: the autograd and fallback path of the monotone networks)."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        if self.weight.dim() == 3:
+            return _stacked_linear(x, self.weight.abs(), self.bias)
+        return torch.nn.functional.linear(x, self.weight.abs(), self.bias)
+
+
+class TwoWayELU(nn.ELU):
+    r"""ELU(x) on the first half of the units (`torch.chunk`: ceil(width / 2)), -ELU(-x) on the second.  Mirrors zuko/nn.py:335-353."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        x0, x1 = torch.chunk(x, 2, dim=-1)
+        return torch.cat((super().forward(x0), -super().forward(-x1)), dim=-1)
 
 
 class MaskedLinear(nn.Linear):
@@ -133,6 +160,25 @@ class MLP(_FusedSequential):
         super().__init__(*layers)
         self.in_features = in_features
         self.out_features = out_features
+
+
+class MonotonicMLP(MLP):
+    r"""MLP with |W| weights and the two-way ELU: every entry of its Jacobian is positive.  Mirrors zuko/nn.py:356-392 (module tree,
+    state_dict keys and initialisation order).  `forward` is plain torch ops; inside a flow the stacked networks are evaluated by
+    zk_mnn_forward / zk_mnn_inverse (zuko_amd.transforms.MonotonicNetworkTransform)."""
+
+    def __init__(self, *args, **kwargs) -> None:
+        kwargs["activation"] = TwoWayELU
+        kwargs["normalize"] = False
+        super().__init__(*args, **kwargs)
+        for layer in self:
+            if isinstance(layer, Linear):
+                layer.__class__ = MonotonicLinear
+
+    def forward(self, x: Tensor) -> Tensor:
+        for m in self:
+            x = m(x)
+        return x
 
 
 class Residual(_FusedSequential):

@@ -2,7 +2,9 @@ r"""Tensor-level wrappers around the C-ABI.  PyTorch is used for device memory, 
 shape bookkeeping only; every arithmetic result comes out of a HIP kernel in libzuko_amd.so.
 
 All functions require tensors on a HIP device (`tensor.is_cuda`) in float32 or float64 and raise
-otherwise — there is no CPU or eager-PyTorch fallback.
+otherwise — there is no CPU or eager-PyTorch fallback.  One documented exception: the monotone networks of a neural autoregressive
+flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shapes their kernel does not serve, for float64 and for
+calls that need gradients (no adjoint kernel yet).
 """
 
 from __future__ import annotations
@@ -504,3 +506,193 @@ def sum_f64(v: Tensor, scale: float = 1.0) -> Tensor:
     err = _C.lib().zk_sum_f64(_dtype_code(v), v1.numel(), _ptr(v1), scale, _ptr(ws), _ptr(out), _stream())
     _C.check(err, "zk_sum_f64")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# monotone neural network (NAF): zk_mnn_forward / zk_mnn_inverse, torch ops when the kernel does not serve the call
+# ------------------------------------------------------------------------------------------------
+
+MNN_BOUND = 10.0
+MNN_EPS = 1e-6
+MNN_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_naf.py measures the kernels against it)
+
+
+def mnn_supported(S: int, widths) -> bool:
+    """True when zk_mnn_forward / zk_mnn_inverse serve per-feature networks (1 + S) -> widths -> 1: 1 <= S <= 63, one to three hidden
+    layers, every width a multiple of 16 and <= 128, and a weight image of at most 128 KiB (zuko_amd/mnn_plan.py: layout)."""
+    from . import mnn_plan
+
+    return mnn_plan.supported(int(S), tuple(widths))
+
+
+def _mnn_feat(network, feat, device):
+    """int32 device vector of the selected features (None = all, in order); `feat` is None, a (lo, hi) run or an index tensor.  The range is checked
+    here, on the host, where the indices originate (the kernel's own clamp is a memory guard).  Tables are cached per run, and per index tensor
+    OBJECT: the entry holds the tensor, so neither its id nor its storage can be handed to another tensor while the entry lives, and its version.
+    The price: up to 1024 index tensors and their device tables stay alive on the network until the cache is cleared (wholesale, when full, or
+    by zuko_amd.invalidate), and the first use of an index tensor copies it to the host, which synchronises the stream — the sweep schedule of an
+    autoregressive layer holds a handful of such tensors, made once."""
+    if feat is None:
+        return None
+    stack = next(iter(network.parameters())).shape[0]
+    cache = network.__dict__.setdefault("_mnn_feat_cache", {})
+    if len(cache) > 1024:
+        cache.clear()
+    if isinstance(feat, tuple):
+        lo, hi = int(feat[0]), int(feat[1])
+        if not 0 <= lo < hi <= stack:
+            raise IndexError(f"zuko_amd: monotone network: features [{lo}, {hi}) outside a stack of {stack} networks")
+        key = (str(device), lo, hi)
+        if key not in cache:
+            cache[key] = torch.arange(lo, hi, dtype=torch.int32, device=device)
+        return cache[key]
+    key = (str(device), id(feat))
+    entry = cache.get(key)
+    if entry is None or entry[0] is not feat or entry[1] != feat._version:
+        host = feat.detach().cpu()
+        if host.numel() and not (0 <= int(host.min()) and int(host.max()) < stack):
+            raise IndexError(f"zuko_amd: monotone network: feature indices outside a stack of {stack} networks")
+        entry = (feat, feat._version, host.to(device=device, dtype=torch.int32).contiguous())
+        cache[key] = entry
+    return entry[2]
+
+
+def _mnn_torch_f(network, x: Tensor, signal: Tensor, feat) -> Tensor:
+    """MNN.f (zuko/flows/neural.py:56-60) in torch ops, on the networks of the selected features."""
+    sel = None
+    if feat is not None:
+        sel = torch.arange(feat[0], feat[1], device=x.device) if isinstance(feat, tuple) else feat.to(device=x.device, dtype=torch.long)
+    xb, _ = torch.broadcast_tensors(x.unsqueeze(-1), signal[..., :1])
+    h = torch.cat((xb, signal.expand(xb.shape[:-1] + signal.shape[-1:])), dim=-1)
+    for m in network:
+        if hasattr(m, "weight"):
+            W, b = m.weight.abs(), m.bias
+            if sel is not None:
+                W, b = W.index_select(0, sel), None if b is None else b.index_select(0, sel)
+            h = torch.einsum("...ij,...j->...i", W, h)
+            h = h if b is None else h + b
+        else:
+            h = m(h)
+    return h.squeeze(-1)
+
+
+def _mnn_kernel_serves(network, x: Tensor, signal: Tensor):
+    """The network's weight image when the HIP kernels serve this call (fp32, supported shape, nothing asks for gradients), else None."""
+    from . import mnn_plan
+
+    params = list(network.parameters())
+    if not MNN_KERNEL:
+        return None
+    if x.dtype != torch.float32 or signal.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+        return None
+    if torch.is_grad_enabled() and (x.requires_grad or signal.requires_grad or any(p.requires_grad for p in params)):
+        return None
+    return mnn_plan.image_of(network, x.device)
+
+
+def _mnn_prepare(x: Tensor, signal: Tensor):
+    S = signal.shape[-1]
+    xb, sb = torch.broadcast_tensors(x.unsqueeze(-1), signal[..., :1])
+    xb, sb = xb.squeeze(-1), signal.expand(xb.shape[:-1] + (S,))  # ([..., D, 1] -> x [..., D], signal [..., D, S])
+    shape = xb.shape
+    D = shape[-1]
+    x2, s2 = xb.reshape(-1, D), sb.reshape(-1, D * S)
+    if x2.stride(-1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < D):
+        x2 = x2.contiguous()
+    if s2.stride(-1) != 1 or (s2.shape[0] > 1 and s2.stride(0) < D * S):
+        s2 = s2.contiguous()
+    return shape, x2, s2
+
+
+def _mnn_args(img, x2: Tensor, s2: Tensor, feat, out: Tensor, **extra):
+    N, D = x2.shape
+    lay = img.layout
+    w = list(lay.widths) + [0, 0]
+    return _C.args("zk_mnn_args_v1", S=lay.S, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], n_features=img.features, image_floats=lay.total,
+                   N=N, Dsel=D, ldx=x2.stride(0) if N > 1 else D, ld_signal=s2.stride(0) if N > 1 else D * lay.S, ldy=D, x=x2.data_ptr(), signal=s2.data_ptr(),
+                   image=img.data.data_ptr(), feat=None if feat is None else feat.data_ptr(), y=out.data_ptr(), **extra)
+
+
+def _mnn_check(network, x: Tensor, signal: Tensor, feat) -> None:
+    _require_device(x, signal, *network.parameters())
+    if x.dim() < 1 or signal.dim() < 2 or signal.shape[-2] != x.shape[-1]:
+        raise ValueError(f"zuko_amd: monotone network: x [..., D] and signal [..., D, S] expected, got {tuple(x.shape)} and {tuple(signal.shape)}")
+    n_sel = x.shape[-1]
+    stack = next(iter(network.parameters())).shape[0]
+    if (feat is None and n_sel != stack) or (isinstance(feat, tuple) and feat[1] - feat[0] != n_sel) or (isinstance(feat, Tensor) and feat.numel() != n_sel):
+        raise ValueError(f"zuko_amd: monotone network: {n_sel} columns do not match the feature selection of a stack of {stack} networks")
+
+
+def mnn_forward(x: Tensor, signal: Tensor, network, feat=None, reduce: bool = False):
+    """(y, ladj) of the per-feature monotone networks `network` (a stacked zuko_amd.nn.MonotonicMLP(1 + S, 1, ...)): x [..., D], signal
+    [..., D, S]; column j uses the network of feature feat[j] (`feat`: None, a (lo, hi) run or an index tensor).  zk_mnn_forward when it
+    serves the call; otherwise (unsupported shape, float64, gradients) the reference's torch ops with torch.autograd.grad for the
+    derivative (zuko/transforms.py:623-637)."""
+    _mnn_check(network, x, signal, feat)
+    img = _mnn_kernel_serves(network, x, signal)
+    if img is None:
+        create_graph = torch.is_grad_enabled() and (x.requires_grad or signal.requires_grad or any(p.requires_grad for p in network.parameters()))
+        with torch.enable_grad():
+            xg = x.clone().requires_grad_()
+            y = _mnn_torch_f(network, xg, signal, feat)
+        jac = torch.autograd.grad(y, xg, torch.ones_like(y), create_graph=create_graph)[0]
+        if not create_graph:
+            y = y.detach()
+        ladj = jac.log()
+        return y, (ladj.sum(dim=-1) if reduce else ladj)
+    shape, x2, s2 = _mnn_prepare(x, signal)
+    N, D = x2.shape
+    data = img.refresh(network)
+    y = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x.device)
+    work = torch.empty((N, D), dtype=torch.float32, device=x.device) if reduce else None
+    a = _mnn_args(img, x2, s2, _mnn_feat(network, feat, x.device), y, ladj=ladj.data_ptr(), work=None if work is None else work.data_ptr(), ladj_reduced=int(reduce))
+    _C.check(_C.lib().zk_mnn_forward(a, _stream()), "zk_mnn_forward")
+    del data
+    return y.reshape(shape), ladj.reshape(shape[:-1] if reduce else shape)
+
+
+class _MnnBisection(torch.autograd.Function):
+    """Bisection on [-bound, bound] in torch ops, gradients by implicit differentiation: dx = dy / f'(x), dphi = -f_phi(x) dy / f'(x)."""
+
+    @staticmethod
+    def forward(ctx, f, y, bound, n, *phi):
+        lo, hi = torch.full_like(y, -bound), torch.full_like(y, bound)
+        for _ in range(n):
+            mid = (lo + hi) / 2
+            below = f(mid) < y
+            lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+        x = (lo + hi) / 2
+        ctx.f = f
+        ctx.save_for_backward(x, *phi)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x):
+        x, *phi = ctx.saved_tensors
+        with torch.enable_grad():
+            x = x.detach().requires_grad_()
+            y = ctx.f(x)
+        jac = torch.autograd.grad(y, x, torch.ones_like(y), retain_graph=bool(phi))[0]
+        grad_y = grad_x / jac
+        grad_phi = torch.autograd.grad(y, phi, -grad_y) if phi else ()
+        return (None, grad_y, None, None, *grad_phi)
+
+
+def mnn_inverse(y: Tensor, signal: Tensor, network, feat=None, bound: float = MNN_BOUND, eps: float = MNN_EPS) -> Tensor:
+    """x with f(x) = y by n = ceil(log2(2 bound / eps)) bisection steps on [-bound, bound] (zuko/transforms.py:609-617): zk_mnn_inverse,
+    or the same loop in torch ops when the kernel does not serve the call (see mnn_forward)."""
+    _mnn_check(network, y, signal, feat)
+    n = math.ceil(math.log2(2 * bound / eps))
+    img = _mnn_kernel_serves(network, y, signal)
+    if img is None:
+        phi = [p for p in (signal, *network.parameters()) if p.requires_grad] if torch.is_grad_enabled() else []
+        return _MnnBisection.apply(lambda v: _mnn_torch_f(network, v, signal, feat), y, float(bound), n, *phi)
+    shape, y2, s2 = _mnn_prepare(y, signal)
+    data = img.refresh(network)
+    x = torch.empty(y2.shape, dtype=torch.float32, device=y.device)
+    a = _mnn_args(img, y2, s2, _mnn_feat(network, feat, y.device), x, n_bisect=n, bound=float(bound))
+    _C.check(_C.lib().zk_mnn_inverse(a, _stream()), "zk_mnn_inverse")
+    del data
+    return x.reshape(shape)

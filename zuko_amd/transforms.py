@@ -35,6 +35,7 @@ __all__ = [
     "CouplingTransform",
     "DependentTransform",
     "MonotonicAffineTransform",
+    "MonotonicNetworkTransform",
     "MonotonicRQSTransform",
     "SOSPolynomialTransform",
     "ShiftedSOSPolynomialTransform",
@@ -179,6 +180,30 @@ class BoundedBernsteinTransform(BernsteinTransform):
     r"""Bernstein polynomial pinned to the identity at +-B.  Mirrors zuko/transforms.py:780-831."""
 
     bounded = True
+
+
+class MonotonicNetworkTransform(_Univariate):
+    r"""y_d = f_d(x_d | signal_d) with f_d the monotone network of feature d (a stacked `zuko_amd.nn.MonotonicMLP(1 + S, 1, ...)`), the
+    univariate map of the neural autoregressive flow.  Mirrors MNN.f + MonotonicTransform (zuko/flows/neural.py:56-71,
+    zuko/transforms.py:570-637): value and log-derivative in one launch (zk_mnn_forward; the derivative in forward mode instead of
+    torch.autograd.grad), the inverse by the reference's bisection on [-bound, bound] to `eps` (zk_mnn_inverse).  `features`: the
+    networks the columns of x belong to — None (all, in order), a (lo, hi) run or an index tensor; the ordered inverse of an
+    autoregressive layer evaluates one sweep's features at a time.  Unsupported network shapes, float64 and calls that need
+    gradients run the same expressions as torch ops (zuko_amd/ops.py: mnn_forward)."""
+
+    def __init__(self, signal: Tensor, network, features=None, bound: float = 10.0, eps: float = 1e-6, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.signal = signal
+        self.network = network
+        self.features = features
+        self.bound = bound
+        self.eps = eps
+
+    def _forward(self, x, reduce):
+        return ops.mnn_forward(x, self.signal, self.network, self.features, reduce)
+
+    def _inverse(self, y: Tensor) -> Tensor:
+        return ops.mnn_inverse(y, self.signal, self.network, self.features, self.bound, self.eps)
 
 
 # ------------------------------------------------------------------------------------------------
