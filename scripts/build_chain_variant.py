@@ -18,7 +18,6 @@ sa._find = lambda name: None  # (the current kernels of lib/ars have the same na
 for kind, bins in (("rqs", 8), ("affine", 0)):
     for plan, layout, lins in sa._plans_for(kind, 64, 0, (256, 256, 256), bins):
         t = sa.chain_tables_for(lins, full=True, packed={"uni": layout.kind, "featmap": plan.featmap, "nt": layout.nt, "fpl": layout.fpl, "total": layout.total})[0]
-        stamp = sa._header_digest()
-        stem = "arsd_" + sa._digest({"t": t, "headers": stamp})
-        meta = {"so": stem + ".so", "headers": stamp, "core": "chain", "l0": [], "alt": None, "DIN": t["DIN0"], "DOUT": t["DOUT"], "HT": t["HT"], "flags": flags}
-        print(sa._build_so(stem, lambda: sa.emit_chain_split(t), meta, False, out))
+        fam = sa.FAMILIES["arsd"][t["chain"]]
+        stem, meta = sa._identity(fam, t)
+        print(sa._build_so(stem, lambda: sa.emit(fam, t), dict(meta, flags=flags), False, out))

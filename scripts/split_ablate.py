@@ -33,10 +33,10 @@ def build():
     os.makedirs(OUT, exist_ok=True)
     src = os.path.join(OUT, "arx_cfg2.hip")
     with open(src, "w") as f:
-        f.write((sa.emit_half if HALF else sa.emit_split)(t))
+        f.write(sa.emit(sa.ARH if HALF else sa.ARX, t))
     procs = []
     for k in (NAMES if os.environ.get("ABL_ONLY0", "0") != "1" else [0]):
-        cmd = [sa._hipcc(), "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result", "-Wno-uninitialized", "-ffp-contract=off", f"-I{sa.CSRC}", f"-DARX_ABL={k}", "-shared",
+        cmd = [sa._hipcc(), *sa.hipcc_flags(), f"-DARX_ABL={k}", "-shared",
                "-no-hip-rt", src, f"-L{sa._torch_lib_dir()}", "-l:libamdhip64.so", "-o", os.path.join(OUT, f"arx_abl{k}.so")] + sys.argv[2:]
         procs.append(subprocess.Popen(cmd))
     assert all(p.wait() == 0 for p in procs)
@@ -80,9 +80,7 @@ def run():
             a = st._half_args(N=N, DIN=64, x=_ptr(x), ldx=64, y=_ptr(y), ldy=64, ladj=_ptr(ladj), accumulate=0)
             a.launcher = launcher.value
         else:
-            a = _C.args("zk_ar_args_v1", launcher=launcher, rev=0, uni_kind=p.layout.kind, N=N, D=64, DIN=64, x=_ptr(x), ldx=64, y=_ptr(y), ldy=64, ladj=_ptr(ladj), accumulate=0,
-                        wstream=_ptr(st.fine_stream), bias=_ptr(st.bias), bias_floats=st.bias_floats, featmap=_ptr(st.featmap), n_layers=p.n_layers, n_groups=p.n_groups,
-                        n_chunks=st.fine_n_chunks, act=1, bound=st.bound, slope=st.slope)
+            a = st.static_args(launcher, 0, st.fine, N=N, DIN=64, x=_ptr(x), ldx=64, y=_ptr(y), ldy=64, ladj=_ptr(ladj), accumulate=0)
         fn = lambda: _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
         for _ in range(3):
             fn()

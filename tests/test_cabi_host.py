@@ -233,3 +233,68 @@ def test_jit_threshold_counts_rows_over_calls(monkeypatch):
         __slots__ = ()
 
     assert static_ar.effective_rows(Slotted(), 300) == 300  # (nowhere to keep the count: the per-call rule)
+
+
+def test_generated_kernel_lookup_precedence(tmp_path, monkeypatch):
+    """zuko_amd/static_ar.py: lookup / lookup_half over a synthetic index and a stubbed loader (nothing is compiled or loaded).  The operand-split
+    kernel is preferred to the f32-instruction one; a kernel whose ALTERNATIVE first-layer pattern matches serves the plan as rev 1; a kind that
+    exists as a split kernel only has no f32 tier; a meta stamped by other headers is not indexed; the two-part kernel is not handed out under
+    ZUKO_AMD_MATMUL=bf16x3 or ZUKO_AMD_EXACT_F32=1."""
+    import json
+
+    from zuko_amd import fused, static_ar
+
+    for name in ("ZUKO_AMD_EXACT_F32", "ZUKO_AMD_MATMUL", "ZUKO_AMD_NO_STATIC_AR", "ZUKO_AMD_SPLIT_GEOM", "ZUKO_AMD_CACHE_DIR"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("ZUKO_AMD_JIT", "0")
+    monkeypatch.setattr(fused, "_precision", None)
+    monkeypatch.setattr(static_ar, "_load", lambda meta, *a, **k: meta["so"])
+
+    def index(*metas):
+        idx = {}
+        for m in metas:
+            idx.setdefault(m["core"], []).append(m)
+        monkeypatch.setattr(static_ar, "_INDEX", idx)
+
+    (pa, lay, _), (pd, _, _) = static_ar._plans_for("rqs", 64, 0, (256, 256, 256), 8)
+    (core, la), (core_d, ld) = static_ar._split(static_ar.tables(pa, lay.kind, 1)), static_ar._split(static_ar.tables(pd, lay.kind, 1))
+    assert core == core_d and la != ld  # the two feature orders differ in the first layer's input tiles only
+    f32 = {"so": "f32.so", "core": static_ar._digest(core), "l0": la, "alt": ld}
+    split = {"so": "split.so", "core": "x" + static_ar._digest(static_ar.split_tables(pa, lay.kind, 1)[0]), "l0": [], "alt": None}
+    half = {"so": "half.so", "core": "h" + static_ar._digest(static_ar.half_tables(pa, lay.kind, 1)[0]), "l0": [], "alt": None}
+    index(f32, split, half)
+    assert static_ar.lookup(pa, lay.kind, 1) == ("split.so", 0)
+    assert static_ar.lookup(pd, lay.kind, 1) == ("f32.so", 1)  # (no split kernel of the descending order in this index)
+    index(f32)
+    assert static_ar.lookup(pa, lay.kind, 1) == ("f32.so", 0) and static_ar.lookup(pd, lay.kind, 1) == ("f32.so", 1)
+    index(dict(f32, alt=None))
+    assert static_ar.lookup(pd, lay.kind, 1) is None
+    # 16 bins: an operand-split kernel or none, even with an f32-instruction kernel of that shape in the index
+    (p16, lay16, _), _ = static_ar._plans_for("rqs", 64, 0, (256, 256, 256), 16)
+    assert lay16.kind in static_ar.SPLIT_ONLY_KINDS
+    core16, l16 = static_ar._split(static_ar.tables(p16, lay16.kind, 1))
+    index({"so": "f32_16.so", "core": static_ar._digest(core16), "l0": l16, "alt": None})
+    assert static_ar.lookup(p16, lay16.kind, 1) is None
+    index({"so": "split_16.so", "core": "x" + static_ar._digest(static_ar.split_tables(p16, lay16.kind, 1)[0]), "l0": [], "alt": None})
+    assert static_ar.lookup(p16, lay16.kind, 1) == ("split_16.so", 0)
+    # the two-part kernel
+    index(f32, split, half)
+    assert static_ar.lookup_half(pa, lay.kind, 1) == "half.so"
+    monkeypatch.setenv("ZUKO_AMD_EXACT_F32", "1")
+    assert static_ar.lookup_half(pa, lay.kind, 1) is None and static_ar.lookup(pa, lay.kind, 1) == ("f32.so", 0)
+    monkeypatch.delenv("ZUKO_AMD_EXACT_F32")
+    monkeypatch.setenv("ZUKO_AMD_MATMUL", "bf16x3")
+    monkeypatch.setattr(fused, "_precision", None)  # (the mode is read from the environment once)
+    assert static_ar.lookup_half(pa, lay.kind, 1) is None and static_ar.lookup(pa, lay.kind, 1) == ("split.so", 0)
+    monkeypatch.delenv("ZUKO_AMD_MATMUL")
+    monkeypatch.setattr(fused, "_precision", None)
+    # the scan of the kernel directories: a meta is indexed when its .so is there and its stamp is that of the current headers
+    d = tmp_path / "ars"
+    d.mkdir()
+    monkeypatch.setenv("ZUKO_AMD_CACHE_DIR", str(tmp_path))
+    for name, stamp in (("fresh", static_ar._header_digest()), ("stale", "0" * 12), ("fresh_h", static_ar._half_digest())):
+        (d / f"{name}.so").write_bytes(b"")
+        (d / f"{name}.json").write_text(json.dumps({"so": f"{name}.so", "core": "synthetic", "l0": [], "alt": None, "headers": stamp, "half": int(name == "fresh_h")}))
+    (d / "gone.json").write_text(json.dumps({"so": "gone.so", "core": "synthetic", "l0": [], "alt": None, "headers": static_ar._header_digest()}))
+    monkeypatch.setattr(static_ar, "_INDEX", None)
+    assert sorted(m["so"] for m in static_ar._scan()["synthetic"]) == ["fresh.so", "fresh_h.so"]

@@ -125,7 +125,7 @@ def _isa_of_generated(cfgs):
         (pa, lay, _), (pd, _, _) = static_ar._plans_for(*cfg)
         ta, td = static_ar.tables(pa, lay.kind), static_ar.tables(pd, lay.kind)
         (ca, la), (cd, ld) = static_ar._split(ta), static_ar._split(td)
-        src = static_ar.emit(ta, ld if (ca == cd and la != ld) else None)
+        src = static_ar.emit(static_ar.ARS, ta, ld if (ca == cd and la != ld) else None)
         h = hashlib.sha256((src + static_ar._header_digest()).encode()).hexdigest()[:16]
         out = os.path.join(ROOT, "zuko_amd", "lib", f"ars_isa.{h}.s")
         jobs.append((src, out, ta))
@@ -137,8 +137,7 @@ def _isa_of_generated(cfgs):
             hip = out[:-2] + ".hip"
             with open(hip, "w") as f:
                 f.write(src)
-            subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-result", "-Wno-uninitialized", "-ffp-contract=off", f"-I{CSRC}", "--cuda-device-only", "-S",
-                            hip, "-o", out], check=True, stderr=subprocess.DEVNULL)
+            subprocess.run([hipcc, *static_ar.hipcc_flags(), "--cuda-device-only", "-S", hip, "-o", out], check=True, stderr=subprocess.DEVNULL)
         return open(out).read()
 
     with ThreadPoolExecutor(max_workers=4) as ex:

@@ -5,7 +5,7 @@ csrc/fused_ar_half_impl.h pins the vector work between the matrix instructions: 
 value, the ReLU one v_max_f32, the sample maximum one v_max3_f32 per pair, the last layer's descale one fma per parameter.  Left
 to the compiler the same source costs 500 vector instructions more per launch (the split converts its high part back to f32,
 the vectoriser gathers register pairs with v_mov) and spills.  The test generates the kernel of NSF(64, hidden 256 x 3, 8 bins)
-as zuko_amd/static_ar.py does, compiles it to ISA with the flags of static_ar._build_so (cached per source + header hash under
+as zuko_amd/static_ar.py does, compiles it to ISA with the flags of static_ar._build_so (static_ar.hipcc_flags; cached per source + header hash under
 zuko_amd/lib/) and bounds the instruction mix of the product instantiation (DIAG = false)."""
 
 import collections
@@ -28,7 +28,7 @@ def _isa() -> str:
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     (plan, lay, _), _ = static_ar._plans_for(*CFG2)
-    src = static_ar.emit_half(static_ar.half_tables(plan, lay.kind, 1)[0])
+    src = static_ar.emit(static_ar.ARH, static_ar.half_tables(plan, lay.kind, 1)[0])
     h = hashlib.sha256((src + static_ar._half_digest()).encode()).hexdigest()[:16]
     out = os.path.join(ROOT, "zuko_amd", "lib", f"arh_isa.{h}.s")
     if not os.path.exists(out):
@@ -37,8 +37,7 @@ def _isa() -> str:
         with open(hip, "w") as f:
             f.write(src)
         tmp = out + f".{os.getpid()}"
-        subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result", "-Wno-uninitialized", "-ffp-contract=off", f"-I{CSRC}",
-                        "--cuda-device-only", "-S", hip, "-o", tmp], check=True, stderr=subprocess.DEVNULL)
+        subprocess.run([hipcc, *static_ar.hipcc_flags(), "--cuda-device-only", "-S", hip, "-o", tmp], check=True, stderr=subprocess.DEVNULL)
         os.replace(tmp, out)
     return open(out).read()
 

@@ -292,7 +292,7 @@ def test_static_kernel_tables_describe_the_plan(cfg):
                         if f >= 0:
                             assert np.allclose(acc[:, g, tt, r], phi[:, f, p_], rtol=1e-9, atol=1e-9), (cfg, i, g, tt, r)
     # the emitted source carries exactly these tables
-    src = static_ar.emit(tabs[0], None if la == ld or ca != cd else ld)
+    src = static_ar.emit(static_ar.ARS, tabs[0], None if la == ld or ca != cd else ld)
     assert f"NCHUNK = {tabs[0]['NCHUNK']}" in src and "zk_ars_launch" in src and ("HAS_ALT = true" in src) == (ca == cd and la != ld)
 
 
@@ -812,7 +812,7 @@ def test_generic_split_kernel_selection(monkeypatch):
     assert st is not None and st.static is None and st.generic_ok
     gs = st._gsplit()
     assert gs is not None
-    gathers, offsets, n_chunks, stream = gs
+    gathers, offsets, n_chunks, stream = gs.gather, gs.offsets, gs.n_chunks, gs.buf
     assert stream.numel() == n_chunks * fused.GS_BLOCKS_PER_CHUNK * 768 and sum(g.numel() for g in gathers) == n_chunks * fused.GS_BLOCKS_PER_CHUNK * 512
     assert offsets == [768 * sum(g.numel() // 512 for g in gathers[:l]) for l in range(len(gathers))]
     st.gs_mode = "0"
@@ -826,3 +826,124 @@ def test_generic_split_kernel_selection(monkeypatch):
         assert st2._gsplit() is None
         st2.gs_mode = "force"
         assert st2._gsplit() is not None
+
+
+class _FakeKernel:
+    """What static_ar.lookup / lookup_half hand out: a loaded generated kernel, here with a made-up launcher address."""
+
+    def __init__(self, launcher, **meta):
+        import ctypes
+
+        self.launcher, self.meta = ctypes.c_void_p(launcher), meta
+
+
+class _LaunchRecorder:
+    """Stands in for the loaded library: every entry point records its argument block and reports success."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def entry(*args):
+            if name.startswith("zk_ar_forward"):
+                a = args[0]
+                self.calls.append((name, a.launcher, a.wstream, a.n_chunks, bool(a.base_loc)))
+            return 0
+
+        return entry
+
+
+F32_LAUNCHER, SPLIT_LAUNCHER, HALF_LAUNCHER = 0x1000, 0x2000, 0x3000
+
+
+def _expected_launch(kind, D, generated, half, mode, y, xlds):
+    """(entry point, stream) of FusedAR.run() or None when it must refuse, restated from the documented order: the two-part kernel, the generic
+    operand-split kernel, the generated kernel, the generic f32 kernel.  y: "aligned" | "misaligned" | "terminal"."""
+    terminal, rows_ok = y == "terminal", y != "misaligned"  # (rows staged through LDS are written 16 bytes at a time; a terminal launch writes none)
+    if half and mode != "force" and (not xlds or rows_ok):
+        return "zk_ar_forward_static", "half"
+    if kind <= 4 and mode != "0" and (generated == "none" or mode == "force"):  # the generic operand-split kernel's stream is kept current
+        if terminal:
+            return None  # (it has no terminal instantiation — also where a launch that writes rows would pass it by: 4 / 16 bins on features % 4 != 0)
+        if kind <= 1 or (D % 4 == 0 and rows_ok):
+            return "zk_ar_forward_split", "gs"
+    if generated != "none" and (not xlds or rows_ok):
+        if terminal and (generated != "split" or kind in (5, 6)):
+            return None
+        return "zk_ar_forward_static", "fine"
+    if terminal or kind > 4:
+        return None
+    return "zk_ar_forward", "generic"
+
+
+@pytest.mark.parametrize("cfg", [("affine", 12, 0, (64, 64), 0), ("rqs", 12, 0, (64, 64), 8), ("sos", 12, 0, (64, 64), 0), ("rqs", 10, 0, (64, 64), 4)])
+def test_product_launch_choice(cfg, monkeypatch):
+    """Which entry point and which weight stream FusedAR.run() uses (host logic, no GPU; the library is a recorder), over {no generated kernel, f32
+    generated, operand-split generated} x {two-part kernel held and eligible, or not} x ZUKO_AMD_GSPLIT {1, 0, force} x {rows 16-byte aligned,
+    misaligned, terminal launch} x XLDS {0, 1}, for the affine map, the 8-bin spline, the SOS polynomial (generated kernels only) and the 4-bin spline
+    on 10 features — the one shape where, under `force` beside a generated kernel, a launch that writes rows passes the generic operand-split kernel by
+    while serves_terminal() answers False.  serves_terminal() must be True exactly when run(..., base=) does not raise."""
+    from zuko_amd import _C, fused, static_ar
+
+    for name in ("ZUKO_AMD_GSPLIT", "ZUKO_AMD_EXACT_F32", "ZUKO_AMD_MATMUL", "ZUKO_AMD_NO_STATIC_AR"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(fused, "_precision", None)
+    rec = _LaunchRecorder()
+    monkeypatch.setattr(_C, "lib", lambda: rec)
+    monkeypatch.setattr(_C, "stream", lambda: 0)
+    monkeypatch.setattr(_C, "gather_multi", lambda items, stream: None)
+    cpu = torch.device("cpu")
+    (plan, lay, lins), _ = static_ar._plans_for(*cfg)
+    kind, D, N = lay.kind, cfg[1], 8
+    assert kind == {("affine", 0): 0, ("rqs", 8): 1, ("rqs", 4): 2, ("sos", 0): 5}[cfg[0], cfg[4]]
+    two_part = kind in (0, 1)  # (the polynomial maps have no two-part kernel; one shape with 4 bins is enough for the row this case is here for)
+    inp, ladj = torch.zeros(N, plan.din + (-plan.din % 4)), torch.zeros(N)
+    ld = D + (-D % 4)  # (rows a multiple of 16 bytes apart; "misaligned" starts them 4 bytes off)
+    ys = {"aligned": torch.empty(N, ld)[:, :D], "misaligned": torch.empty(N * ld + 1)[1:].view(N, ld)[:, :D], "terminal": None}
+    assert ys["aligned"].data_ptr() % 16 == 0 and ys["misaligned"].data_ptr() % 16 != 0 and ys["aligned"].stride(0) % 4 == 0
+    base = (torch.zeros(D), torch.ones(D))
+    rows = 0
+    for generated in ("none", "f32", "split"):
+        for half in ((False, True) if two_part else (False,)):
+            for xlds in (0, 1):
+                found = {"none": None, "f32": (_FakeKernel(F32_LAUNCHER, XLDS=xlds), 0), "split": (_FakeKernel(SPLIT_LAUNCHER, split=1, XLDS=xlds), 0)}[generated]
+                monkeypatch.setattr(static_ar, "lookup", lambda *a, found=found, **k: found)
+                monkeypatch.setattr(static_ar, "lookup_half", lambda *a, half=half, xlds=xlds, **k: _FakeKernel(HALF_LAUNCHER, half=1, split=2, XLDS=xlds) if half else None)
+                st = fused.FusedAR(plan, cpu, 1, 5.0, 1e-3)
+                assert (st.static is not None) == (generated != "none") and (st.half is not None) == half
+                chunks = {"generic": plan.n_chunks, "half": static_ar.half_tables(plan, kind, 1)[0]["NCHUNK"] if half else None,
+                          "fine": {"none": None, "f32": plan.fine_n_chunks, "split": static_ar.split_tables(plan, kind, 1)[0]["NCHUNK"]}[generated],
+                          "gs": fused.gsplit_gather(plan)[2] if kind <= 4 else None}
+                where = {}  # stream name -> address: one buffer per stream, whatever the row
+                for mode in ("1", "0", "force"):
+                    st.gs_mode = mode
+                    st.refresh(lins)
+                    assert st.half_ok == half, "freshly initialised weights are eligible for the two-part kernel"
+                    for y_kind, y in ys.items():
+                        want = _expected_launch(kind, D, generated, half, mode, y_kind, xlds)
+                        row = (cfg[0], generated, half, xlds, mode, y_kind)
+                        del rec.calls[:]
+                        if y_kind == "terminal":
+                            fits = plan.n_groups * 4 * lay.fpl + 3 * D <= 1024
+                            assert fits and st.serves_terminal() == (want is not None), row
+                            if want is None:
+                                with pytest.raises(RuntimeError):
+                                    st.run(inp, None, ladj, False, base=base)
+                                assert not rec.calls, row
+                                continue
+                            st.run(inp, None, ladj, False, base=base)
+                        elif want is None:
+                            with pytest.raises(RuntimeError):
+                                st.run(inp, y, ladj, False)
+                            assert not rec.calls, row
+                            continue
+                        else:
+                            st.run(inp, y, ladj, False)
+                        assert len(rec.calls) == 1, row
+                        entry, launcher, wstream, n_chunks, has_base = rec.calls[0]
+                        assert (entry, n_chunks, has_base) == (want[0], chunks[want[1]], y_kind == "terminal"), (row, rec.calls[0], want)
+                        assert launcher == {"half": HALF_LAUNCHER, "fine": SPLIT_LAUNCHER if generated == "split" else F32_LAUNCHER}.get(want[1]), row
+                        assert where.setdefault(want[1], wstream) == wstream and wstream, row
+                        rows += 1
+                assert len(set(where.values())) == len(where) and where.get("generic", st.stream.data_ptr()) == st.stream.data_ptr()
+    assert rows >= (60 if two_part else 14)

@@ -474,6 +474,19 @@ def half_scales(linears):
     return out
 
 
+@dataclass
+class WeightStream:
+    """One gathered copy of a conditioner's masked weights on the device, in the order one kernel reads it."""
+
+    gather: list         # per linear layer: int32 gather indices into W_l.flatten() (-1 = zero), on the device
+    offsets: list        # per linear layer: its first float in `buf`
+    n_chunks: int        # ring chunks the kernel consumes
+    buf: Tensor          # the stream itself, as f32 words
+    mode: int            # how `gather` is applied: 0 one f32 per index (zk_gather_f32), 1 one block of three bf16 images per 512 indices
+                         # (zk_gather_split_bf16), 2 one block of two scaled f16 images per 512 indices (zk_gather_split_f16)
+    stamp: object = None  # the parameter stamp `buf` was last gathered for
+
+
 def chunk_of(variant: int = 0) -> int:
     """Tiles per chunk the stream is padded to (= AR_CH of csrc/fused_ar.hip: a 3 x 24-tile LDS ring)."""
     return CHUNK
@@ -481,6 +494,9 @@ def chunk_of(variant: int = 0) -> int:
 
 def default_variant() -> int:
     return 0  # reserved argument of the C ABI
+
+
+HALF, GSPLIT, STATIC, GENERIC = range(4)  # FusedAR._product(): the kernel that serves a launch
 
 
 class FusedAR:
@@ -501,32 +517,33 @@ class FusedAR:
         self.bias_floats = plan.bias_off[-1] + len(plan.bias_gather[-1])
         self.bias = torch.empty(self.bias_floats, dtype=torch.float32, device=device)
         self._stamp = None
-        self._fine_stamp = None
         self.generic_ok = plan.max_width <= MAX_WIDTH and plan.layout.kind <= 4  # (wider plans and the polynomial maps exist only as static-shape kernels)
         self.eps = 1e-6     # Bernstein continuation margin (zuko/transforms.py:594); set by the caller when the transform was built with another
         self._gl = None     # SOS quadrature: ctypes arrays of the Gauss-Legendre nodes / weights on [0, 1] (kept alive here)
         self.static = None          # (StaticKernel, rev) of zuko_amd/static_ar.py once one has been found / compiled
-        self._static_tried_rows = -1
-        self.fine_gather = self.fine_stream = self.fine_offsets = None
-        self.fine_n_chunks = 0
+        self._static_tried_rows = self._half_tried_rows = -1
+        self.fine = None            # WeightStream of self.static
         # the two-part (f16 x 2) twin of an operand-split kernel: inference launches when the weights allow it (set_matmul_precision)
         self.half = None            # StaticKernel
-        self.half_gather = self.half_stream = self.half_offsets = None
-        self.half_n_chunks = 0
-        self.half_ok = False        # the weights of _half_stamp are eligible and their stream is built
+        self.half_stream = None     # its WeightStream
+        self.half_ok = False        # the weights of half_stream.stamp are eligible and their stream is built
         self.half_descale = None    # per linear layer 2^-e
-        self._half_stamp = None
         self._acquire_static(None)  # kernels already on disk (prebuilt or compiled earlier) are used whatever the batch size
         # the generic operand-split kernel (csrc/fused_ar_gsplit.hip): what run() launches while there is no static-shape kernel for the plan
         # (its tables are built on first use).  ZUKO_AMD_GSPLIT=0: keep such plans on the f32 matrix instruction; =force: even when there is one
         self.gs_mode = os.environ.get("ZUKO_AMD_GSPLIT", "1")  # (read when the state object is made — once per transform and device; zuko_amd.invalidate(module) re-reads it)
-        self.gs = None              # (gathers on the device, offsets, n_chunks, stream) | False: the plan has no generic split kernel
-        self._gs_stamp = self._seen_stamp = None
+        self.gs = None              # its WeightStream | False: the plan has no generic split kernel
+        self._seen_stamp = None
 
     @property
     def static_variant(self) -> int:
         """0: generic kernel; 1 / 2: a static-shape kernel with its primary / alternative first-layer pattern."""
         return 0 if self.static is None else 1 + self.static[1]
+
+    @property
+    def _gs_stamp(self):
+        """The parameter stamp the generic operand-split kernel's stream was last gathered for; None while it has not been built."""
+        return self.gs.stamp if self.gs else None
 
     def _acquire_static(self, rows) -> None:
         """Look the plan's static-shape kernel up (zuko_amd/static_ar.py); `rows` >= the JIT threshold allows compiling it."""
@@ -543,36 +560,32 @@ class FusedAR:
         if found is not None and (self.static is None or found[0] is not self.static[0]):
             self.static = found
             if found[0].meta.get("split"):
-                t, gathers = static_ar.split_tables(self.plan, self.plan.layout.kind, self.act)
-                self.fine_gather = [torch.from_numpy(g).to(self.device) for g in gathers]
-                self.fine_offsets = [b * 256 for b in t["BASE"]] + [t["LAST_BASE"] * 256]
-                self.fine_n_chunks = t["NCHUNK"]
-                stream_images = t["STREAM_IMAGES"]
+                self.fine = self._table_stream(static_ar.split_tables(self.plan, self.plan.layout.kind, self.act), 1)
             else:
-                self.fine_gather = [torch.from_numpy(g).to(self.device) for g in self.plan.fine_gather]
-                self.fine_offsets = [b * 256 for b in self.plan.fine_layer_block0]
-                self.fine_n_chunks = self.plan.fine_n_chunks
-                stream_images = self.fine_n_chunks * 24
-            self.fine_stream = torch.zeros(stream_images * 256, dtype=torch.float32, device=self.device)
-            self._fine_stamp = None
+                p = self.plan
+                self.fine = self._weight_stream(p.fine_gather, [b * 256 for b in p.fine_layer_block0], p.fine_n_chunks, p.fine_n_chunks * 24 * 256, 0)
+
+    def _weight_stream(self, gathers, offsets, n_chunks: int, floats: int, mode: int) -> WeightStream:
+        """A stream of `floats` zeros with its gather indices on the device; refresh() fills it."""
+        return WeightStream([torch.from_numpy(g).to(self.device) for g in gathers], offsets, n_chunks, torch.zeros(floats, dtype=torch.float32, device=self.device), mode)
+
+    def _table_stream(self, tg, mode: int) -> WeightStream:
+        """The stream of a generated operand-split kernel, from (tables, gathers) of static_ar.split_tables / half_tables (1 KiB images)."""
+        t, gathers = tg
+        return self._weight_stream(gathers, [b * 256 for b in t["BASE"]] + [t["LAST_BASE"] * 256], t["NCHUNK"], t["STREAM_IMAGES"] * 256, mode)
 
     def _acquire_half(self, rows) -> None:
         """The plan's two-part kernel (zuko_amd/static_ar.py: lookup_half), looked up once per batch size class like the static kernel."""
         from . import static_ar
 
-        if self.half is not None or self.plan.fine_gather is None or not static_ar.half_enabled() or (rows is not None and rows <= getattr(self, "_half_tried_rows", -1)):
+        if self.half is not None or self.plan.fine_gather is None or not static_ar.half_enabled() or (rows is not None and rows <= self._half_tried_rows):
             return
         if rows is not None:
             self._half_tried_rows = rows if rows < static_ar.jit_min_rows() else 1 << 62
         kern = static_ar.lookup_half(self.plan, self.plan.layout.kind, self.act, rows)
         if kern is not None:
-            t, gathers = static_ar.half_tables(self.plan, self.plan.layout.kind, self.act)
             self.half = kern
-            self.half_gather = [torch.from_numpy(g).to(self.device) for g in gathers]
-            self.half_offsets = [b * 256 for b in t["BASE"]] + [t["LAST_BASE"] * 256]
-            self.half_n_chunks = t["NCHUNK"]
-            self.half_stream = torch.zeros(t["STREAM_IMAGES"] * 256, dtype=torch.float32, device=self.device)
-            self._half_stamp = None
+            self.half_stream = self._table_stream(static_ar.half_tables(self.plan, self.plan.layout.kind, self.act), 2)
 
     def _refresh_half(self, linears, stamp) -> None:
         """(Re)build the two-part kernel's stream for the current weights: eligibility + per-layer scales (one synchronisation), then one gather per layer."""
@@ -580,7 +593,8 @@ class FusedAR:
         from .ops import _ptr, _stream
 
         scales = half_scales(linears)
-        self._half_stamp = stamp
+        ws = self.half_stream
+        ws.stamp = stamp
         self.half_ok = all(ok for ok, _ in scales)
         if not self.half_ok:
             return
@@ -589,25 +603,30 @@ class FusedAR:
             w = m.weight.detach()
             if not w.is_contiguous():
                 w = w.contiguous()
-            nb = self.half_gather[l].numel() // 512
+            nb = ws.gather[l].numel() // 512
             if nb:
-                _C.check(_C.lib().zk_gather_split_f16(_ptr(w), _ptr(m.mask.contiguous().view(torch.uint8)), _ptr(self.half_gather[l]), nb, _ptr(self.half_stream[self.half_offsets[l] :]), 2.0 ** e,
-                                                      _stream()), "zk_gather_split_f16")
+                _C.check(_C.lib().zk_gather_split_f16(_ptr(w), _ptr(m.mask.contiguous().view(torch.uint8)), _ptr(ws.gather[l]), nb, _ptr(ws.buf[ws.offsets[l] :]), 2.0 ** e, _stream()),
+                         "zk_gather_split_f16")
 
-    def _half_args(self, **io):
-        p = self.plan
+    def static_args(self, launcher, rev: int, ws: WeightStream, **io):
+        """The argument block of a generated kernel (include/zuko_amd.h: zk_ar_args_v1): its launcher and stream, the plan's tables + `io`."""
         from . import _C
         from .ops import _ptr
 
+        p = self.plan
+        fields = dict(launcher=launcher, rev=rev, uni_kind=p.layout.kind, D=p.features, wstream=_ptr(ws.buf), bias=_ptr(self.bias), bias_floats=self.bias_floats, featmap=_ptr(self.featmap),
+                      n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=ws.n_chunks, act=self.act, bound=self.bound, slope=self.slope)
+        fields.update(io)  # (the training launches set `bound` / `slope` themselves)
+        return _C.args("zk_ar_args_v1", **fields)
+
+    def _half_args(self, **io):
         d = list(self.half_descale) + [1.0] * (4 - len(self.half_descale))
-        return _C.args("zk_ar_args_v1", launcher=self.half.launcher, rev=0, uni_kind=p.layout.kind, D=p.features, wstream=_ptr(self.half_stream), bias=_ptr(self.bias),
-                       bias_floats=self.bias_floats, featmap=_ptr(self.featmap), n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=self.half_n_chunks, act=self.act,
-                       bound=self.bound, slope=self.slope, wdescale0=d[0], wdescale1=d[1], wdescale2=d[2], wdescale3=d[3], **io)
+        return self.static_args(self.half.launcher, 0, self.half_stream, wdescale0=d[0], wdescale1=d[1], wdescale2=d[2], wdescale3=d[3], **io)
 
     def _half_serves(self, y: Tensor | None) -> bool:
         """Whether this inference launch goes to the two-part kernel: one is held, the mode allows it, the current weights are eligible and gathered.
         (y None: a terminal launch, which writes no rows.)"""
-        return (self.half is not None and self.half_ok and self._half_stamp is not None and self._half_stamp == self._seen_stamp and matmul_precision() == "f16x2"
+        return (self.half is not None and self.half_ok and self.half_stream.stamp is not None and self.half_stream.stamp == self._seen_stamp and matmul_precision() == "f16x2"
                 and self.gs_mode != "force" and (y is None or not self.half.meta["XLDS"] or (y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0)))
 
     def serves_terminal(self) -> bool:
@@ -616,12 +635,28 @@ class FusedAR:
         p = self.plan
         if p.n_groups * 4 * p.layout.fpl + 3 * p.features > 1024:
             return False
-        if self._half_serves(None):
-            return True
+        which = self._product(None)
+        return which == HALF or (which == STATIC and bool(self.static[0].meta.get("split")) and p.layout.kind not in (5, 6))
+
+    def _product(self, y: Tensor | None) -> int:
+        """The kernel that serves run(inp, y, ...), after refresh(): HALF (two-part), GSPLIT (generic operand-split), STATIC (generated) or GENERIC
+        (the generic kernel on the f32 matrix instruction; where the plan has none — not generic_ok — nothing serves the launch).  y None: a terminal
+        launch, which writes no rows — only HALF and STATIC have an instantiation for it (serves_terminal)."""
+        p = self.plan
+        if self._half_serves(y):
+            return HALF
+        aligned = y is None or (y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0)  # (rows staged through LDS are written 16 bytes at a time)
         gs = self._gsplit()
-        if gs is not None and self._gs_stamp is not None and self._gs_stamp == self._seen_stamp:
-            return False  # (run() would take the generic operand-split kernel)
-        return self.static is not None and bool(self.static[0].meta.get("split")) and p.layout.kind not in (5, 6)
+        if gs is not None and gs.stamp is not None and gs.stamp == self._seen_stamp:
+            # (4 / 16 bins and the circular map exist for the LDS-staged epilogue only, like the generic f32 kernel's)
+            if p.layout.kind <= 1 or (p.features % 4 == 0 and aligned):
+                return GSPLIT
+            if y is None:
+                return GENERIC  # kept from serves_terminal(): no terminal launch while this stream is current, though a launch that writes rows goes on to STATIC here
+        # (a static-shape kernel that stages rows through LDS needs them 16-byte addressable; the generic kernel has an instantiation for the other case)
+        if self.static is not None and (not self.static[0].meta["XLDS"] or aligned):
+            return STATIC
+        return GENERIC
 
     def ready(self, rows: int) -> bool:
         """Whether run() can be served: always for plans the generic kernel covers; for wider ones only with a static-shape kernel
@@ -643,8 +678,7 @@ class FusedAR:
                 self.gs = False
             else:
                 gathers, offsets, n_chunks = t
-                self.gs = ([torch.from_numpy(g).to(self.device) for g in gathers], offsets, n_chunks,
-                           torch.zeros(n_chunks * GS_BLOCKS_PER_CHUNK * 768, dtype=torch.float32, device=self.device))
+                self.gs = self._weight_stream(gathers, offsets, n_chunks, n_chunks * GS_BLOCKS_PER_CHUNK * 768, 1)
         return self.gs or None
 
     def refresh(self, linears, fine_only: bool = False) -> None:
@@ -659,10 +693,10 @@ class FusedAR:
         stamp = _param_stamp(linears)
         self._seen_stamp = stamp
         want_generic = self.generic_ok and not (fine_only and self.static is not None) and stamp != self._stamp
-        want_fine = self.static is not None and stamp != self._fine_stamp
+        want_fine = self.static is not None and stamp != self.fine.stamp
         gs = self._gsplit()
-        want_gs = gs is not None and stamp != self._gs_stamp
-        if self.half is not None and not fine_only and stamp != self._half_stamp and matmul_precision() == "f16x2":
+        want_gs = gs is not None and stamp != gs.stamp
+        if self.half is not None and not fine_only and stamp != self.half_stream.stamp and matmul_precision() == "f16x2":
             self._refresh_half(linears, stamp)
         if not (want_generic or want_fine or want_gs):
             return
@@ -674,14 +708,8 @@ class FusedAR:
             mask = m.mask.contiguous().view(torch.uint8)
             if want_generic:
                 items.append((w, mask, self.gather[l], self.gather[l].numel(), self.stream[self.plan.layer_block0[l] * 256 :], 0))
-            if want_fine:
-                fdst = self.fine_stream[self.fine_offsets[l] :]
-                if self.static[0].meta.get("split"):
-                    items.append((w, mask, self.fine_gather[l], self.fine_gather[l].numel() // 512, fdst, 1))
-                else:
-                    items.append((w, mask, self.fine_gather[l], self.fine_gather[l].numel(), fdst, 0))
-            if want_gs and gs[0][l].numel():
-                items.append((w, mask, gs[0][l], gs[0][l].numel() // 512, gs[3][gs[1][l] :], 1))
+            for ws in ((self.fine,) if want_fine else ()) + ((gs,) if want_gs else ()):
+                items.append((w, mask, ws.gather[l], ws.gather[l].numel() // (512 if ws.mode else 1), ws.buf[ws.offsets[l] :], ws.mode))
             nb = self.bias_gather[l].numel()
             bdst = self.bias[self.plan.bias_off[l] :]
             if m.bias is None:
@@ -692,9 +720,9 @@ class FusedAR:
         if want_generic:
             self._stamp = stamp
         if want_fine:
-            self._fine_stamp = stamp
+            self.fine.stamp = stamp
         if want_gs:
-            self._gs_stamp = stamp
+            gs.stamp = stamp
 
     def run(self, inp: Tensor, y: Tensor | None, ladj: Tensor | None, accumulate: bool, base=None) -> None:
         """inp [N, DINP] (cat(x, c), zero-padded to a multiple of 4 columns), y [N, D], ladj [N].
@@ -704,54 +732,35 @@ class FusedAR:
         from .ops import _ptr, _stream
 
         p = self.plan
-        N = inp.shape[0]
+        io = dict(N=inp.shape[0], DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate))
         if base is not None:
             if y is not None or ladj is None or not self.serves_terminal():
                 raise RuntimeError("zuko_amd: terminal launch requested of a conditioner without an operand-split static-shape kernel (FusedAR.serves_terminal() was not consulted)")
-            io = dict(N=N, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate), base_loc=_ptr(base[0]), base_scale=_ptr(base[1]))
-            if self._half_serves(None):
-                a = self._half_args(**io)
-            else:
-                kern, rev = self.static
-                a = _C.args("zk_ar_args_v1", launcher=kern.launcher, rev=rev, uni_kind=p.layout.kind, D=p.features, wstream=_ptr(self.fine_stream), bias=_ptr(self.bias),
-                            bias_floats=self.bias_floats, featmap=_ptr(self.featmap), n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=self.fine_n_chunks, act=self.act,
-                            bound=self.bound, slope=self.slope, **io)
-            _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
-            return
-        if self._half_serves(y):
-            a = self._half_args(N=N, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate))
-            _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
-            return
-        gs = self._gsplit()
-        if gs is not None and self._gs_stamp is not None and self._gs_stamp == self._seen_stamp and (p.layout.kind <= 1 or (p.features % 4 == 0 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0)):
-            # (4 / 16 bins and the circular map exist for the LDS-staged epilogue only, like the generic f32 kernel's)
-            a = self._generic_args(N=N, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate))
-            a.wstream, a.n_chunks = gs[3].data_ptr(), gs[2]
+            io.update(base_loc=_ptr(base[0]), base_scale=_ptr(base[1]))
+        else:
+            io.update(y=_ptr(y), ldy=y.stride(0))
+        which = self._product(y)
+        if which == HALF:
+            _C.check(_C.lib().zk_ar_forward_static(self._half_args(**io), _stream()), "zk_ar_forward_static")
+        elif which == GSPLIT:
+            a = self._generic_args(**io)
+            a.wstream, a.n_chunks = self.gs.buf.data_ptr(), self.gs.n_chunks
             _C.check(_C.lib().zk_ar_forward_split(a, _stream()), "zk_ar_forward_split")
-            return
-        if self.static is not None:
+        elif which == STATIC:
             kern, rev = self.static
-            # (a static-shape kernel that stages rows through LDS needs them 16-byte addressable; the generic kernel has an instantiation for the other case)
-            if not kern.meta["XLDS"] or (y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0):
-                extra = {}
-                if p.layout.kind == 5:
-                    if self._gl is None:
-                        from .ops import _leggauss01
+            if p.layout.kind == 5:
+                if self._gl is None:
+                    from .ops import _leggauss01
 
-                        self._gl = _leggauss01(5)
-                    extra = dict(gl_nodes01=ctypes.cast(self._gl[0], ctypes.c_void_p), gl_weights01=ctypes.cast(self._gl[1], ctypes.c_void_p))
-                elif p.layout.kind == 6:
-                    extra = dict(eps=float(self.eps))
-                a = _C.args("zk_ar_args_v1", launcher=kern.launcher, rev=rev, uni_kind=p.layout.kind, N=N, D=p.features, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0),
-                            y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate), wstream=_ptr(self.fine_stream), bias=_ptr(self.bias),
-                            bias_floats=self.bias_floats, featmap=_ptr(self.featmap), n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=self.fine_n_chunks, act=self.act,
-                            bound=self.bound, slope=self.slope, **extra)
-                _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
-                return
-        if not self.generic_ok:
+                    self._gl = _leggauss01(5)
+                io.update(gl_nodes01=ctypes.cast(self._gl[0], ctypes.c_void_p), gl_weights01=ctypes.cast(self._gl[1], ctypes.c_void_p))
+            elif p.layout.kind == 6:
+                io.update(eps=float(self.eps))
+            _C.check(_C.lib().zk_ar_forward_static(self.static_args(kern.launcher, rev, self.fine, **io), _stream()), "zk_ar_forward_static")
+        elif not self.generic_ok:
             raise RuntimeError("zuko_amd: this conditioner is wider than the generic fused kernel covers and has no static-shape kernel (FusedAR.ready() was not consulted)")
-        a = self._generic_args(N=N, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=int(accumulate))
-        _C.check(_C.lib().zk_ar_forward(a, _stream()), "zk_ar_forward")
+        else:
+            _C.check(_C.lib().zk_ar_forward(self._generic_args(**io), _stream()), "zk_ar_forward")
 
     def _generic_args(self, **io):
         """The argument block of the generic kernel's entry points (include/zuko_amd.h: zk_ar_args_v1): the plan's tables + `io`."""
@@ -768,29 +777,23 @@ class FusedAR:
         from .ops import _ptr, _stream
 
         p = self.plan
-        if self._half_serves(y) and p.layout.kind in (1, 2, 3) and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0:
+        which = self._product(y)
+        aligned = y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0  # (every operand-split kernel's diagnostic instantiation stages its rows through LDS)
+        io = dict(N=inp.shape[0], DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), bin_out=_ptr(bins), knots_out=_ptr(knots))
+        if which == HALF and p.layout.kind in (1, 2, 3) and aligned:
             # the product launch is the two-part kernel: ITS diagnostic instantiation
-            a = self._half_args(N=inp.shape[0], DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=0, bin_out=_ptr(bins), knots_out=_ptr(knots))
-            _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
-            return
-        if self.static is not None and self.static[0].meta.get("split") and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0:
+            _C.check(_C.lib().zk_ar_forward_static(self._half_args(accumulate=0, **io), _stream()), "zk_ar_forward_static")
+        elif self.static is not None and self.static[0].meta.get("split") and aligned:
             # the product launch is an operand-split kernel: its own diagnostic instantiation (the generic kernel differs from it by rounding)
             kern, rev = self.static
-            a = _C.args("zk_ar_args_v1", launcher=kern.launcher, rev=rev, uni_kind=p.layout.kind, N=inp.shape[0], D=p.features, DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0),
-                        y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), accumulate=0, wstream=_ptr(self.fine_stream), bias=_ptr(self.bias), bias_floats=self.bias_floats,
-                        featmap=_ptr(self.featmap), n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=self.fine_n_chunks, act=self.act, bound=self.bound, slope=self.slope,
-                        bin_out=_ptr(bins), knots_out=_ptr(knots))
-            _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static")
-            return
-        a = self._generic_args(N=inp.shape[0], DIN=inp.shape[1], x=_ptr(inp), ldx=inp.stride(0), y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), bin_out=_ptr(bins), knots_out=_ptr(knots))
-        gs = self._gsplit()
-        if gs is not None and self._gs_stamp is not None and self._gs_stamp == self._seen_stamp and p.features % 4 == 0 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0:
+            _C.check(_C.lib().zk_ar_forward_static(self.static_args(kern.launcher, rev, self.fine, accumulate=0, **io), _stream()), "zk_ar_forward_static")
+        elif which == GSPLIT and p.features % 4 == 0 and aligned:
             # the product launch is the generic operand-split kernel: ITS diagnostic instantiation
-            a.wstream, a.n_chunks = gs[3].data_ptr(), gs[2]
+            a = self._generic_args(**io)
+            a.wstream, a.n_chunks = self.gs.buf.data_ptr(), self.gs.n_chunks
             _C.check(_C.lib().zk_ar_forward_split(a, _stream()), "zk_ar_forward_split")
-            return
-        err = _C.lib().zk_ar_forward_diag(a, _stream())
-        _C.check(err, "zk_ar_forward_diag")
+        else:
+            _C.check(_C.lib().zk_ar_forward_diag(self._generic_args(**io), _stream()), "zk_ar_forward_diag")
 
     def run_inverse_sweep(self, buf: Tensor, y: Tensor) -> None:
         """One sweep x <- f^{-1}(y | x) in place: buf [N, DINP] holds cat(x, c, 0-pad), y [N, D]."""

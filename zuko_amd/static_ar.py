@@ -13,6 +13,15 @@ address to the library (zk_ar_forward_static).
   (ZUKO_AMD_JIT_MIN_ROWS, default 2^15 rows in one call or 8 x that in total over the calls; ZUKO_AMD_JIT=0 disables it).  Without hipcc, or below the threshold, the generic
   tile-skipping kernel (widths <= 256) or the layer-wise kernels (wider) run instead — same results.
 
+The generated families, each one record (`Family`: header, Shape fields, entry point, signature, index key, meta) served by one emitter
+(`emit`), one compile function (`compile_unit`), one find-or-compile routine (`find_or_compile`) and one loader (`StaticKernel`):
+
+* `ars`   the forward kernel on the f32 matrix instruction (csrc/fused_ar_static_impl.h), also the conditioner-only training forward;
+* `arx`   its operand-split twin, three bf16 parts per operand (csrc/fused_ar_split_impl.h): inference and training forward;
+* `arh`   the two-part twin of that, two f16 parts per operand (csrc/fused_ar_half_impl.h): inference launches only;
+* `arsd`  the backward kernels, in three shapes: the dgrad chain on the f32 instruction, the operand-split chain over every layer, and the
+          whole backward of the transform in one launch (tables with "chain" == 1, 2, 3).
+
 The kernels are bit-identical to the generic kernel on the same plan (tests/test_gpu_flows.py), so none of this changes a
 number; it removes the run-time tile tests, makes every LDS wait partial and lifts the generic kernel's width limit of 256
 (one wavefront per SIMD, 32 + 32 activation tiles, for widths up to 512).
@@ -21,6 +30,7 @@ number; it removes the run-time tile tests, makes every LDS wait partial and lif
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import fcntl
 import hashlib
 import json
@@ -85,6 +95,12 @@ def _warn_once(key: str, msg: str) -> None:
         sys.stderr.write(f"[zuko_amd static_ar] {msg}\n")
 
 
+def hipcc_flags() -> list:
+    """The flags every generated unit is compiled with, without those that say what to produce (_build_so: a shared object; the ISA guards of
+    tests/test_codegen*.py: device assembly)."""
+    return ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={_arch()}", "-Wno-unused-result", "-Wno-uninitialized", "-ffp-contract=off", f"-I{CSRC}"]
+
+
 def _build_so(stem: str, source, meta: dict | None, verbose: bool, out_dir: str | None = None) -> str | None:
     """Compile the one-kernel translation unit `source()` into <dir>/<stem>.so (+ <stem>.json when `meta` is given); a no-op when it
     is there.  Returns the .so path, or None when there is no hipcc, the compile fails, or the directory cannot be written (read-only
@@ -111,7 +127,7 @@ def _build_so(stem: str, source, meta: dict | None, verbose: bool, out_dir: str 
             with open(src, "w") as f:
                 f.write(source())
             tmp = os.path.join(d, f".{stem}.so.{os.getpid()}")
-            cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", f"--offload-arch={_arch()}", "-Wno-unused-result", "-Wno-uninitialized", "-ffp-contract=off", f"-I{CSRC}", "-shared", "-no-hip-rt",
+            cmd = [hipcc, *hipcc_flags(), "-shared", "-no-hip-rt",
                    *os.environ.get("ZUKO_AMD_STATIC_CXXFLAGS", "").split(),  # (probe / ablation builds into a ZUKO_AMD_CACHE_DIR of their own: NOT part of the kernel's signature)
                    src, f"-L{_torch_lib_dir()}", "-l:libamdhip64.so", "-o", tmp]
             if verbose:
@@ -374,82 +390,9 @@ def half_tables(plan, uni_kind: int, act: int = 1):
     return out, g
 
 
-def emit_half(t: dict) -> str:
-    boff = [0]
-    for n in t["NB"]:
-        boff.append(boff[-1] + n)
-    lines = [
-        "// generated by zuko_amd/static_ar.py — do not edit",
-        '#include "fused_ar_half_impl.h"',
-        "namespace {",
-        "struct Shape {",
-        f"  static constexpr int D = {t['D']}, DIN = {t['DIN']}, NIT = {t['NIT']}, NH = {t['NH']}, TMAX = {t['TMAX']}, NG = {t['NG']}, NCHUNK = {t['NCHUNK']};",
-        f"  static constexpr int BIAS_STRIDE = {t['BIAS_STRIDE']}, LAST_BASE = {t['LAST_BASE']}, WAVES = {t['WAVES']}, CH = {t['CH']}, NR = {t['NR']}, ACT = {t['ACT']}, OCC = {t['OCC']};",
-        f"  static constexpr bool XLDS = {'true' if t['XLDS'] else 'false'};",
-        _arr("HT", "int", t["HT"]), _arr("NB", "int", t["NB"]), _arr("BOFF", "int", boff), _arr("BASE", "int", t["BASE"]),
-        _arr("B_OT", "unsigned char", t["B_OT"]), _arr("B_IP", "unsigned char", t["B_IP"]), _arr("GOFF", "int", t["GOFF"]), _arr("G_IP", "unsigned char", t["G_IP"]),
-        "};",
-        "}  // namespace",
-        f'extern "C" int zk_ars_launch(const zk::ArArgs* a, int abi, int args_bytes, int train, void* stream) {{ return zk::arh_launch<Shape, {UNI_TYPES[t["uni"]]}>(a, abi, args_bytes, train, stream); }}',
-        "",
-    ]
-    return "\n".join(lines)
-
-
-def compile_half(t: dict, verbose: bool = False, out_dir: str | None = None) -> dict | None:
-    """Build arh_<sig>.so, the two-part operand-split kernel of tables `t` (half_tables); returns its meta or None."""
-    stamp = _half_digest()
-    sig = _digest({"half": t, "headers": stamp})
-    meta = {"so": f"arh_{sig}.so", "core": "h" + _digest(t), "half": 1, "split": 2, "l0": [], "alt": None, "headers": stamp, "uni": t["uni"], "ACT": t["ACT"], "D": t["D"], "DIN": t["DIN"], "HT": t["HT"],
-            "WAVES": t["WAVES"], "CH": t["CH"], "TRAIN_OK": 0, "XLDS": t["XLDS"], "NCHUNK": t["NCHUNK"]}
-    so = _build_so(f"arh_{sig}", lambda: emit_half(t), meta, verbose, out_dir)
-    if so is None:
-        return None
-    global _INDEX
-    _INDEX = None
-    return dict(meta, dir=os.path.dirname(so))
-
-
-def lookup_half(plan, uni_kind: int, act: int, rows: int | None = None):
-    """The two-part kernel (StaticKernel) for this plan, or None: found on disk, or compiled when `rows` reaches the JIT threshold."""
-    if os.environ.get("ZUKO_AMD_NO_STATIC_AR", "0") == "1" or not split_enabled():
-        return None
-    ts = half_tables(plan, uni_kind, act)
-    if ts is None:
-        return None
-    cdx = "h" + _digest(ts[0])
-    with _LOCK:
-        idx = _INDEX if _INDEX is not None else _scan()
-        for meta in idx.get(cdx, []):
-            return _load(meta)
-    if rows is not None and rows >= jit_min_rows() and jit_enabled():
-        meta = compile_half(ts[0], verbose=os.environ.get("ZUKO_AMD_JIT_VERBOSE", "0") == "1")
-        if meta is not None:
-            with _LOCK:
-                return _load(meta)
-    return None
-
-
-def emit_split(t: dict) -> str:
-    boff = [0]
-    for n in t["NB"]:
-        boff.append(boff[-1] + n)
-    lines = [
-        "// generated by zuko_amd/static_ar.py — do not edit",
-        '#include "fused_ar_split_impl.h"',
-        "namespace {",
-        "struct Shape {",
-        f"  static constexpr int D = {t['D']}, DIN = {t['DIN']}, NIT = {t['NIT']}, NH = {t['NH']}, TMAX = {t['TMAX']}, NG = {t['NG']}, NCHUNK = {t['NCHUNK']};",
-        f"  static constexpr int BIAS_STRIDE = {t['BIAS_STRIDE']}, LAST_BASE = {t['LAST_BASE']}, WAVES = {t['WAVES']}, CH = {t['CH']}, NR = {t['NR']}, ACT = {t['ACT']}, OCC = {t['OCC']};",
-        f"  static constexpr bool XLDS = {'true' if t['XLDS'] else 'false'}, HAS_ALT = false, TRAIN_OK = {'true' if t['TRAIN_OK'] else 'false'};",
-        _arr("HT", "int", t["HT"]), _arr("NB", "int", t["NB"]), _arr("BOFF", "int", boff), _arr("BASE", "int", t["BASE"]),
-        _arr("B_OT", "unsigned char", t["B_OT"]), _arr("B_IP", "unsigned char", t["B_IP"]), _arr("GOFF", "int", t["GOFF"]), _arr("G_IP", "unsigned char", t["G_IP"]),
-        "};",
-        "}  // namespace",
-        f'extern "C" int zk_ars_launch(const zk::ArArgs* a, int abi, int args_bytes, int train, void* stream) {{ return zk::arx_launch<Shape, {UNI_TYPES[t["uni"]]}>(a, abi, args_bytes, train, stream); }}',
-        "",
-    ]
-    return "\n".join(lines)
+# --------------------------------------------------------------------------------------------------------------------
+# the generated families: what a translation unit looks like, how it is named, what its meta holds
+# --------------------------------------------------------------------------------------------------------------------
 
 
 def _split(t: dict):
@@ -469,43 +412,129 @@ def _arr(name: str, ctype: str, vals) -> str:
     return f"  static constexpr {ctype} {name}[{len(vals)}] = {{{', '.join(str(int(v)) for v in vals)}}};"
 
 
-def emit(t: dict, alt: list | None) -> str:
-    """C++ source of the translation unit for tables `t`; `alt`: the first layer's input tiles under the alternative order."""
-    n0 = t["NS"][0]
-    s_alt = (alt if alt is not None else t["S_IT"][:n0]) + t["S_IT"][n0:]
-    soff = [0]
-    for n in t["NS"]:
-        soff.append(soff[-1] + n)
-    lines = [
-        "// generated by zuko_amd/static_ar.py — do not edit",
-        '#include "fused_ar_static_impl.h"',
-        "namespace {",
-        "struct Shape {",
-        f"  static constexpr int D = {t['D']}, DIN = {t['DIN']}, NIT = {t['NIT']}, NH = {t['NH']}, TMAX = {t['TMAX']}, NG = {t['NG']}, NCHUNK = {t['NCHUNK']};",
-        f"  static constexpr int BIAS_STRIDE = {t['BIAS_STRIDE']}, LAST_BASE = {t['LAST_BASE']}, WAVES = {t['WAVES']}, ACT = {t['ACT']};",
-        f"  static constexpr bool XLDS = {'true' if t['XLDS'] else 'false'}, HAS_ALT = {'true' if alt is not None else 'false'}, TRAIN_OK = {'true' if t['TRAIN_OK'] else 'false'};",
-        _arr("HT", "int", t["HT"]), _arr("NS", "int", t["NS"]), _arr("SOFF", "int", soff), _arr("BASE", "int", t["BASE"]),
-        _arr("S_OTG", "unsigned char", t["S_OTG"]), _arr("S_IT", "unsigned char", t["S_IT"]), _arr("S_ALT", "unsigned char", s_alt),
-        _arr("S_MASK", "unsigned char", t["S_MASK"]), _arr("GOFF", "int", t["GOFF"]), _arr("G_IT", "unsigned char", t["G_IT"]),
+def _pick(t: dict, *names) -> dict:
+    return {n: t[n] for n in names}
+
+
+@dataclasses.dataclass(frozen=True)
+class Family:
+    """One family of generated kernels: everything emit / compile_unit / find_or_compile need to know about it."""
+
+    prefix: str          # of the file stem: <prefix>_<signature digest>
+    header: str          # the template the unit instantiates (csrc/)
+    stamp: object        # () -> digest of the headers the unit depends on: part of the signature, checked by _scan
+    shape: tuple         # the lines of `struct Shape`, in order: (C type, names) — "int" / "bool": one line of scalars, a name being a table field or
+                         # "NAME=literal"; "int[]" / "unsigned char[]": one array per name
+    prefix_sums: dict    # array -> the name of its prefix-sum companion, printed right after it
+    entry: str           # the extern "C" symbol ...
+    params: tuple        # ... and its parameters (C type, name), all forwarded to the launcher
+    launcher: str        # the launcher expression ({uni}: the univariate map's type)
+    sig: object          # (tables, alt) -> what the signature digest is taken of (next to the stamp)
+    index: object        # tables -> the key the unit's meta is indexed under (_scan, _found); None: found by file name
+    meta: object         # tables -> the family's own fields of the meta JSON
+
+
+_FORWARD = dict(entry="zk_ars_launch", params=(("const zk::ArArgs*", "a"), ("int", "abi"), ("int", "args_bytes"), ("int", "train"), ("void*", "stream")))
+_BACKWARD = dict(entry="zk_ars_dgrad_launch", params=(("const zk::ArArgs*", "a"), ("int", "abi"), ("int", "args_bytes"), ("void*", "stream")))
+
+# the f32-instruction forward kernel (csrc/fused_ar_static_impl.h).  Indexed by its core: one kernel serves both feature orders when they differ in
+# the first layer's input tiles only (`alt`, rev 1)
+ARS = Family(
+    prefix="ars", header="fused_ar_static_impl.h", stamp=_header_digest, **_FORWARD, launcher="zk::ars_launch<Shape, {uni}>",
+    shape=(("int", ("D", "DIN", "NIT", "NH", "TMAX", "NG", "NCHUNK")), ("int", ("BIAS_STRIDE", "LAST_BASE", "WAVES", "ACT")), ("bool", ("XLDS", "HAS_ALT", "TRAIN_OK")),
+           ("int[]", ("HT", "NS", "BASE")), ("unsigned char[]", ("S_OTG", "S_IT", "S_ALT", "S_MASK")), ("int[]", ("GOFF",)), ("unsigned char[]", ("G_IT",))),
+    prefix_sums={"NS": "SOFF"},
+    sig=lambda t, alt: {"core": _split(t)[0], "l0": _split(t)[1], "alt": alt},
+    index=lambda t: _digest(_split(t)[0]),
+    meta=lambda t: _pick(t, "uni", "ACT", "D", "DIN", "HT", "WAVES", "TRAIN_OK", "XLDS"),
+)
+# its operand-split twin, three bf16 parts per operand (csrc/fused_ar_split_impl.h: arx_kernel)
+ARX = Family(
+    prefix="arx", header="fused_ar_split_impl.h", stamp=_header_digest, **_FORWARD, launcher="zk::arx_launch<Shape, {uni}>",
+    shape=(("int", ("D", "DIN", "NIT", "NH", "TMAX", "NG", "NCHUNK")), ("int", ("BIAS_STRIDE", "LAST_BASE", "WAVES", "CH", "NR", "ACT", "OCC")),
+           ("bool", ("XLDS", "HAS_ALT=false", "TRAIN_OK")), ("int[]", ("HT", "NB", "BASE")), ("unsigned char[]", ("B_OT", "B_IP")), ("int[]", ("GOFF",)), ("unsigned char[]", ("G_IP",))),
+    prefix_sums={"NB": "BOFF"},
+    sig=lambda t, alt: {"split": t},
+    index=lambda t: "x" + _digest(t),
+    meta=lambda t: dict(_pick(t, "uni", "ACT", "D", "DIN", "HT", "WAVES", "CH", "TRAIN_OK", "XLDS", "NCHUNK"), split=1),
+)
+# the two-part twin of that, two f16 parts per operand, inference only (csrc/fused_ar_half_impl.h: arh_kernel); stamped by its own header too
+ARH = dataclasses.replace(
+    ARX, prefix="arh", header="fused_ar_half_impl.h", stamp=_half_digest, launcher="zk::arh_launch<Shape, {uni}>",
+    shape=ARX.shape[:2] + (("bool", ("XLDS",)),) + ARX.shape[3:],
+    sig=lambda t, alt: {"half": t},
+    index=lambda t: "h" + _digest(t),
+    meta=lambda t: dict(_pick(t, "uni", "ACT", "D", "DIN", "HT", "WAVES", "CH", "TRAIN_OK", "XLDS", "NCHUNK"), half=1, split=2),
+)
+# the backward kernels, in three shapes told apart by the tables' "chain" field (chain_tables: 1, chain_split_tables: 2 and 3).  Their signature
+# covers the whole tables, so they are found by file name
+ARSD_F32 = Family(  # dgrad through the hidden layers on the f32 instruction (csrc/fused_ar_static_impl.h: ars_dgrad_kernel)
+    prefix="arsd", header="fused_ar_static_impl.h", stamp=_header_digest, **_BACKWARD, launcher="zk::ars_dgrad_launch<Shape>",
+    shape=(("int", ("DIN", "DOUT", "NIT", "NH", "TMAX", "NCHUNK", "WAVES=8", "ACT=1")), ("bool", ("HAS_ALT=false",)), ("int[]", ("HT", "NS", "BASE")),
+           ("unsigned char[]", ("S_OTG", "S_IT", "S_ALT", "S_MASK"))),
+    prefix_sums={"NS": "SOFF"},
+    sig=lambda t, alt: {"t": t},
+    index=None,
+    meta=lambda t: _pick(t, "DIN", "DOUT", "HT"),
+)
+ARSD_SPLIT = dataclasses.replace(  # dgrad through every layer, operand-split (csrc/fused_ar_split_impl.h: arxd_kernel)
+    ARSD_F32, header="fused_ar_split_impl.h", launcher="zk::arxd_launch<Shape>",
+    shape=(("int", ("DIN0", "DOUT", "NH", "TMAX", "NCHUNK", "WAVES=8", "CH", "NP0", "ACT=1")), ("int[]", ("HT", "NB", "BASE")), ("unsigned char[]", ("P0", "B_OT", "B_IP"))),
+    prefix_sums={"NB": "BOFF"},
+    meta=lambda t: {"DIN": t["DIN0"], "DOUT": t["DOUT"], "HT": t["HT"]},
+)
+ARSD_FULL = dataclasses.replace(  # the whole backward of the transform in one launch (arxb_kernel)
+    ARSD_SPLIT, launcher="zk::arxb_launch<Shape, {uni}>", shape=ARSD_SPLIT.shape + (("int", ("NG",)), ("int[]", ("PB",))))
+FAMILIES = {"ars": ARS, "arx": ARX, "arh": ARH, "arsd": {1: ARSD_F32, 2: ARSD_SPLIT, 3: ARSD_FULL}}
+
+
+def emit(fam: Family, t: dict, alt: list | None = None) -> str:
+    """C++ source of the translation unit of family `fam` for tables `t`; `alt` (ARS): the first layer's input tiles under the alternative order."""
+    v = dict(t, HAS_ALT=alt is not None)
+    if "S_IT" in t:
+        n0 = t["NS"][0]
+        v["S_ALT"] = (alt if alt is not None else t["S_IT"][:n0]) + t["S_IT"][n0:]
+    lines = ["// generated by zuko_amd/static_ar.py — do not edit", f'#include "{fam.header}"', "namespace {", "struct Shape {"]
+    for ctype, names in fam.shape:
+        if ctype.endswith("[]"):
+            for name in names:
+                lines.append(_arr(name, ctype[:-2], v[name]))
+                if name in fam.prefix_sums:
+                    lines.append(_arr(fam.prefix_sums[name], "int", [sum(v[name][:i]) for i in range(len(v[name]) + 1)]))
+        else:
+            show = (lambda x: "true" if x else "false") if ctype == "bool" else str
+            lines.append(f"  static constexpr {ctype} " + ", ".join(n.replace("=", " = ") if "=" in n else f"{n} = {show(v[n])}" for n in names) + ";")
+    launcher = fam.launcher.format(uni=UNI_TYPES.get(t.get("uni")))
+    lines += [
         "};",
         "}  // namespace",
-        f'extern "C" int zk_ars_launch(const zk::ArArgs* a, int abi, int args_bytes, int train, void* stream) {{ return zk::ars_launch<Shape, {UNI_TYPES[t["uni"]]}>(a, abi, args_bytes, train, stream); }}',
+        f'extern "C" int {fam.entry}({", ".join(f"{c} {n}" for c, n in fam.params)}) {{ return {launcher}({", ".join(n for _, n in fam.params)}); }}',
         "",
     ]
     return "\n".join(lines)
 
 
+def _identity(fam: Family, t: dict, alt: list | None = None):
+    """(file stem, meta) of the unit `emit(fam, t, alt)`: the stem carries the digest of everything the unit is made from."""
+    stamp = fam.stamp()
+    ident = fam.sig(t, alt)
+    stem = f"{fam.prefix}_{_digest(dict(ident, headers=stamp))}"
+    meta = {"so": stem + ".so", "core": "chain" if fam.index is None else fam.index(t), "l0": ident.get("l0", []), "alt": alt, "headers": stamp, **fam.meta(t)}
+    return stem, meta
+
+
 # --------------------------------------------------------------------------------------------------------------------
-# compile / load
+# compile / find / load
 # --------------------------------------------------------------------------------------------------------------------
 
 
 class StaticKernel:
-    def __init__(self, so: str, meta: dict) -> None:
+    """A loaded generated kernel: `launcher` is the address of its entry point, handed to the library in the argument block."""
+
+    def __init__(self, so: str, meta: dict, entry: str) -> None:
         self.so, self.meta = so, meta
         self.cdll = ctypes.CDLL(so)
-        fn = self.cdll.zk_ars_launch
-        self.launcher = ctypes.cast(fn, ctypes.c_void_p)
+        self.launcher = ctypes.cast(getattr(self.cdll, entry), ctypes.c_void_p)
 
 
 _LOCK = threading.Lock()
@@ -516,7 +545,6 @@ _INDEX: dict | None = None  # core digest -> list of meta dicts found on disk
 def _scan() -> dict:
     global _INDEX
     idx: dict = {}
-    stamp = _header_digest()
     for d in _dirs():
         try:
             names = sorted(os.listdir(d)) if os.path.isdir(d) else []
@@ -543,14 +571,11 @@ def _torch_lib_dir() -> str:
     return os.path.join(os.path.dirname(spec.origin), "lib")
 
 
-def compile_kernel(t: dict, alt: list | None, verbose: bool = False, out_dir: str | None = None) -> dict | None:
-    """Build ars_<sig>.so for tables `t` (no-op when it is there and current); returns its meta or None (no hipcc / failure / read-only directory)."""
-    core, l0 = _split(t)
-    stamp = _header_digest()
-    sig = _digest({"core": core, "l0": l0, "alt": alt, "headers": stamp})
-    meta = {"so": f"ars_{sig}.so", "core": _digest(core), "l0": l0, "alt": alt, "headers": stamp, "uni": t["uni"], "ACT": t["ACT"], "D": t["D"], "DIN": t["DIN"], "HT": t["HT"], "WAVES": t["WAVES"],
-            "TRAIN_OK": t["TRAIN_OK"], "XLDS": t["XLDS"]}
-    so = _build_so(f"ars_{sig}", lambda: emit(t, alt), meta, verbose, out_dir)
+def compile_unit(fam: Family, t: dict, alt: list | None = None, verbose: bool = False, out_dir: str | None = None) -> dict | None:
+    """Build <stem>.so, the kernel of family `fam` for tables `t` (no-op when it is there and current); returns its meta or None (no hipcc /
+    failure / read-only directory)."""
+    stem, meta = _identity(fam, t, alt)
+    so = _build_so(stem, lambda: emit(fam, t, alt), meta, verbose, out_dir)
     if so is None:
         return None
     global _INDEX
@@ -558,26 +583,53 @@ def compile_kernel(t: dict, alt: list | None, verbose: bool = False, out_dir: st
     return dict(meta, dir=os.path.dirname(so))
 
 
-def compile_split(t: dict, verbose: bool = False, out_dir: str | None = None) -> dict | None:
-    """Build arx_<sig>.so, the operand-split kernel of tables `t` (split_tables); returns its meta or None."""
-    stamp = _header_digest()
-    sig = _digest({"split": t, "headers": stamp})
-    meta = {"so": f"arx_{sig}.so", "core": "x" + _digest(t), "split": 1, "l0": [], "alt": None, "headers": stamp, "uni": t["uni"], "ACT": t["ACT"], "D": t["D"], "DIN": t["DIN"], "HT": t["HT"],
-            "WAVES": t["WAVES"], "CH": t["CH"], "TRAIN_OK": t["TRAIN_OK"], "XLDS": t["XLDS"], "NCHUNK": t["NCHUNK"]}
-    so = _build_so(f"arx_{sig}", lambda: emit_split(t), meta, verbose, out_dir)
-    if so is None:
-        return None
-    global _INDEX
-    _INDEX = None
-    return dict(meta, dir=os.path.dirname(so))
-
-
-def _load(meta: dict) -> StaticKernel:
+def _load(meta: dict, entry: str = _FORWARD["entry"]) -> StaticKernel | None:
     k = _LOADED.get(meta["so"])
     if k is None:
-        k = StaticKernel(os.path.join(meta.get("dir", ARS_DIR), meta["so"]), meta)
+        so = os.path.join(meta.get("dir", ARS_DIR), meta["so"])
+        try:
+            k = StaticKernel(so, meta, entry)
+        except OSError as exc:
+            _warn_once("load:" + so, f"cannot load {so}: {exc}")
+            return None
         _LOADED[meta["so"]] = k
     return k
+
+
+def _found(fam: Family, t: dict, l0: list | None):
+    """(meta, rev) of a kernel on disk that serves tables `t`, or None.  l0 (ARS): the first layer's input tiles the kernel must have as its primary
+    (rev 0) or alternative (rev 1) pattern."""
+    if fam.index is None:
+        name = _identity(fam, t)[0] + ".so"
+        so = _LOADED[name].so if name in _LOADED else _find(name)
+        return None if so is None else ({"so": name, "dir": os.path.dirname(so)}, 0)
+    idx = _INDEX if _INDEX is not None else _scan()
+    for meta in idx.get(fam.index(t), []):
+        if l0 is None or meta["l0"] == l0:
+            return meta, 0
+        if meta["alt"] is not None and meta["alt"] == l0:
+            return meta, 1
+    return None
+
+
+def find_or_compile(fam: Family, t: dict, allow: bool, l0: list | None = None, verbose: bool = False, out_dir: str | None = None):
+    """(StaticKernel, rev) of family `fam` for tables `t`: found on disk, else compiled when `allow`; None otherwise.  (A compile runs OUTSIDE the
+    module lock — the per-kernel file lock serialises ranks / threads that want the same kernel — so that other threads' lookups do not wait
+    10-25 s behind it.)"""
+    with _LOCK:
+        found = _found(fam, t, l0)
+    if found is None and allow:
+        meta = compile_unit(fam, t, None, verbose, out_dir)
+        found = None if meta is None else (meta, 0)
+    if found is None:
+        return None
+    with _LOCK:
+        k = _load(found[0], fam.entry)
+    return None if k is None else (k, found[1])
+
+
+def _enabled() -> bool:
+    return os.environ.get("ZUKO_AMD_NO_STATIC_AR", "0") != "1"
 
 
 def jit_enabled() -> bool:
@@ -589,6 +641,14 @@ def jit_min_rows() -> int:
         return int(os.environ.get("ZUKO_AMD_JIT_MIN_ROWS", str(1 << 15)))
     except ValueError:
         return 1 << 15
+
+
+def _jit_allowed(rows: int | None) -> bool:
+    return rows is not None and rows >= jit_min_rows() and jit_enabled()
+
+
+def _jit_verbose() -> bool:
+    return os.environ.get("ZUKO_AMD_JIT_VERBOSE", "0") == "1"
 
 
 JIT_CUMULATIVE_FACTOR = 8
@@ -610,45 +670,29 @@ def effective_rows(holder, rows: int, count: bool = True) -> int:
 def lookup(plan, uni_kind: int, act: int, rows: int | None = None):
     """(StaticKernel, rev) for this plan, or None.  Kernels found on disk are used whatever the batch; a missing one is compiled
     when `rows` reaches the JIT threshold."""
-    if os.environ.get("ZUKO_AMD_NO_STATIC_AR", "0") == "1":
+    if not _enabled():
         return None
     t = tables(plan, uni_kind, act)
     if t is None:
         return None
-    allow = rows is not None and rows >= jit_min_rows() and jit_enabled()
-    verbose = os.environ.get("ZUKO_AMD_JIT_VERBOSE", "0") == "1"
-    # (a compile runs OUTSIDE the module lock — the per-kernel file lock serialises ranks / threads that want the same kernel — so that
-    #  other threads' lookups do not wait 10-25 s behind it)
+    allow = _jit_allowed(rows)
     if split_enabled():  # the operand-split kernel (6/16 of the f32 matrix time) when there is one or one may be built
         ts = split_tables(plan, uni_kind, act)
-        if ts is not None:
-            cdx = "x" + _digest(ts[0])
-            with _LOCK:
-                idx = _INDEX if _INDEX is not None else _scan()
-                for meta in idx.get(cdx, []):
-                    return _load(meta), 0
-            if allow:
-                meta = compile_split(ts[0], verbose=verbose)
-                if meta is not None:
-                    with _LOCK:
-                        return _load(meta), 0
+        found = None if ts is None else find_or_compile(ARX, ts[0], allow, verbose=_jit_verbose())
+        if found is not None:
+            return found
     if uni_kind in SPLIT_ONLY_KINDS:
         return None
-    core, l0 = _split(t)
-    cd = _digest(core)
-    with _LOCK:
-        idx = _INDEX if _INDEX is not None else _scan()
-        for meta in idx.get(cd, []):
-            if meta["l0"] == l0:
-                return _load(meta), 0
-            if meta["alt"] is not None and meta["alt"] == l0:
-                return _load(meta), 1
-    if allow:
-        meta = compile_kernel(t, None, verbose=verbose)
-        if meta is not None:
-            with _LOCK:
-                return _load(meta), 0
-    return None
+    return find_or_compile(ARS, t, allow, l0=_split(t)[1], verbose=_jit_verbose())
+
+
+def lookup_half(plan, uni_kind: int, act: int, rows: int | None = None):
+    """The two-part kernel (StaticKernel) for this plan, or None: found on disk, or compiled when `rows` reaches the JIT threshold."""
+    if not _enabled() or not half_enabled():
+        return None
+    ts = half_tables(plan, uni_kind, act)
+    found = None if ts is None else find_or_compile(ARH, ts[0], _jit_allowed(rows), verbose=_jit_verbose())
+    return None if found is None else found[0]
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -798,89 +842,10 @@ def chain_split_tables(masks_sorted: list, rows: list, cols: list, packed: dict 
     return t, [np.stack(b).astype(np.int32).reshape(-1) for b in blocks_of]
 
 
-def emit_chain_split(t: dict) -> str:
-    boff = [0]
-    for nb in t["NB"]:
-        boff.append(boff[-1] + nb)
-    lines = [
-        "// generated by zuko_amd/static_ar.py — do not edit",
-        '#include "fused_ar_split_impl.h"',
-        "namespace {",
-        "struct Shape {",
-        f"  static constexpr int DIN0 = {t['DIN0']}, DOUT = {t['DOUT']}, NH = {t['NH']}, TMAX = {t['TMAX']}, NCHUNK = {t['NCHUNK']}, WAVES = 8, CH = {t['CH']}, NP0 = {t['NP0']}, ACT = 1;",
-        _arr("HT", "int", t["HT"]), _arr("NB", "int", t["NB"]), _arr("BOFF", "int", boff), _arr("BASE", "int", t["BASE"]), _arr("P0", "unsigned char", t["P0"]),
-        _arr("B_OT", "unsigned char", t["B_OT"]), _arr("B_IP", "unsigned char", t["B_IP"]),
-    ]
-    if t.get("chain") == 3:  # the whole backward of the transform (arxb_kernel)
-        lines += [f"  static constexpr int NG = {t['NG']};", _arr("PB", "int", t["PB"])]
-        launch = f"zk::arxb_launch<Shape, {UNI_TYPES[t['uni']]}>"
-    else:
-        launch = "zk::arxd_launch<Shape>"
-    lines += [
-        "};",
-        "}  // namespace",
-        f'extern "C" int zk_ars_dgrad_launch(const zk::ArArgs* a, int abi, int args_bytes, void* stream) {{ return {launch}(a, abi, args_bytes, stream); }}',
-        "",
-    ]
-    return "\n".join(lines)
-
-
-def emit_chain(t: dict) -> str:
-    soff = [0]
-    for n in t["NS"]:
-        soff.append(soff[-1] + n)
-    lines = [
-        "// generated by zuko_amd/static_ar.py — do not edit",
-        '#include "fused_ar_static_impl.h"',
-        "namespace {",
-        "struct Shape {",
-        f"  static constexpr int DIN = {t['DIN']}, DOUT = {t['DOUT']}, NIT = {t['NIT']}, NH = {t['NH']}, TMAX = {t['TMAX']}, NCHUNK = {t['NCHUNK']}, WAVES = 8, ACT = 1;",
-        "  static constexpr bool HAS_ALT = false;",
-        _arr("HT", "int", t["HT"]), _arr("NS", "int", t["NS"]), _arr("SOFF", "int", soff), _arr("BASE", "int", t["BASE"]),
-        _arr("S_OTG", "unsigned char", t["S_OTG"]), _arr("S_IT", "unsigned char", t["S_IT"]), _arr("S_ALT", "unsigned char", t["S_IT"]),
-        _arr("S_MASK", "unsigned char", t["S_MASK"]),
-        "};",
-        "}  // namespace",
-        'extern "C" int zk_ars_dgrad_launch(const zk::ArArgs* a, int abi, int args_bytes, void* stream) { return zk::ars_dgrad_launch<Shape>(a, abi, args_bytes, stream); }',
-        "",
-    ]
-    return "\n".join(lines)
-
-
-class ChainKernel:
-    def __init__(self, so: str) -> None:
-        self.so = so
-        self.cdll = ctypes.CDLL(so)
-        self.launcher = ctypes.cast(self.cdll.zk_ars_dgrad_launch, ctypes.c_void_p)
-
-
-_CHAINS: dict[str, ChainKernel] = {}
-
-
-def chain_kernel(t: dict, allow_compile: bool, verbose: bool = False, out_dir: str | None = None):
-    """The compiled dgrad-chain kernel for tables `t` (arsd_<sig>.so), built on demand when allowed; None otherwise."""
-    stamp = _header_digest()
-    sig = _digest({"t": t, "headers": stamp})
-    stem = f"arsd_{sig}"
-    with _LOCK:
-        k = _CHAINS.get(stem)
-        if k is not None:
-            return k
-        so = _find(stem + ".so")
-        if so is None:
-            if not allow_compile:
-                return None
-            meta = {"so": stem + ".so", "headers": stamp, "core": "chain", "l0": [], "alt": None, "DIN": t.get("DIN", t.get("DIN0")), "DOUT": t["DOUT"], "HT": t["HT"]}
-            so = _build_so(stem, lambda: emit_chain_split(t) if t.get("chain") in (2, 3) else emit_chain(t), meta, verbose, out_dir)
-            if so is None:
-                return None
-        try:
-            k = ChainKernel(so)
-        except OSError as exc:
-            _warn_once("load:" + so, f"cannot load {so}: {exc}")
-            return None
-        _CHAINS[stem] = k
-        return k
+def chain_kernel(t: dict, allow_compile: bool):
+    """The loaded backward kernel for tables `t` (chain_tables / chain_split_tables), built on demand when allowed; None otherwise."""
+    found = find_or_compile(FAMILIES["arsd"][t["chain"]], t, allow_compile)
+    return None if found is None else found[0]
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -963,7 +928,6 @@ def prebuild(verbose: bool = True, jobs: int = 4) -> list[str]:
     from concurrent.futures import ThreadPoolExecutor
 
     # kernels built against another version of the template / headers can never be selected again: drop them
-    stamp = _header_digest()
     if os.path.isdir(ARS_DIR):
         for name in os.listdir(ARS_DIR):
             if name.endswith(".json"):
@@ -984,7 +948,12 @@ def prebuild(verbose: bool = True, jobs: int = 4) -> list[str]:
                     os.remove(os.path.join(ARS_DIR, name))
                 except OSError:
                     pass
-    work, chains, splits, halves = [], [], [], []
+    work = []  # (family, tables, alt), every unit once
+
+    def want(fam, t, alt=None):
+        if (fam, t, alt) not in work:
+            work.append((fam, t, alt))
+
     for entry in PREBUILT:
         kind, features, context, hidden, bins = entry[:5]
         import torch
@@ -999,15 +968,15 @@ def prebuild(verbose: bool = True, jobs: int = 4) -> list[str]:
                 if (features + context) % 4 == 0 and layout.kind in (0, 1) and layout.total in (2, 23) and pl is not None:  # what zuko_amd/train.py:autoregressive() covers
                     cands.append(chain_tables_for(lins, full=True, packed={"uni": layout.kind, "featmap": pl.featmap, "nt": layout.nt, "fpl": layout.fpl, "total": layout.total}))
                 for tg in cands:
-                    if tg is not None and not any(c[0] == tg[0] for c in chains):
-                        chains.append(tg)
+                    if tg is not None:
+                        want(FAMILIES["arsd"][tg[0]["chain"]], tg[0])
         for pl in (pa, pd):
             ts = split_tables(pl, layout.kind, act)
-            if ts is not None and not any(x == ts[0] for x in splits):
-                splits.append(ts[0])
+            if ts is not None:
+                want(ARX, ts[0])
             th = half_tables(pl, layout.kind, act)  # the two-part twin (inference launches)
-            if th is not None and not any(x == th[0] for x in halves):
-                halves.append(th[0])
+            if th is not None:
+                want(ARH, th[0])
         if layout.kind in SPLIT_ONLY_KINDS:
             continue  # (no f32-instruction kernel, no training chain for this kind)
         ta, td = tables(pa, layout.kind, act), tables(pd, layout.kind, act)
@@ -1015,9 +984,9 @@ def prebuild(verbose: bool = True, jobs: int = 4) -> list[str]:
             raise RuntimeError(f"zuko_amd.static_ar: no static kernel for the prebuilt shape {entry}")
         (ca, la), (cdesc, ld) = _split(ta), _split(td)
         if ca == cdesc:
-            work.append((ta, None if la == ld else ld))
+            want(ARS, ta, None if la == ld else ld)
         else:
-            work += [(ta, None), (td, None)]
+            want(ARS, ta), want(ARS, td)
     # the alternative workgroup geometry of the split kernels, for the headline conditioner only (tests/test_gpu_flows.py exercises it)
     prev = os.environ.get("ZUKO_AMD_SPLIT_GEOM")
     if prev is None:
@@ -1027,18 +996,15 @@ def prebuild(verbose: bool = True, jobs: int = 4) -> list[str]:
             for pl, layout, _ in _plans_for(kind, features, context, hidden, bins):
                 pl._split_cache = None
                 ts = split_tables(pl, layout.kind, 1)
-                if ts is not None and not any(x == ts[0] for x in splits):
-                    splits.append(ts[0])
+                if ts is not None:
+                    want(ARX, ts[0])
         finally:
             del os.environ["ZUKO_AMD_SPLIT_GEOM"]
     with ThreadPoolExecutor(max_workers=jobs) as ex:
-        metas = list(ex.map(lambda w: compile_kernel(w[0], w[1], verbose, ARS_DIR), work))
-        kerns = list(ex.map(lambda tg: chain_kernel(tg[0], True, verbose, ARS_DIR), chains))
-        xmetas = list(ex.map(lambda t: compile_split(t, verbose, ARS_DIR), splits))
-        hmetas = list(ex.map(lambda t: compile_half(t, verbose, ARS_DIR), halves))
-    if any(m is None for m in metas + xmetas + hmetas) or any(k is None for k in kerns):
+        metas = list(ex.map(lambda w: compile_unit(*w, verbose, ARS_DIR), work))
+    if any(m is None for m in metas):
         raise RuntimeError("zuko_amd.static_ar: a prebuilt static kernel failed to compile")
-    return [m["so"] for m in metas + xmetas + hmetas] + [os.path.basename(k.so) for k in kerns]
+    return [m["so"] for m in metas]
 
 
 if __name__ == "__main__":

@@ -368,16 +368,15 @@ def _fused_forward(st, x: Tensor, out_features: int, uni=None, packed_width: int
     phi = torch.empty((N, packed_width or out_features), dtype=torch.float32, device=x.device)
     kern, rev = st.static
     hp = [_ptr(h) for h in hs] + [None] * (3 - len(hs))
-    extra = {}
+    extra = dict(bound=0.0, slope=0.0)  # (the map's constants: set below when the launch evaluates it)
     if amax is not None:  # [maxima of x, h_1, h_2, ..] (device, zeroed): the launch folds max |x|, max |h_l| into them (operand-split kernels)
         extra.update({f"amax{i}": _ptr(t) for i, t in enumerate(amax[1:4])})
         extra["amax3"] = _ptr(amax[0])  # (x)
     if uni is not None:
         y, ladj = torch.empty((N, p.features), dtype=torch.float32, device=x.device), torch.empty(N, dtype=torch.float32, device=x.device)
         extra.update(dict(y=_ptr(y), ldy=y.stride(0), ladj=_ptr(ladj), bound=float(uni[0]), slope=float(uni[1])))
-    a = _C.args("zk_ar_args_v1", launcher=kern.launcher, rev=rev, uni_kind=p.layout.kind, N=N, D=p.features, DIN=x.shape[1], x=_ptr(x), ldx=x.stride(0), h1=hp[0], h2=hp[1], h3=hp[2],
-                phi=_ptr(phi), ldphi=phi.stride(0), phi_packed=int(packed_width > 0), wstream=_ptr(st.fine_stream), bias=_ptr(st.bias), bias_floats=st.bias_floats, featmap=_ptr(st.featmap),
-                n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=st.fine_n_chunks, act=1, **extra)
+    a = st.static_args(kern.launcher, rev, st.fine, N=N, DIN=x.shape[1], x=_ptr(x), ldx=x.stride(0), h1=hp[0], h2=hp[1], h3=hp[2], phi=_ptr(phi), ldphi=phi.stride(0),
+                       phi_packed=int(packed_width > 0), **extra)  # (st.act is 1: _fused_forward_state)
     err = _C.lib().zk_ar_forward_train(a, _stream())
     _C.check(err, "zk_ar_forward_train")
     return (hs, phi) if uni is None else (hs, phi, y, ladj)
