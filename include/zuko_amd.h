@@ -648,6 +648,57 @@ int zk_mnn_forward(const zk_mnn_args_v1* args, void* stream);
 int zk_mnn_inverse(const zk_mnn_args_v1* args, void* stream);
 int zk_mnn_image_floats(int S, int n_hidden, int width0, int width1, int width2);
 
+/* ---- unconstrained monotone neural network of the unconstrained neural autoregressive flow (UNAF; fp32) ---------------------------------
+ * Every feature f owns an integrand network h_f: (1 + S) -> width0 [-> width1 [-> width2]] -> 1 with SIGNED weights and ELU(alpha = 1); its
+ * input is cat(u, signal).  With sq(v) = v / (1 + |v / 7|), g(u) = exp(sq(h(u, signal))) and (t_i, w_i) the n_quad-point Gauss-Legendre rule on
+ * [0, 1] (zuko/flows/neural.py:100-104, zuko/utils.py:328-363):
+ *     f(x) = x * sum_{i = 0 .. n_quad - 1} w_i g(t_i x)                 (the sum in the order i = 0, 1, ...)
+ * zk_umnn_forward replaces UnconstrainedMonotonicTransform.call_and_ladj + AdditiveTransform (zuko/transforms.py:911-924, zuko/flows/neural.py:
+ * 106-118): y = f(x) + constant, ladj = sq(h(x, signal)) (= log g(x) without the exp / log round trip).  zk_umnn_inverse replaces
+ * MonotonicTransform._inverse + Bisection.forward: target = y - constant, a = -bound, b = bound, n_bisect times c = (a + b) / 2,
+ * f(c) < target ? a = c : b = c, result (a + b) / 2.  The execution model, the limits, the weight image (zuko_amd/mnn_plan.py: layout, here of the
+ * signed weights) and `feat`, `ladj`, `work` are those of zk_mnn_*; zk_mnn_image_floats is the size of an image.  An element's result depends
+ * on its own x, signal, constant and feature only.
+ *
+ *   signal    the S values of element (n, j) start at signal + n * ld_signal + j * ld_col, ld_col >= S (ld_col = S: packed as for zk_mnn_*;
+ *             ld_col = S + 1 with constant = signal + S: the conditioner's phi [N, Dsel, S + 1] read in place), ld_signal >= (Dsel - 1) * ld_col + S
+ *   constant  element (n, j) at constant + n * ld_constant + j * ld_constant_col (strides >= 0), or NULL (= 0)
+ *   quad      DEVICE float [2 * n_quad]: the nodes t_i, then the weights w_i; 1 <= n_quad <= 64 */
+typedef struct zk_umnn_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_umnn_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t S;               /* signal features */
+  int32_t n_hidden;        /* hidden layers, 1..3 */
+  int32_t width0;          /* hidden widths; 0 behind n_hidden */
+  int32_t width1;
+  int32_t width2;
+  int32_t n_features;      /* images in `image` */
+  int32_t image_floats;    /* floats per image = zk_mnn_image_floats(S, n_hidden, width0, width1, width2) */
+  int32_t ladj_reduced;    /* zk_umnn_forward: != 0: ladj is [N] */
+  int32_t n_bisect;        /* zk_umnn_inverse: bisection steps (the reference: ceil(log2(2 bound / eps)) = 25) */
+  int32_t n_quad;          /* quadrature points (the reference: 32) */
+  int64_t N;
+  int64_t Dsel;
+  int64_t ldx;
+  int64_t ld_signal;
+  int64_t ld_col;
+  int64_t ldy;
+  int64_t ld_constant;
+  int64_t ld_constant_col;
+  double bound;            /* zk_umnn_inverse: the search interval is [-bound, bound] */
+  const void* x;
+  const void* signal;
+  const void* constant;    /* or NULL */
+  const void* image;
+  const void* quad;
+  const int32_t* feat;     /* or NULL */
+  void* y;
+  void* ladj;              /* zk_umnn_forward */
+  void* work;              /* zk_umnn_forward with ladj_reduced */
+} zk_umnn_args_v1;
+int zk_umnn_forward(const zk_umnn_args_v1* args, void* stream);
+int zk_umnn_inverse(const zk_umnn_args_v1* args, void* stream);
+
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *
  * out[n] = sum_d Normal(loc[d], scale[d]).log_prob(z[n, d]) (+ ladj[n] if ladj != NULL). */
 int zk_diag_normal_log_prob(int dtype, int64_t N, int64_t D, const void* z, const void* loc, const void* scale,

@@ -1,10 +1,10 @@
 r"""Flow factories of the hot path: MAF / NSF (autoregressive), NICE / RealNVP (coupling),
-SOSPF / BPF (polynomial), NAF (monotone networks).  Same constructor signatures and module trees as zuko.flows."""
+SOSPF / BPF (polynomial), NAF / UNAF (monotone networks).  Same constructor signatures and module trees as zuko.flows."""
 
 from .autoregressive import MAF, MaskedAutoregressiveTransform
 from .coupling import NICE, GeneralCouplingTransform, RealNVP
 from .elementwise import ElementWiseTransform
-from .neural import MNN, NAF
+from .neural import MNN, NAF, UMNN, UNAF
 from .polynomial import BPF, SOSPF
 from .spline import NCSF, NSF
 
@@ -17,6 +17,8 @@ __all__ = [
     "NICE",
     "NSF",
     "SOSPF",
+    "UMNN",
+    "UNAF",
     "ElementWiseTransform",
     "GeneralCouplingTransform",
     "MaskedAutoregressiveTransform",

@@ -1,4 +1,4 @@
-r"""Weight image of the monotone networks of a neural autoregressive flow (csrc/mnn.hip).
+r"""Weight image of the per-feature networks of the neural autoregressive flows (csrc/mnn.hip, csrc/umnn.hip).
 
 A `MonotonicMLP(1 + S, 1, hidden, stack=F)` holds F independent networks (zuko/nn.py:356-392).  The kernel keeps ONE network in
 LDS at a time, as an image of `image_floats` floats per feature:
@@ -18,6 +18,9 @@ LDS at a time, as an image of `image_floats` floats per feature:
 The absolute value is taken when the image is made: `index_table` addresses the concatenation of |W_0|, ..., |W_last|, b_0, ..., b_last
 (`flat_parameters`), and zk_gather_f32 builds every feature's image from it on the device.  The arithmetic of `layout` is the one of
 csrc/mnn.hip: mnn_layout (zk_mnn_image_floats returns its total; tests compare the two).
+
+The integrand networks of an unconstrained monotone network (UNAF: a stacked `MLP(1 + S, 1, hidden, stack=F)` with ELU(alpha = 1), csrc/umnn.hip)
+use the same image with the SIGNED weights: `flat_parameters` takes no absolute value for them.
 """
 
 from __future__ import annotations
@@ -130,18 +133,32 @@ def _linears(network):
     return [m for m in network if hasattr(m, "weight")]
 
 
+def is_signed(network) -> bool:
+    """True for the integrand network of a UMNN (plain `Linear`s: signed weights), False for a MonotonicMLP (|W|)."""
+    from .nn import MonotonicLinear
+
+    return not any(isinstance(l, MonotonicLinear) for l in _linears(network))
+
+
 def shape_of(network):
-    """(S, hidden widths, features) of a stacked MonotonicMLP(1 + S, 1, ...), or None when it is something else."""
+    """(S, hidden widths, features) of a stacked MonotonicMLP(1 + S, 1, ...) or of a stacked MLP(1 + S, 1, ...) whose activations are all
+    ELU(alpha = 1) (the integrand of a UMNN), or None when it is something else."""
+    import torch.nn as nn
+
     lins = _linears(network)
     if len(lins) < 2 or any(l.weight.dim() != 3 or l.bias is None for l in lins):
         return None
     if len(list(network)) != 2 * len(lins) - 1 or lins[-1].weight.shape[1] != 1:
         return None
+    if is_signed(network) and any(type(m) is not nn.ELU or m.alpha != 1.0 for m in network if not hasattr(m, "weight")):
+        return None  # (the kernel of the signed networks knows the plain ELU only)
     return lins[0].weight.shape[2] - 1, tuple(l.weight.shape[1] for l in lins[:-1]), lins[0].weight.shape[0]
 
 
 def flat_parameters(network):
     lins = _linears(network)
+    if is_signed(network):
+        return torch.cat([l.weight.detach().reshape(-1) for l in lins] + [l.bias.detach().reshape(-1) for l in lins])
     return torch.cat([l.weight.detach().abs().reshape(-1) for l in lins] + [l.bias.detach().reshape(-1) for l in lins])
 
 

@@ -161,6 +161,15 @@ class MLP(_FusedSequential):
         self.in_features = in_features
         self.out_features = out_features
 
+    def forward(self, x: Tensor) -> Tensor:
+        if self[0].weight.dim() == 3:
+            # a stack of networks (`stack=`: the integrands of a UMNN) is plain torch ops, module by module: the fused (linear, activation)
+            # kernels and the training kernels are built for one weight matrix, and a stacked Linear takes no activation code
+            for m in self:
+                x = m(x)
+            return x
+        return super().forward(x)
+
 
 class MonotonicMLP(MLP):
     r"""MLP with |W| weights and the two-way ELU: every entry of its Jacobian is positive.  Mirrors zuko/nn.py:356-392 (module tree,

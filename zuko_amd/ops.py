@@ -557,8 +557,9 @@ def _mnn_feat(network, feat, device):
     return entry[2]
 
 
-def _mnn_torch_f(network, x: Tensor, signal: Tensor, feat) -> Tensor:
-    """MNN.f (zuko/flows/neural.py:56-60) in torch ops, on the networks of the selected features."""
+def _mnn_torch_f(network, x: Tensor, signal: Tensor, feat, signed: bool = False) -> Tensor:
+    """MNN.f (zuko/flows/neural.py:56-60) in torch ops, on the networks of the selected features; `signed`: the weights as they are (the
+    integrand of a UMNN) instead of |W|."""
     sel = None
     if feat is not None:
         sel = torch.arange(feat[0], feat[1], device=x.device) if isinstance(feat, tuple) else feat.to(device=x.device, dtype=torch.long)
@@ -566,7 +567,7 @@ def _mnn_torch_f(network, x: Tensor, signal: Tensor, feat) -> Tensor:
     h = torch.cat((xb, signal.expand(xb.shape[:-1] + signal.shape[-1:])), dim=-1)
     for m in network:
         if hasattr(m, "weight"):
-            W, b = m.weight.abs(), m.bias
+            W, b = (m.weight if signed else m.weight.abs()), m.bias
             if sel is not None:
                 W, b = W.index_select(0, sel), None if b is None else b.index_select(0, sel)
             h = torch.einsum("...ij,...j->...i", W, h)
@@ -694,5 +695,186 @@ def mnn_inverse(y: Tensor, signal: Tensor, network, feat=None, bound: float = MN
     x = torch.empty(y2.shape, dtype=torch.float32, device=y.device)
     a = _mnn_args(img, y2, s2, _mnn_feat(network, feat, y.device), x, n_bisect=n, bound=float(bound))
     _C.check(_C.lib().zk_mnn_inverse(a, _stream()), "zk_mnn_inverse")
+    del data
+    return x.reshape(shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# unconstrained monotone neural network (UNAF): zk_umnn_forward / zk_umnn_inverse, torch ops when the kernel does not serve the call
+# ------------------------------------------------------------------------------------------------
+
+UMNN_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_unaf.py measures the kernels against it)
+UMNN_QUAD_MAX = 64  # UMNN_QUAD_MAX of csrc/umnn.hip
+
+
+def umnn_supported(S: int, widths) -> bool:
+    """True when zk_umnn_forward / zk_umnn_inverse serve per-feature integrand networks (1 + S) -> widths -> 1: the limits of mnn_supported."""
+    return mnn_supported(S, widths)
+
+
+@lru_cache(maxsize=None)
+def _umnn_rule(n: int):
+    """(nodes, weights) of the n-point Gauss-Legendre rule on [0, 1] in float64 (zuko/utils.py:328-347)."""
+    nodes, weights = np.polynomial.legendre.leggauss(int(n))
+    return (nodes + 1) / 2, weights / 2
+
+
+_UMNN_QUAD: dict = {}
+
+
+def _umnn_quad(n: int, device) -> Tensor:
+    """float32 device table [2 n] of zk_umnn_*: the nodes, then the weights, rounded from float64; cached per device."""
+    key = (str(device), int(n))
+    t = _UMNN_QUAD.get(key)
+    if t is None:
+        t = torch.from_numpy(np.concatenate(_umnn_rule(n)).astype(np.float32)).to(device)
+        _UMNN_QUAD[key] = t
+    return t
+
+
+def _umnn_squash(h: Tensor) -> Tensor:
+    return h / (1 + abs(h / 7))  # log g, within (-7, 7) (zuko/flows/neural.py:104)
+
+
+def _umnn_torch_g(network, u: Tensor, signal: Tensor, feat) -> Tensor:
+    """UMNN.g (zuko/flows/neural.py:100-104) in torch ops, on the networks of the selected features."""
+    return torch.exp(_umnn_squash(_mnn_torch_f(network, u, signal, feat, signed=True)))
+
+
+def _umnn_quadrature(g, x: Tensor, n: int) -> Tensor:
+    """x sum_i w_i g(t_i x) (GaussLegendre.quadrature over [0, x], zuko/utils.py:349-363; its lerp(0, x, t_i) is t_i x up to rounding)."""
+    nodes, weights = (torch.as_tensor(v, dtype=x.dtype, device=x.device) for v in _umnn_rule(n))
+    u = nodes.reshape((n,) + (1,) * x.dim()) * x
+    return x * torch.tensordot(weights, g(u), dims=1)
+
+
+class _UmnnGaussLegendre(torch.autograd.Function):
+    """f(x) = int_0^x g with the reference's gradients (zuko/utils.py:282-326): g(x) grad w.r.t. the upper limit, and for the parameters the
+    quadrature re-run under autograd."""
+
+    @staticmethod
+    def forward(ctx, g, x, n, *phi):
+        ctx.g, ctx.n = g, n
+        ctx.save_for_backward(x, *phi)
+        return _umnn_quadrature(g, x, n)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_area):
+        x, *phi = ctx.saved_tensors
+        grad_x = ctx.g(x) * grad_area if ctx.needs_input_grad[1] else None
+        grad_phi = ()
+        if phi and any(ctx.needs_input_grad[3:]):
+            with torch.enable_grad():
+                area = _umnn_quadrature(ctx.g, x.detach(), ctx.n)
+            grad_phi = torch.autograd.grad(area, phi, grad_area)
+        return (None, grad_x, None, *(grad_phi or (None,) * len(phi)))
+
+
+def _umnn_phi(network, signal: Tensor):
+    return [p for p in (signal, *network.parameters()) if p.requires_grad] if torch.is_grad_enabled() else []
+
+
+def _umnn_torch_f(network, signal: Tensor, feat, n: int):
+    phi = _umnn_phi(network, signal)
+    return lambda v: _UmnnGaussLegendre.apply(lambda u: _umnn_torch_g(network, u, signal, feat), v, n, *phi)
+
+
+def _umnn_check(network, x: Tensor, signal: Tensor, constant, feat, n: int) -> None:
+    _require_device(constant)
+    _mnn_check(network, x, signal, feat)
+    if constant is not None and (constant.dim() < 1 or constant.shape[-1] not in (1, x.shape[-1])):
+        raise ValueError(f"zuko_amd: unconstrained monotone network: constant [..., D] expected next to x {tuple(x.shape)}, got {tuple(constant.shape)}")
+    if int(n) < 1:
+        raise ValueError(f"zuko_amd: unconstrained monotone network: a quadrature of {n} points")
+
+
+def _umnn_kernel_serves(network, x: Tensor, signal: Tensor, constant, n: int):
+    """The network's weight image when the HIP kernels serve this call (fp32, ELU networks of a supported shape, at most 64 quadrature points,
+    nothing asks for gradients), else None."""
+    from . import mnn_plan
+
+    if not UMNN_KERNEL or n > UMNN_QUAD_MAX or not mnn_plan.is_signed(network):
+        return None
+    ts = [x, signal, *network.parameters()] + ([] if constant is None else [constant])
+    if any(t.dtype != torch.float32 for t in ts):
+        return None
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        return None
+    return mnn_plan.image_of(network, x.device)
+
+
+def _umnn_prepare(x: Tensor, signal: Tensor, constant):
+    """The operands as the kernel reads them, IN PLACE wherever their strides allow (the conditioner's packed phi [N, D, S + 1] is not copied to
+    split it): shape, x [N, D], signal [N, D, S], constant [N, D] | None and the stride fields of the argument block."""
+    S = signal.shape[-1]
+    batch = torch.broadcast_shapes(x.shape[:-1], signal.shape[:-2], *(() if constant is None else (constant.shape[:-1],)))
+    D = x.shape[-1]
+    x2 = x.expand(batch + (D,)).reshape(-1, D)
+    N = x2.shape[0]
+    if x2.stride(1) != 1 or (N > 1 and x2.stride(0) < 1):
+        x2 = x2.contiguous()
+    s3 = signal.expand(batch + (D, S)).reshape(-1, D, S)
+    if s3.stride(2) != 1 or (D > 1 and s3.stride(1) < S) or (N > 1 and s3.stride(0) < (D - 1) * s3.stride(1) + S):
+        s3 = s3.contiguous()
+    ld_col = s3.stride(1) if D > 1 else S
+    strides = dict(ldx=x2.stride(0) if N > 1 else D, ld_signal=s3.stride(0) if N > 1 else (D - 1) * ld_col + S, ld_col=ld_col, ldy=D)
+    c2 = None
+    if constant is not None:
+        c2 = constant.expand(batch + (D,)).reshape(-1, D)
+        strides.update(ld_constant=c2.stride(0) if N > 1 else 0, ld_constant_col=c2.stride(1) if D > 1 else 0)
+    return batch + (D,), x2, s3, c2, strides
+
+
+def _umnn_args(img, n: int, x2: Tensor, s3: Tensor, c2, strides: dict, feat, out: Tensor, **extra):
+    N, D = x2.shape
+    lay = img.layout
+    w = list(lay.widths) + [0, 0]
+    return _C.args("zk_umnn_args_v1", S=lay.S, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], n_features=img.features, image_floats=lay.total,
+                   n_quad=n, N=N, Dsel=D, x=x2.data_ptr(), signal=s3.data_ptr(), constant=None if c2 is None else c2.data_ptr(), image=img.data.data_ptr(),
+                   quad=_umnn_quad(n, x2.device).data_ptr(), feat=None if feat is None else feat.data_ptr(), y=out.data_ptr(), **strides, **extra)
+
+
+def umnn_forward(x: Tensor, signal: Tensor, constant, network, feat=None, reduce: bool = False, n: int = 32):
+    """(y, ladj) of the per-feature unconstrained monotone networks: y = x sum_i w_i g(t_i x) + constant over the n-point Gauss-Legendre rule,
+    g = exp(squash(h)) with h = `network` (a stacked zuko_amd.nn.MLP(1 + S, 1, ...) with ELU), ladj = squash(h(x)) = log g(x).  x [..., D],
+    signal [..., D, S], constant [..., D] | None; column j uses the network of feature feat[j] (`feat`: None, a (lo, hi) run or an index tensor).
+    zk_umnn_forward when it serves the call; otherwise (unsupported shape or activation, float64, gradients) the same expressions as torch ops
+    with the reference's autograd semantics (zuko/utils.py:282-326)."""
+    _umnn_check(network, x, signal, constant, feat, n)
+    img = _umnn_kernel_serves(network, x, signal, constant, n)
+    if img is None:
+        y = _umnn_torch_f(network, signal, feat, n)(x)
+        y = y if constant is None else y + constant
+        ladj = _umnn_squash(_mnn_torch_f(network, x, signal, feat, signed=True)).expand(y.shape)
+        return y, (ladj.sum(dim=-1) if reduce else ladj)
+    shape, x2, s3, c2, strides = _umnn_prepare(x, signal, constant)
+    N, D = x2.shape
+    data = img.refresh(network)
+    y = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x.device)
+    work = torch.empty((N, D), dtype=torch.float32, device=x.device) if reduce else None
+    a = _umnn_args(img, n, x2, s3, c2, strides, _mnn_feat(network, feat, x.device), y, ladj=ladj.data_ptr(), work=None if work is None else work.data_ptr(),
+                   ladj_reduced=int(reduce))
+    _C.check(_C.lib().zk_umnn_forward(a, _stream()), "zk_umnn_forward")
+    del data
+    return y.reshape(shape), ladj.reshape(shape[:-1] if reduce else shape)
+
+
+def umnn_inverse(y: Tensor, signal: Tensor, constant, network, feat=None, bound: float = MNN_BOUND, eps: float = MNN_EPS, n: int = 32) -> Tensor:
+    """x with f(x) + constant = y by ceil(log2(2 bound / eps)) bisection steps on [-bound, bound] (zuko/transforms.py:609-617): zk_umnn_inverse,
+    or the same loop in torch ops when the kernel does not serve the call (see umnn_forward)."""
+    _umnn_check(network, y, signal, constant, feat, n)
+    steps = math.ceil(math.log2(2 * bound / eps))
+    img = _umnn_kernel_serves(network, y, signal, constant, n)
+    if img is None:
+        target = y if constant is None else y - constant
+        target = target.expand(torch.broadcast_shapes(target.shape, signal.shape[:-1]))
+        return _MnnBisection.apply(_umnn_torch_f(network, signal, feat, n), target, float(bound), steps, *_umnn_phi(network, signal))
+    shape, y2, s3, c2, strides = _umnn_prepare(y, signal, constant)
+    data = img.refresh(network)
+    x = torch.empty(y2.shape, dtype=torch.float32, device=y.device)
+    a = _umnn_args(img, n, y2, s3, c2, strides, _mnn_feat(network, feat, y.device), x, n_bisect=steps, bound=float(bound))
+    _C.check(_C.lib().zk_umnn_inverse(a, _stream()), "zk_umnn_inverse")
     del data
     return x.reshape(shape)

@@ -40,6 +40,7 @@ __all__ = [
     "SOSPolynomialTransform",
     "ShiftedSOSPolynomialTransform",
     "SoftclipTransform",
+    "UnconstrainedMonotonicNetworkTransform",
 ]
 
 
@@ -204,6 +205,31 @@ class MonotonicNetworkTransform(_Univariate):
 
     def _inverse(self, y: Tensor) -> Tensor:
         return ops.mnn_inverse(y, self.signal, self.network, self.features, self.bound, self.eps)
+
+
+class UnconstrainedMonotonicNetworkTransform(_Univariate):
+    r"""y_d = \int_0^{x_d} g_d(u | signal_d) du + constant_d with g_d = exp(squash(h_d)) and h_d the integrand network of feature d (a stacked
+    `zuko_amd.nn.MLP(1 + S, 1, ...)` with ELU), the integral by an n-point Gauss-Legendre rule: the univariate map of the unconstrained neural
+    autoregressive flow.  Mirrors UMNN.g + UnconstrainedMonotonicTransform composed with AdditiveTransform (zuko/flows/neural.py:100-118,
+    zuko/transforms.py:878-924): value and log-derivative in one launch (zk_umnn_forward), the inverse by the reference's bisection on
+    [-bound, bound] to `eps` (zk_umnn_inverse).  `features` as for MonotonicNetworkTransform.  Unsupported network shapes or activations,
+    float64 and calls that need gradients run the same expressions as torch ops (zuko_amd/ops.py: umnn_forward)."""
+
+    def __init__(self, signal: Tensor, constant: Tensor | None, network, features=None, n: int = 32, bound: float = 10.0, eps: float = 1e-6, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.signal = signal
+        self.constant = constant
+        self.network = network
+        self.features = features
+        self.n = n
+        self.bound = bound
+        self.eps = eps
+
+    def _forward(self, x, reduce):
+        return ops.umnn_forward(x, self.signal, self.constant, self.network, self.features, reduce, self.n)
+
+    def _inverse(self, y: Tensor) -> Tensor:
+        return ops.umnn_inverse(y, self.signal, self.constant, self.network, self.features, self.bound, self.eps, self.n)
 
 
 # ------------------------------------------------------------------------------------------------
