@@ -647,6 +647,10 @@ typedef struct zk_mnn_args_v1 {
 int zk_mnn_forward(const zk_mnn_args_v1* args, void* stream);
 int zk_mnn_inverse(const zk_mnn_args_v1* args, void* stream);
 int zk_mnn_image_floats(int S, int n_hidden, int width0, int width1, int width2);
+/* The launch geometry zk_mnn_forward / zk_mnn_inverse choose for an [N, Dsel] call (host only, nothing touches the device): a block covers
+ * rows_per_block rows (64, 128 or 256) x feats_per_block consecutive columns (1 or 4).  Results do not depend on it; the query exists so that
+ * tests can name the shapes that reach every geometry.  N >= 1, 1 <= Dsel <= 2^20, both pointers non-NULL; otherwise hipErrorInvalidValue. */
+int zk_mnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block);
 
 /* ---- unconstrained monotone neural network of the unconstrained neural autoregressive flow (UNAF; fp32) ---------------------------------
  * Every feature f owns an integrand network h_f: (1 + S) -> width0 [-> width1 [-> width2]] -> 1 with SIGNED weights and ELU(alpha = 1); its
@@ -698,6 +702,8 @@ typedef struct zk_umnn_args_v1 {
 } zk_umnn_args_v1;
 int zk_umnn_forward(const zk_umnn_args_v1* args, void* stream);
 int zk_umnn_inverse(const zk_umnn_args_v1* args, void* stream);
+/* The launch geometry of zk_umnn_forward / zk_umnn_inverse: as zk_mnn_launch_geometry. */
+int zk_umnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block);
 
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *
  * out[n] = sum_d Normal(loc[d], scale[d]).log_prob(z[n, d]) (+ ladj[n] if ladj != NULL). */

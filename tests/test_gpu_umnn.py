@@ -8,6 +8,7 @@ import torch
 
 import umnn_ref
 from conftest import T, golden, sd_hash
+from mnn_nets import UmnnNet as Net
 from parity import C_NOISE, _stats, assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -15,57 +16,6 @@ pytestmark = pytest.mark.gpu
 FORWARD_CASES = ["umnn_a", "umnn_b", "umnn_c", "umnn_e"]
 INVERSE_CASES = ["umnn_a", "umnn_b", "umnn_c"]
 UNAF_KW, UNAF_SEED = dict(features=5, context=3, transforms=2), 11
-
-
-class Net:
-    """A fixture's networks on the device: the weight image built as the product builds it (host index table + zk_gather_f32) from the SIGNED
-    weights, and the quadrature table."""
-
-    def __init__(self, g, dev, n_quad=32):
-        import zuko_amd._C as C
-        from zuko_amd import mnn_plan
-
-        self.W, self.B = umnn_ref.params_of(g, device=dev)
-        self.S, self.widths, self.F = self.W[0].shape[2] - 1, tuple(w.shape[1] for w in self.W[:-1]), self.W[0].shape[0]
-        self.L = mnn_plan.layout(self.S, self.widths)
-        idx = torch.from_numpy(mnn_plan.index_table(self.S, self.widths, self.F).reshape(-1)).to(dev)
-        flat = torch.cat([w.reshape(-1) for w in self.W] + [b.reshape(-1) for b in self.B])
-        self.image = torch.empty(idx.numel(), dtype=torch.float32, device=dev)
-        C.check(C.lib().zk_gather_f32(flat.data_ptr(), None, idx.data_ptr(), idx.numel(), self.image.data_ptr(), C.stream()), "zk_gather_f32")
-        t, w = np.polynomial.legendre.leggauss(n_quad)
-        self.n_quad = n_quad
-        self.quad = torch.from_numpy(np.concatenate([(t + 1) / 2, w / 2]).astype(np.float32)).to(dev)
-        torch.cuda.synchronize()
-
-    def _args(self, x, sig, cst, out, feat, **extra):
-        """x [N, D], sig [N, D, S] (last stride 1, any column and row stride), cst [N, D] (any strides) | None."""
-        import zuko_amd._C as C
-
-        N, D = x.shape
-        w = list(self.widths) + [0, 0]
-        assert x.stride(1) == 1 and sig.stride(2) == 1 and sig.shape == (N, D, self.S)
-        kw = {} if cst is None else dict(constant=cst.data_ptr(), ld_constant=cst.stride(0), ld_constant_col=cst.stride(1))
-        return C.args("zk_umnn_args_v1", S=self.S, n_hidden=len(self.widths), width0=w[0], width1=w[1], width2=w[2], n_features=self.F, image_floats=self.L.total, N=N,
-                      Dsel=D, n_quad=self.n_quad, ldx=x.stride(0), ld_signal=sig.stride(0), ld_col=sig.stride(1), ldy=D, x=x.data_ptr(), signal=sig.data_ptr(),
-                      image=self.image.data_ptr(), quad=self.quad.data_ptr(), feat=None if feat is None else feat.data_ptr(), y=out.data_ptr(), **kw, **extra)
-
-    def forward(self, x, sig, cst, feat=None, reduce=False):
-        import zuko_amd._C as C
-
-        N, D = x.shape
-        y = torch.empty((N, D), dtype=torch.float32, device=x.device)
-        ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x.device)
-        work = torch.empty((N, D), dtype=torch.float32, device=x.device)
-        a = self._args(x, sig, cst, y, feat, ladj=ladj.data_ptr(), work=work.data_ptr(), ladj_reduced=int(reduce))
-        C.check(C.lib().zk_umnn_forward(a, C.stream()), "zk_umnn_forward")
-        return y, ladj
-
-    def inverse(self, t, sig, cst, feat=None):
-        import zuko_amd._C as C
-
-        x = torch.empty(t.shape, dtype=torch.float32, device=t.device)
-        C.check(C.lib().zk_umnn_inverse(self._args(t, sig, cst, x, feat, n_bisect=25, bound=10.0), C.stream()), "zk_umnn_inverse")
-        return x
 
 
 @pytest.fixture(scope="module")

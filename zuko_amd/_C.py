@@ -157,8 +157,10 @@ SIGNATURES = {
     "zk_mnn_forward": [_MNN, P],
     "zk_mnn_inverse": [_MNN, P],
     "zk_mnn_image_floats": [I, I, I, I, I],
+    "zk_mnn_launch_geometry": [L, L, POINTER(c_int), POINTER(c_int)],
     "zk_umnn_forward": [_UMNN, P],
     "zk_umnn_inverse": [_UMNN, P],
+    "zk_umnn_launch_geometry": [L, L, POINTER(c_int), POINTER(c_int)],
 }
 
 

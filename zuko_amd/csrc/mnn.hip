@@ -303,12 +303,8 @@ template <bool INVERSE> static int mnn_launch(const zk_mnn_args_v1* p, void* str
   a.y = (float*)p->y; a.ladj = (float*)(p->ladj_reduced ? p->work : p->ladj);
   a.N = p->N; a.ldx = p->ldx; a.lds = p->ld_signal; a.ldy = p->ldy;
   a.Dsel = (int)p->Dsel; a.n_features = p->n_features; a.n_bisect = p->n_bisect; a.bound = (float)p->bound;
-  // launch geometry (results do not depend on it): enough blocks for 256 CUs first, then longer runs per image load
-  const long long t64 = (a.N + 63) / 64;
-  a.feats_per_block = t64 * ((a.Dsel + 3) / 4) >= 512 ? 4 : 1;
+  if (zk_mnn_launch_geometry(a.N, a.Dsel, &a.rows_per_block, &a.feats_per_block) != 0) return ZK_EINVAL;  // (results do not depend on it)
   const long long cols = (a.Dsel + a.feats_per_block - 1) / a.feats_per_block;
-  a.rows_per_block = 256;
-  while (a.rows_per_block > 64 && ((a.N + a.rows_per_block - 1) / a.rows_per_block) * cols < 1024) a.rows_per_block /= 2;
   const long long gx = (a.N + a.rows_per_block - 1) / a.rows_per_block;
   if (gx > 0x7fffffffLL || cols > 65535) return ZK_EINVAL;
   const dim3 grid((unsigned)gx, (unsigned)cols);
@@ -326,6 +322,18 @@ template <bool INVERSE> static int mnn_launch(const zk_mnn_args_v1* p, void* str
 
 extern "C" int zk_mnn_forward(const zk_mnn_args_v1* args, void* stream) { return zk::mnn_launch<false>(args, stream); }
 extern "C" int zk_mnn_inverse(const zk_mnn_args_v1* args, void* stream) { return zk::mnn_launch<true>(args, stream); }
+// The launch geometry of an [N, Dsel] call: enough blocks for 256 CUs first, then longer runs per image load.  A pure function of the two sizes.
+extern "C" int zk_mnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block) {
+  if (N < 1 || Dsel < 1 || Dsel > (1 << 20) || !rows_per_block || !feats_per_block) return ZK_EINVAL;
+  const long long t64 = (N + 63) / 64;
+  const int feats = t64 * ((Dsel + 3) / 4) >= 512 ? 4 : 1;
+  const long long cols = (Dsel + feats - 1) / feats;
+  int rows = 256;
+  while (rows > 64 && ((N + rows - 1) / rows) * cols < 1024) rows /= 2;
+  *rows_per_block = rows;
+  *feats_per_block = feats;
+  return 0;
+}
 extern "C" int zk_mnn_image_floats(int S, int n_hidden, int width0, int width1, int width2) {
   zk::MnnLayout L;
   const int widths[3] = {width0, width1, width2};

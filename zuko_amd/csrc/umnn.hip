@@ -305,12 +305,8 @@ template <bool INVERSE> static int umnn_launch(const zk_umnn_args_v1* p, void* s
   a.y = (float*)p->y; a.ladj = (float*)(p->ladj_reduced ? p->work : p->ladj);
   a.N = p->N; a.ldx = p->ldx; a.lds = p->ld_signal; a.ldcol = p->ld_col; a.ldy = p->ldy; a.ldc = p->ld_constant; a.ldccol = p->ld_constant_col;
   a.Dsel = (int)p->Dsel; a.n_features = p->n_features; a.n_bisect = p->n_bisect; a.n_quad = p->n_quad; a.bound = (float)p->bound;
-  // launch geometry (results do not depend on it): enough blocks for 256 CUs first, then longer runs per image load
-  const long long t64 = (a.N + 63) / 64;
-  a.feats_per_block = t64 * ((a.Dsel + 3) / 4) >= 512 ? 4 : 1;
+  if (zk_umnn_launch_geometry(a.N, a.Dsel, &a.rows_per_block, &a.feats_per_block) != 0) return ZK_EINVAL;  // (results do not depend on it)
   const long long cols = (a.Dsel + a.feats_per_block - 1) / a.feats_per_block;
-  a.rows_per_block = 256;
-  while (a.rows_per_block > 64 && ((a.N + a.rows_per_block - 1) / a.rows_per_block) * cols < 1024) a.rows_per_block /= 2;
   const long long gx = (a.N + a.rows_per_block - 1) / a.rows_per_block;
   if (gx > 0x7fffffffLL || cols > 65535) return ZK_EINVAL;
   const dim3 grid((unsigned)gx, (unsigned)cols);
@@ -328,3 +324,16 @@ template <bool INVERSE> static int umnn_launch(const zk_umnn_args_v1* p, void* s
 
 extern "C" int zk_umnn_forward(const zk_umnn_args_v1* args, void* stream) { return zk::umnn_launch<false>(args, stream); }
 extern "C" int zk_umnn_inverse(const zk_umnn_args_v1* args, void* stream) { return zk::umnn_launch<true>(args, stream); }
+// The launch geometry of an [N, Dsel] call (the rule of zk_mnn_launch_geometry, restated as the kernels are): enough blocks for 256 CUs first,
+// then longer runs per image load.  A pure function of the two sizes.
+extern "C" int zk_umnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block) {
+  if (N < 1 || Dsel < 1 || Dsel > (1 << 20) || !rows_per_block || !feats_per_block) return ZK_EINVAL;
+  const long long t64 = (N + 63) / 64;
+  const int feats = t64 * ((Dsel + 3) / 4) >= 512 ? 4 : 1;
+  const long long cols = (Dsel + feats - 1) / feats;
+  int rows = 256;
+  while (rows > 64 && ((N + rows - 1) / rows) * cols < 1024) rows /= 2;
+  *rows_per_block = rows;
+  *feats_per_block = feats;
+  return 0;
+}
