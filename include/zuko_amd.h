@@ -702,7 +702,7 @@ typedef struct zk_umnn_args_v1 {
 } zk_umnn_args_v1;
 int zk_umnn_forward(const zk_umnn_args_v1* args, void* stream);
 int zk_umnn_inverse(const zk_umnn_args_v1* args, void* stream);
-/* The launch geometry of zk_umnn_forward / zk_umnn_inverse: as zk_mnn_launch_geometry. */
+/* The launch geometry of zk_umnn_forward / zk_umnn_inverse: the rule, arguments and return values of zk_mnn_launch_geometry (one function behind both). */
 int zk_umnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block);
 
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *

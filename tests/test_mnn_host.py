@@ -142,7 +142,7 @@ def test_mnn_entry_points_reject_foreign_blocks_and_unsupported_shapes_without_a
         return C.args("zk_mnn_args_v1", **base)
 
     for fn in (lib.zk_mnn_forward, lib.zk_mnn_inverse):
-        assert fn(block(), None) == 0  # (a well-formed block over zero rows: accepted, nothing to launch)
+        assert fn(block(), None) == 0  # (a well-formed block over zero rows: accepted, nothing to launch — with every pointer null)
         bad = block()
         bad.struct_size -= 8
         assert fn(bad, None) == EINVAL
@@ -154,9 +154,14 @@ def test_mnn_entry_points_reject_foreign_blocks_and_unsupported_shapes_without_a
         assert fn(bad, None) == EINVAL
         assert fn(None, None) == EINVAL
         for kw in (dict(width0=30, width1=30), dict(width0=144), dict(width1=0), dict(n_hidden=4), dict(n_hidden=0), dict(S=0), dict(S=64), dict(image_floats=1),
-                   dict(n_hidden=3, width0=128, width1=128, width2=128), dict(ld_signal=79), dict(ldy=4), dict(Dsel=0), dict(N=-1), dict(n_features=0)):
+                   dict(n_hidden=3, width0=128, width1=128, width2=128), dict(ld_signal=79), dict(ldy=4), dict(Dsel=0), dict(N=-1), dict(n_features=0),
+                   dict(Dsel=(1 << 20) + 1, ldy=1 << 21, ld_signal=1 << 25)):
             assert fn(block(**kw), None) == EINVAL, kw
         assert fn(block(N=4), None) == EINVAL  # (rows but no pointers)
+    assert lib.zk_mnn_forward(block(Dsel=1 << 20, ldy=1 << 21, ld_signal=1 << 25), None) == 0  # (the largest column count)
+    # the bisection's parameters are the inverse's alone
+    assert lib.zk_mnn_inverse(block(bound=0.0), None) == EINVAL and lib.zk_mnn_inverse(block(n_bisect=65), None) == EINVAL
+    assert lib.zk_mnn_inverse(block(n_bisect=64), None) == 0 and lib.zk_mnn_forward(block(n_bisect=65, bound=0.0), None) == 0
 
 
 def test_cpu_tensors_are_rejected_and_stacked_linear_is_provided():

@@ -173,7 +173,7 @@ def test_umnn_entry_points_reject_foreign_blocks_and_unsupported_shapes_without_
         return C.args("zk_umnn_args_v1", **base)
 
     for fn in (lib.zk_umnn_forward, lib.zk_umnn_inverse):
-        assert fn(block(), None) == 0  # (a well-formed block over zero rows: accepted, nothing to launch)
+        assert fn(block(), None) == 0  # (a well-formed block over zero rows: accepted, nothing to launch — with every pointer null)
         assert fn(block(ld_col=16, ld_signal=80), None) == 0 and fn(block(n_quad=1), None) == 0 and fn(block(n_quad=64), None) == 0
         bad = block()
         bad.struct_size -= 8
@@ -187,10 +187,13 @@ def test_umnn_entry_points_reject_foreign_blocks_and_unsupported_shapes_without_
         assert fn(None, None) == EINVAL
         for kw in (dict(n_quad=0), dict(n_quad=65), dict(ld_col=15), dict(ld_signal=83), dict(width0=30, width1=30), dict(width0=144), dict(width1=0), dict(n_hidden=4),
                    dict(n_hidden=0), dict(S=0), dict(S=64), dict(image_floats=1), dict(n_hidden=3, width0=128, width1=128, width2=128), dict(ldy=4), dict(Dsel=0),
-                   dict(N=-1), dict(n_features=0), dict(ld_constant=-1), dict(ld_constant_col=-1)):
+                   dict(N=-1), dict(n_features=0), dict(ld_constant=-1), dict(ld_constant_col=-1), dict(Dsel=(1 << 20) + 1, ldy=1 << 21, ld_signal=1 << 25)):
             assert fn(block(**kw), None) == EINVAL, kw
         assert fn(block(N=4), None) == EINVAL  # (rows but no pointers)
+    assert lib.zk_umnn_forward(block(Dsel=1 << 20, ldy=1 << 21, ld_signal=1 << 25), None) == 0  # (the largest column count)
+    # the bisection's parameters are the inverse's alone
     assert lib.zk_umnn_inverse(block(bound=0.0), None) == EINVAL and lib.zk_umnn_inverse(block(n_bisect=65), None) == EINVAL
+    assert lib.zk_umnn_inverse(block(n_bisect=64), None) == 0 and lib.zk_umnn_forward(block(n_bisect=65, bound=0.0), None) == 0
 
 
 def test_other_activations_are_not_served():

@@ -17,7 +17,7 @@ LDS at a time, as an image of `image_floats` floats per feature:
 
 The absolute value is taken when the image is made: `index_table` addresses the concatenation of |W_0|, ..., |W_last|, b_0, ..., b_last
 (`flat_parameters`), and zk_gather_f32 builds every feature's image from it on the device.  The arithmetic of `layout` is the one of
-csrc/mnn.hip: mnn_layout (zk_mnn_image_floats returns its total; tests compare the two).
+csrc/zk_mnn_common.h: mnn_layout, which both kernel families use (zk_mnn_image_floats returns its total; tests compare the two).
 
 The integrand networks of an unconstrained monotone network (UNAF: a stacked `MLP(1 + S, 1, hidden, stack=F)` with ELU(alpha = 1), csrc/umnn.hip)
 use the same image with the SIGNED weights: `flat_parameters` takes no absolute value for them.
@@ -30,7 +30,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-LDS_MAX = 128 * 1024  # MNN_LDS_MAX of csrc/mnn.hip
+LDS_MAX = 128 * 1024  # MNN_LDS_MAX of csrc/zk_mnn_common.h
 
 
 @dataclass
