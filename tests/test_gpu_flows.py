@@ -1,6 +1,8 @@
 """GPU parity: conditioner GEMM and whole flows (log_prob / z / ladj / inverse) against the golden
 vectors of the reference, plus size-independent properties at the BASELINE batch sizes."""
 
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -794,6 +796,74 @@ def test_fused_coupling_kernel(dev, D, ctx, hidden, N, precision, monkeypatch, m
     assert torch.isnan(lb[1]) and torch.isnan(yb.cpu()[1, ~a_cols]).all()
 
 
+@functools.lru_cache(maxsize=None)
+def _static_coupling_reference(n_hidden, N):
+    """One RealNVP(256, hidden [512] * n_hidden) coupling layer on the CPU, its inputs and the oracle's answers in both directions (f32 and float64):
+    computed once per (depth, batch) and shared by the three kernels' cases, which only read them."""
+    import zuko_amd.flows as F
+
+    torch.manual_seed(512 * n_hidden + N)
+    flow = F.RealNVP(256, 0, transforms=1, hidden_features=[512] * n_hidden)
+    sd = {k: v.detach().clone() for k, v in flow.state_dict().items() if v is not None}
+    spec = O.spec_from_state_dict(sd, "coupling", O.UNI_AFFINE, 256)
+    spec64 = to_f64(spec)
+    x = torch.randn(N, 256, generator=torch.Generator().manual_seed(7))
+    with torch.no_grad():
+        fwd = O.flow_forward(spec, x) + O.flow_forward(spec64, d64(x))
+        inv = (O.flow_inverse(spec, x), O.flow_inverse(spec64, d64(x)))
+    return flow, spec, spec64, x, fwd, inv
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [77, 64 * 256 + 65])
+@pytest.mark.parametrize("inverse", [False, True], ids=["forward", "inverse"])
+@pytest.mark.parametrize("n_hidden", [1, 3])
+@pytest.mark.parametrize("kernel", ["static", "split", "half"])
+def test_coupling_kernels_of_the_static_shape(dev, kernel, n_hidden, inverse, N, monkeypatch, matmul):
+    """The three static-shape coupling kernels (coupling_kernel_static: ZUKO_AMD_EXACT_F32=1; coupling_kernel_split: bf16x3; coupling_kernel_half:
+    f16x2) at the smallest conditioner they accept (128 inputs, hidden [512]: two linear layers) and at cfg4's depth, forward and inverse.
+    N = 77: partial last wavefront and tile; N = 64 * 256 + 65: the grid is 256 workgroups, so workgroup 0 takes a second pass (the ring wraps from
+    the last chunk of one pass into the next) and that pass is a ragged tile."""
+    import copy
+
+    flow_cpu, spec, spec64, x, (zo, lo, z64, l64), (xo, x64) = _static_coupling_reference(n_hidden, N)
+    if kernel == "static":
+        monkeypatch.setenv("ZUKO_AMD_EXACT_F32", "1")  # (read when the FusedCoupling is constructed: fused_state below)
+    else:
+        matmul("bf16x3" if kernel == "split" else "f16x2")
+    flow = copy.deepcopy(flow_cpu).to(dev)
+    lazy = flow.transform.transforms[0]
+    st = lazy.fused_state(dev)
+    assert st is not None and st.split == (kernel != "static")
+    launches, run = [], st.run  # every result below must come from the fused launch, not from the layer-wise path behind FusedCouplingTransform._fused
+    monkeypatch.setattr(st, "run", lambda x_, c_, inv_=False: launches.append(bool(inv_)) or run(x_, c_, inv_))
+    tag = f"static-shape coupling ({kernel}) hidden=[512]*{n_hidden} N={N}"
+    with torch.no_grad():
+        if not inverse:
+            z, ladj = lazy().call_and_ladj(x.to(dev))
+            assert st.half_ok == (kernel == "half"), "the two-part kernel serves exactly in f16x2 mode"
+            assert_parity(z, zo, z64, f"{tag}: z")
+            assert_parity(ladj, lo, l64, f"{tag}: ladj")
+            # a non-finite input poisons the transformed half of its own row only; pass-through columns stay as they are
+            xb = x[:4].clone()
+            xb[1, int(lazy.mask.nonzero()[0])] = float("nan")  # a pass-through (conditioning) column
+            yb, lb = lazy().call_and_ladj(xb.to(dev))
+            a_cols = lazy.mask.cpu()
+            assert torch.equal(yb.cpu()[:, a_cols][[0, 2, 3]], xb[:, a_cols][[0, 2, 3]]) and torch.isfinite(yb.cpu()[[0, 2, 3]]).all()
+            assert torch.isnan(lb[1]) and torch.isnan(yb.cpu()[1, ~a_cols]).all()
+            assert launches == [False, False], "z / ladj and the poisoned rows: one forward launch each"
+        else:
+            xk, ladj_inv = lazy().inv.call_and_ladj(x.to(dev))  # (x holds the values to invert)
+            assert st.half_ok == (kernel == "half"), "the two-part kernel serves exactly in f16x2 mode"
+            z_back, _ = lazy().call_and_ladj(xk)
+            zb_o, lf_o = O.flow_forward(spec, xk.cpu())
+            zb_64, lf_64 = O.flow_forward(spec64, d64(xk))
+            assert_parity(xk, xo, x64, f"{tag}: x")
+            assert_parity(z_back, zb_o, zb_64, f"{tag}: forward(inverse(z))")
+            assert_parity(-ladj_inv, lf_o, lf_64, f"{tag}: ladj of the inverse launch")
+            assert launches == [True, False], "x / ladj from one inverse launch, the way back from one forward launch"
+
+
 STATIC_CASES = [("nsf", 64, 0, [256] * 3), ("maf", 64, 0, [256] * 3), ("nsf", 3, 5, [128] * 3), ("nsf", 32, 0, [256, 256]), ("maf", 16, 0, [128, 128]),
                 ("nsf", 20, 3, [100, 72]), ("maf", 7, 2, [40]), ("nsf", 16, 2, [64, 64], "ELU"), ("maf", 12, 0, [48, 32], "Tanh")]
 
@@ -1194,12 +1264,14 @@ def test_wide_conditioners_run_fused(dev, D, ctx, hidden, monkeypatch):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,ctx,hidden,N", [(256, 0, [512] * 3, 300), (5, 3, [32, 32], 1000), (12, 2, [40, 70, 24], 77)])
-def test_fused_coupling_inverse(dev, D, ctx, hidden, N, monkeypatch):
+@pytest.mark.parametrize("precision", ["bf16x3", "f16x2"])
+def test_fused_coupling_inverse(dev, D, ctx, hidden, N, precision, monkeypatch, matmul):
     """zk_coupling_inverse (CouplingTransform._inverse, zuko/transforms.py:1050-1056, in one launch) against the layer-wise
     HIP inverse, the oracle's inverse and the round trip through the fused forward; `.inv.call_and_ladj` and
-    `rsample_and_log_prob` take x and the log-determinant from the same launch."""
+    `rsample_and_log_prob` take x and the log-determinant from the same launch.  precision: as in test_fused_coupling_kernel."""
     import zuko_amd.flows as F
 
+    matmul(precision)
     torch.manual_seed(D + N + 1)
     flow = F.RealNVP(D, ctx, transforms=3, hidden_features=hidden)
     sd = {k: v.detach().clone() for k, v in flow.state_dict().items() if v is not None}

@@ -252,18 +252,15 @@ class FusedCoupling:
         fn = _C.lib().zk_coupling_inverse if inverse else _C.lib().zk_coupling_forward
         from . import fused
 
+        # which stream the kernel reads: the two-part one (with its per-layer descale factors), the three-part one, or the f32 one
         if self.half_able and self.half_ok and self._half_stamp == self._stamp and fused.matmul_precision() == "f16x2":
             d = self.half_descale
-            a = _C.args("zk_coupling_args_v1", N=N, D=p.features, C=p.context, **{"in": _ptr(x)}, ldx=x.stride(0), ctx=_ptr(ctx), ldc=0 if ctx is None else ctx.stride(0), out=_ptr(y),
-                        ldy=p.features, ladj=_ptr(ladj), accumulate=0, wstream=_ptr(self.half_stream), bias=_ptr(self.bias), bias_floats=self.bias.numel(), bias_off=self.bias_off,
-                        amap=_ptr(self.amap), nit=p.nit, fmap=_ptr(self.fmap), n_groups=p.n_groups, n_layers=p.n_layers, tiles=self.tiles, widths=self.widths,
-                        n_chunks=2 * (len(p.split_gather) // 512) // HALF_CHUNK, act=self.act, slope=self.slope, static_ok=3, wdescale0=d[0], wdescale1=d[1], wdescale2=d[2], wdescale3=d[3])
-            _C.check(fn(a, _stream()), "zk_coupling_inverse" if inverse else "zk_coupling_forward")
-            return y, ladj
+            which = dict(wstream=_ptr(self.half_stream), n_chunks=2 * (len(p.split_gather) // 512) // HALF_CHUNK, static_ok=3, wdescale0=d[0], wdescale1=d[1], wdescale2=d[2], wdescale3=d[3])
+        else:
+            which = dict(wstream=_ptr(self.stream), n_chunks=p.split_chunks if self.split else p.n_chunks, static_ok=2 if self.split else 1)
         a = _C.args("zk_coupling_args_v1", N=N, D=p.features, C=p.context, **{"in": _ptr(x)}, ldx=x.stride(0), ctx=_ptr(ctx), ldc=0 if ctx is None else ctx.stride(0), out=_ptr(y),
-                    ldy=p.features, ladj=_ptr(ladj), accumulate=0, wstream=_ptr(self.stream), bias=_ptr(self.bias), bias_floats=self.bias.numel(), bias_off=self.bias_off,
+                    ldy=p.features, ladj=_ptr(ladj), accumulate=0, bias=_ptr(self.bias), bias_floats=self.bias.numel(), bias_off=self.bias_off,
                     amap=_ptr(self.amap), nit=p.nit, fmap=_ptr(self.fmap), n_groups=p.n_groups, n_layers=p.n_layers, tiles=self.tiles, widths=self.widths,
-                    n_chunks=p.split_chunks if self.split else p.n_chunks, act=self.act, slope=self.slope, static_ok=2 if self.split else 1)
-        err = fn(a, _stream())
-        _C.check(err, "zk_coupling_inverse" if inverse else "zk_coupling_forward")
+                    act=self.act, slope=self.slope, **which)
+        _C.check(fn(a, _stream()), "zk_coupling_inverse" if inverse else "zk_coupling_forward")
         return y, ladj

@@ -17,18 +17,14 @@
 //     place, and the image leaves as whole rows.
 // Host-side planning (stream order, bias image, index maps): zuko_amd/coupling_plan.py.
 #include "../../include/zuko_amd.h"
-#include "zk_univariate.h"
-
-#include <type_traits>
-#include <utility>
+#include "fused_ar_half_impl.h"  // what the autoregressive kernels already have: ArRingS, ars_for, ArLane, the raw LDS reads, arx_split, arh_scale, the vector types
 
 namespace zk {
 
-typedef float f32x4c __attribute__((ext_vector_type(4)));
-
 #define CP_T 32      /* activation tiles (hidden width <= 512) */
 #define CP_IT 16     /* input tiles (conditioner inputs <= 256) */
-#define CP_CH 24
+#define CP_CH 24     /* images per ring chunk: the f32 kernels and the three-part (bf16) one */
+#define CPH_CH 16    /* images per ring chunk of the two-part (f16) kernel */
 #define CP_NR 3
 #define CP_WAVES 4
 #define CP_MAXL 8
@@ -60,17 +56,8 @@ struct CpArgs {
   float wdescale[CP_MAXL];      // two-part (f16) kernel: 2^-ew of every linear layer, the power of two its weights were stored with
 };
 
-__device__ __attribute__((noinline)) float cp_act_slow(float v, int act) {
-  switch (act) {
-    case 2: return v > 0.f ? v : expm1f(v);
-    case 3: return tanhf(v);
-    case 4: return v / (1.f + expf(-v));
-    case 5: return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    case 6: return 1.f / (1.f + expf(-v));
-    case 7: return v > 0.f ? v : 0.01f * v;
-    default: return v;
-  }
-}
+// act_f32 as ONE out-of-line copy: inlined into the 128 values of cp_activate's unrolled tile loop it would not fit the instruction cache
+__device__ __attribute__((noinline)) float cp_act_slow(float v, int act) { return act_f32(v, act); }
 
 struct CpRing {
   float* lds;
@@ -104,7 +91,7 @@ struct CpRing {
   template <int G> __device__ __forceinline__ void begin() {
     if (pos == CP_CH) advance();
   }
-  __device__ __forceinline__ f32x4c tile(int t) const { return *reinterpret_cast<const f32x4c*>(lds + (slot * CP_CH + pos + t) * 256 + lane * 4); }
+  __device__ __forceinline__ f32x4 tile(int t) const { return *reinterpret_cast<const f32x4*>(lds + (slot * CP_CH + pos + t) * 256 + lane * 4); }
   template <int G> __device__ __forceinline__ void commit() { pos += G; }
   __device__ __forceinline__ void end_layer() {
     if (pos != 0) pos = CP_CH;
@@ -165,7 +152,7 @@ __device__ __forceinline__ void cp_store_rows(const CpArgs& a, const float* xw, 
   for (int r = 0; r < 16; ++r) {
       if (n0 + r < a.N)
 #pragma unroll 1
-        for (int c = lane * 4; c < a.D; c += 256) *reinterpret_cast<f32x4c*>(a.y + (n0 + r) * a.ldy + c) = *reinterpret_cast<const f32x4c*>(xw + r * xs + c);
+        for (int c = lane * 4; c < a.D; c += 256) *reinterpret_cast<f32x4*>(a.y + (n0 + r) * a.ldy + c) = *reinterpret_cast<const f32x4*>(xw + r * xs + c);
     }
   } else {
 #pragma unroll 1
@@ -179,12 +166,103 @@ __device__ __forceinline__ void cp_store_rows(const CpArgs& a, const float* xw, 
 
 extern __shared__ __attribute__((aligned(16))) float cp_lds[];
 
+// ---- the frame: everything of a coupling kernel that is not its matrix part -------------------------------------------------
+// LDS:  ring (CP_NR chunks) | bias image | amap (CP_IT * 16) | fmap (NG * 8) | layer words (3 * CP_MAXL: tiles, widths, bias offsets) | wave-private
+// row images (16 rows x xs floats per wavefront).  ONE definition for the kernels (the carved pointers) and for cp_launch (the size).
+struct CpLds {
+  float* bias;
+  int *amap, *fmap, *lay;
+  float* rows;  // this wavefront's image
+  static constexpr int bytes(int chunk, int bias_floats, int n_groups, int xs) {
+    return (CP_NR * chunk * 256 + bias_floats + CP_IT * 16 + n_groups * 8 + 3 * CP_MAXL + CP_WAVES * 16 * xs) * (int)sizeof(float);
+  }
+  __device__ __forceinline__ CpLds(const CpArgs& a, int chunk, int wave)
+      : bias(cp_lds + CP_NR * chunk * 256), amap(reinterpret_cast<int*>(bias + a.bias_floats)), fmap(amap + CP_IT * 16), lay(fmap + a.NG * 8),
+        rows(reinterpret_cast<float*>(lay + 3 * CP_MAXL) + (size_t)wave * 16 * a.xs) {}
+  // Cooperative copy of the launch's tables (the caller's ring start-up and workgroup barrier follow).  Per-layer scalars are read through LDS:
+  // indexing the by-value kernel argument arrays with a run-time layer index would make the compiler spill the whole argument block to scratch
+  // memory.  SHAPES: tiles and widths too (the generic kernel; the static-shape kernels have them as template parameters).
+  template <bool SHAPES> __device__ __forceinline__ void stage(const CpArgs& a, int tid, int nit) const {
+    if (tid == 0) {
+#pragma unroll
+      for (int l = 0; l < CP_MAXL; ++l) {
+        if constexpr (SHAPES) { lay[l] = a.wt[l]; lay[CP_MAXL + l] = a.width[l]; }
+        lay[2 * CP_MAXL + l] = a.bias_off[l];
+      }
+    }
+    for (int i = tid; i < a.bias_floats; i += 256) bias[i] = a.bias[i];
+    for (int i = tid; i < nit * 16; i += 256) amap[i] = a.amap[i];
+    for (int i = tid; i < a.NG * 8; i += 256) fmap[i] = a.fmap[i];
+  }
+  __device__ __forceinline__ int tiles_of(int l) const { return __builtin_amdgcn_readfirstlane(lay[l]); }
+  __device__ __forceinline__ int width_of(int l) const { return __builtin_amdgcn_readfirstlane(lay[CP_MAXL + l]); }
+  __device__ __forceinline__ const float* bias_of(int l, int q) const { return bias + __builtin_amdgcn_readfirstlane(lay[2 * CP_MAXL + l]) + 4 * q; }  // this lane's units of layer l
+};
+
+// B operand values of input tile `it` of the first layer: lane (j, q) gathers units 4 q .. 4 q + 3 from its row of the image through amap
+__device__ __forceinline__ f32x4 cp_gather_inputs(const CpArgs& a, const int* amap_lds, const float* xrow, int it, int q) {
+  f32x4 v;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int src = amap_lds[it * 16 + 4 * q + r];
+    v[r] = src >= 0 ? xrow[src] : (src <= -2 ? xrow[a.D + (-2 - src)] : 0.f);
+  }
+  return v;
+}
+
+// A group of 8 moved features: lane (j, q) owns slots 2 q and 2 q + 1.  Their columns and input values are requested before the group's matrix
+// instructions; cp_group_epilogue applies the two affine maps to p = (shift, scale) of slot 2 q, then of slot 2 q + 1, writes the results back
+// into the row image and adds the log-derivatives to lacc.
+struct CpSlots {
+  int f0, f1;
+  float x0, x1;
+  __device__ __forceinline__ CpSlots(const int* fmap_lds, const float* xrow, int g, int q)
+      : f0(fmap_lds[g * 8 + 2 * q]), f1(fmap_lds[g * 8 + 2 * q + 1]), x0(xrow[f0 < 0 ? 0 : f0]), x1(xrow[f1 < 0 ? 0 : f1]) {}
+};
+__device__ __forceinline__ void cp_group_epilogue(const CpArgs& a, const CpSlots& s, const f32x4& p, float* xrow, float& lacc) {
+  float y0, y1, l0, l1;
+  cp_affine(a, p[0], p[1], s.x0, y0, l0);
+  cp_affine(a, p[2], p[3], s.x1, y1, l1);
+  if (s.f0 >= 0) { xrow[s.f0] = y0; lacc += l0; }
+  if (s.f1 >= 0) { xrow[s.f1] = y1; lacc += l1; }
+}
+
+// End of a pass: the wave's image leaves as whole rows, the sample's log-derivative is summed over q (two shuffles) and stored
+__device__ __forceinline__ void cp_finish_rows(const CpArgs& a, const float* xw, int64_t n0, const ArLane& ln, float lacc) {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  cp_store_rows(a, xw, a.xs, n0, ln.lane);
+  if (a.ladj) {
+    const int64_t n = n0 + ln.j;
+    lacc += __shfl_xor(lacc, 16, 64);
+    lacc += __shfl_xor(lacc, 32, 64);
+    if (n < a.N && ln.q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The static-shape kernels read their weight images (and the split kernels their bias tiles) RAW: ArRingS::read, arx_lds_raw.  cp_settle<N> makes
+// such values usable: it waits until at most N younger LDS operations are outstanding and is the only consumer of the raw registers
+// (tests/test_codegen.py checks the ISA).  One overload per register set of a step: the images, or the images and the four bias tiles of an out-group.
+#define CP_S4(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])
+#define CP_S6(a) CP_S4(a), "+v"(a[4]), "+v"(a[5])
+#define CP_S8(a) CP_S6(a), "+v"(a[6]), "+v"(a[7])
+#define CP_S12(a) CP_S8(a), "+v"(a[8]), "+v"(a[9]), "+v"(a[10]), "+v"(a[11])
+#define CP_SO "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3)
+template <int N> __device__ __forceinline__ void cp_settle(f32x4 (&a)[4]) { asm volatile("s_waitcnt lgkmcnt(%4)" : CP_S4(a) : "n"(N)); }
+template <int N> __device__ __forceinline__ void cp_settle(f32x4 (&a)[6]) { asm volatile("s_waitcnt lgkmcnt(%6)" : CP_S6(a) : "n"(N)); }
+template <int N> __device__ __forceinline__ void cp_settle(f32x4 (&a)[8]) { asm volatile("s_waitcnt lgkmcnt(%8)" : CP_S8(a) : "n"(N)); }
+template <int N> __device__ __forceinline__ void cp_settle(f32x4 (&a)[12]) { asm volatile("s_waitcnt lgkmcnt(%12)" : CP_S12(a) : "n"(N)); }
+template <int N> __device__ __forceinline__ void cp_settle(f32x4 (&a)[8], f32x4& o0, f32x4& o1, f32x4& o2, f32x4& o3) { asm volatile("s_waitcnt lgkmcnt(%12)" : CP_S8(a), CP_SO : "n"(N)); }
+template <int N> __device__ __forceinline__ void cp_settle(f32x4 (&a)[12], f32x4& o0, f32x4& o1, f32x4& o2, f32x4& o3) { asm volatile("s_waitcnt lgkmcnt(%16)" : CP_S12(a), CP_SO : "n"(N)); }
+
 // 32 activation tiles as TWO arrays of 16: a single 512-byte array is not promoted to registers by the compiler (it stays in
 // scratch memory — measured 4x slower), two 256-byte ones are.  `t` is a compile-time constant at every use after unrolling.
 struct CpAct {
-  f32x4c (&lo)[16];
-  f32x4c (&hi)[16];
-  __device__ __forceinline__ f32x4c& operator[](int t) const { return t < 16 ? lo[t & 15] : hi[t & 15]; }
+  f32x4 (&lo)[16];
+  f32x4 (&hi)[16];
+  __device__ __forceinline__ f32x4& operator[](int t) const { return t < 16 ? lo[t & 15] : hi[t & 15]; }
 };
 
 // one dense layer: out[ot] = bias + sum_it W[ot, it] in[it]; NIN = static bound of the input tiles
@@ -193,12 +271,12 @@ template <int NIN> __device__ __forceinline__ void cp_layer(CpRing& ring, int n_
   for (int otg = 0; otg < CP_T / 4; ++otg) {
     if (otg * 4 < n_out) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t) out[otg * 4 + t] = *reinterpret_cast<const f32x4c*>(bias_q + (otg * 4 + t) * 16);
+      for (int t = 0; t < 4; ++t) out[otg * 4 + t] = *reinterpret_cast<const f32x4*>(bias_q + (otg * 4 + t) * 16);
 #pragma unroll
       for (int it = 0; it < NIN; ++it) {
         if (it < n_in) {
           ring.template begin<4>();
-          f32x4c a[4];
+          f32x4 a[4];
 #pragma unroll
           for (int t = 0; t < 4; ++t) a[t] = ring.tile(t);
           ring.template commit<4>();
@@ -234,6 +312,9 @@ __device__ __forceinline__ void cp_activate(const CpAct& h, int n_out, int width
   }
 }
 
+// (Of the frame this kernel takes CpSlots / cp_group_epilogue and, on the host, CpLds::bytes.  Its LDS carve and staging, its first-layer gather and
+//  its pass tail stay written out: at 512 registers with spills each of CpLds, cp_gather_inputs and cp_finish_rows moved its instruction census —
+//  64 LDS reads for the first two, one vector instruction for the third; profiles/coupling_frame/census.md.)
 __global__ __launch_bounds__(256, 1) void coupling_kernel(CpArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -276,13 +357,13 @@ __global__ __launch_bounds__(256, 1) void coupling_kernel(CpArgs a) {
     cp_stage_rows(a, xw, xs, n0, lane);
 
     // ---- first layer: B operands gathered from the image through idx_a ---------------------------------------------
-    f32x4c out_lo[16], out_hi[16], in_lo[16], in_hi[16];
+    f32x4 out_lo[16], out_hi[16], in_lo[16], in_hi[16];
     const CpAct out{out_lo, out_hi}, in{in_lo, in_hi};
 #pragma unroll
-    for (int it = 0; it < CP_T; ++it) in[it] = f32x4c{0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < CP_T; ++it) in[it] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int it = 0; it < CP_IT; ++it) {
-      f32x4c v = {0.f, 0.f, 0.f, 0.f};
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (it < a.nit) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -309,32 +390,26 @@ __global__ __launch_bounds__(256, 1) void coupling_kernel(CpArgs a) {
     const float* bias_last = bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + a.L - 1]) + 4 * q;
     float lacc = 0.f;
     for (int g = 0; g < a.NG; ++g) {
-      const int f0 = fmap_lds[g * 8 + 2 * q], f1 = fmap_lds[g * 8 + 2 * q + 1];
-      const float x0 = xrow[f0 < 0 ? 0 : f0], x1 = xrow[f1 < 0 ? 0 : f1];
-      f32x4c acc0 = *reinterpret_cast<const f32x4c*>(bias_last + g * 16), acc1 = {0.f, 0.f, 0.f, 0.f};  // two chains: a dependent one would wait 40 cycles per MFMA
+      const CpSlots slots(fmap_lds, xrow, g, q);
+      f32x4 acc0 = *reinterpret_cast<const f32x4*>(bias_last + g * 16), acc1 = {0.f, 0.f, 0.f, 0.f};  // two chains: a dependent one would wait 40 cycles per MFMA
 #pragma unroll
       for (int it = 0; it < CP_T; it += 2) {
         if (it < n_last_in) {
           ring.template begin<1>();
-          const f32x4c w0 = ring.tile(0);
+          const f32x4 w0 = ring.tile(0);
           ring.template commit<1>();
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[r], out[it][r], acc0, 0, 0, 0);
         }
         if (it + 1 < n_last_in) {
           ring.template begin<1>();
-          const f32x4c w1 = ring.tile(0);
+          const f32x4 w1 = ring.tile(0);
           ring.template commit<1>();
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[r], out[it + 1][r], acc1, 0, 0, 0);
         }
       }
-      const f32x4c p = acc0 + acc1;  // (shift, scale) of slot 2 q, then of slot 2 q + 1
-      float y0, y1, l0, l1;
-      cp_affine(a, p[0], p[1], x0, y0, l0);
-      cp_affine(a, p[2], p[3], x1, y1, l1);
-      if (f0 >= 0) { xrow[f0] = y0; lacc += l0; }
-      if (f1 >= 0) { xrow[f1] = y1; lacc += l1; }
+      cp_group_epilogue(a, slots, acc0 + acc1, xrow, lacc);
     }
     ring.end_layer();
     asm volatile("" ::: "memory");
@@ -358,96 +433,32 @@ __global__ __launch_bounds__(256, 1) void coupling_kernel(CpArgs a) {
 // groups): no per-tile guards, and the position of every weight tile inside the pass is a compile-time constant, so the ring
 // refill (barrier + DMA issue) is emitted only where that position is a multiple of the chunk size and the code between
 // two refills is one basic block the scheduler can software-pipeline (ds_read of the next tiles above the current MFMAs).
-#ifndef ZK_CP_ABLATE
-#define ZK_CP_ABLATE 0  // probe builds only (wrong results): 2 = no chunk barriers / refills, 4 = no row staging / stores, 8 = no s_barrier, 32 = no ring DMAs
-#endif
-#ifndef ZK_CP_TIMING
-#define ZK_CP_TIMING 0  // -DZK_CP_TIMING=1: s_memtime phase probes printed by wave 0 of block 0 (probe build only)
-#endif
-#define CP_ALWAYS_INLINE __attribute__((always_inline))
-template <class F, int... I> __device__ __forceinline__ void cp_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void cp_for(F&& f) { cp_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-struct CpRingS {
-  unsigned long long t_wait = 0, t_bar = 0, t_iss = 0;
-  float* lds;
-  const float* stream;
-  unsigned cur_off;  // LDS byte address of the slot being read + lane * 16
-  unsigned lds_off;  // LDS byte address of the ring
-  int n_chunks, slot, load_chunk, load_slot, wave, lane;
-  static constexpr int kPerWave = CP_CH / CP_WAVES;
-  static_assert(kPerWave == 6, "immediates -4096 .. +1024 around the wave's fifth tile reach six tiles");
-  // Each wave copies kPerWave consecutive tiles of a chunk, six DMAs back to back on ONE address / M0 value (that of its fifth
-  // tile) with the instruction's signed immediate offset: ~40 cycles of issue for the first, ~15 for each further one
-  // (scripts/probes/dma_issue_probe.hip).  Spreading them over the chunk (one per step) was measured: no better.
-  template <int I> __device__ __forceinline__ void dma(const float* g, float* l) {
-    if constexpr (I < kPerWave) {
-      if (!(ZK_CP_ABLATE & 32)) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, (I - 4) * 1024, 0);
-      dma<I + 1>(g, l);
-    }
-  }
-  __device__ __forceinline__ void issue() {
-    const int b4 = wave * kPerWave + 4;
-    dma<0>(stream + ((size_t)load_chunk * CP_CH + b4) * 256 + lane * 4, lds + (load_slot * CP_CH + b4) * 256);
-    load_chunk = (load_chunk + 1 == n_chunks) ? 0 : load_chunk + 1;
-    load_slot = (load_slot + 1 == CP_NR) ? 0 : load_slot + 1;
-  }
-  __device__ __forceinline__ void advance() {
-    unsigned long long p0 = 0, p1 = 0, p2 = 0;
-    if (ZK_CP_TIMING) p0 = __builtin_amdgcn_s_memtime();
-    // my DMAs of the chunk about to be read have landed (the CP_NR - 2 younger chunks stay in flight: a DMA takes ~5 k cycles,
-    // one chunk is consumed in ~3 k); my (prefetching) reads of the slot to be refilled have returned
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((CP_NR - 2) * (CP_CH / CP_WAVES)) : "memory");
-    if (ZK_CP_TIMING) p1 = __builtin_amdgcn_s_memtime();
-    if (!(ZK_CP_ABLATE & 8)) __builtin_amdgcn_s_barrier();  // bare barrier: __syncthreads() would prepend s_waitcnt vmcnt(0) and drain the look-ahead DMAs
-    asm volatile("" ::: "memory");
-    if (ZK_CP_TIMING) {
-      p2 = __builtin_amdgcn_s_memtime();
-      t_wait += p1 - p0; t_bar += p2 - p1;
-    }
-    issue();  // the slot just released
-    slot = (slot + 1 == CP_NR) ? 0 : slot + 1;
-    cur_off = lds_off + (unsigned)(slot * CP_CH * 1024 + lane * 16);
-  }
-  // Position S inside the layer (layers start on chunk boundaries; static).  The read is issued from inline assembly and returns
-  // a RAW value: the compiler does not know it is an LDS operation and inserts no wait for it — with a global_load_lds in flight
-  // hipcc turns every LDS wait into lgkmcnt(0), which would make a step wait for the tiles it has just requested for the NEXT
-  // step.  cp_settle<N>() makes the value usable: it waits until at most N younger LDS operations are outstanding (LDS
-  // operations of a wave complete in order) and is the only consumer of the raw registers (tests/test_codegen.py checks the ISA).
-  template <int S> __device__ __forceinline__ f32x4c read() {
-    if constexpr (S % CP_CH == 0) {
-      if (!(ZK_CP_ABLATE & 2)) advance();
-    }
-    f32x4c v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(cur_off), "n"((S % CP_CH) * 1024));
-    return v;
-  }
-};
-template <int N> __device__ __forceinline__ void cp_settle(f32x4c& a0, f32x4c& a1, f32x4c& a2, f32x4c& a3) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "n"(N));
-}
+// The ring is the autoregressive static-shape kernels' (fused_ar_static_impl.h): raw reads at static positions, refills where a position is a
+// multiple of the chunk size; its ablation switches (ARX_ABL 1: no DMAs, 4: no barrier) serve probe builds of these kernels too.
+typedef ArRingS<CP_WAVES, CP_CH, CP_NR> CpRingS;   // coupling_kernel_static, coupling_kernel_split
+typedef ArRingS<CP_WAVES, CPH_CH, CP_NR> CpRingH;  // coupling_kernel_half
 
 template <int NIN, int HT> __device__ __forceinline__ void cp_layer_static(CpRingS& ring, const float* bias_q, const CpAct& in, const CpAct& out) {
   // software pipeline: the four A tiles of step s + 1 are requested (into the other register set) before the 16 MFMAs of
   // step s are issued, so the LDS round trip hides behind 512 cycles of matrix work (one wavefront per SIMD: there is no
   // partner wave to hide it)
   constexpr int STEPS = (HT / 4) * NIN;
-  f32x4c a[2][4];
-  cp_for<4>([&](auto t) CP_ALWAYS_INLINE { a[0][t] = ring.template read<decltype(t)::value>(); });
-  cp_for<STEPS>([&](auto st_) CP_ALWAYS_INLINE {
+  f32x4 a[2][4];
+  ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { a[0][t] = ring.template read<decltype(t)::value>(); });
+  ars_for<STEPS>([&](auto st_) ARS_ALWAYS_INLINE {
     constexpr int st = st_, otg = st / NIN, it = st % NIN;
     if constexpr (it == 0) {
-      cp_for<4>([&](auto t) CP_ALWAYS_INLINE { out[otg * 4 + t] = *reinterpret_cast<const f32x4c*>(bias_q + (otg * 4 + t) * 16); });
+      ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { out[otg * 4 + t] = *reinterpret_cast<const f32x4*>(bias_q + (otg * 4 + t) * 16); });
     }
     if constexpr (st + 1 < STEPS) {
-      cp_for<4>([&](auto t) CP_ALWAYS_INLINE { a[(st + 1) & 1][t] = ring.template read<(st + 1) * 4 + decltype(t)::value>(); });
-      cp_settle<4>(a[st & 1][0], a[st & 1][1], a[st & 1][2], a[st & 1][3]);
+      ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { a[(st + 1) & 1][t] = ring.template read<(st + 1) * 4 + decltype(t)::value>(); });
+      cp_settle<4>(a[st & 1]);
     } else {
-      cp_settle<0>(a[st & 1][0], a[st & 1][1], a[st & 1][2], a[st & 1][3]);
+      cp_settle<0>(a[st & 1]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    cp_for<4>([&](auto r) CP_ALWAYS_INLINE {
-      cp_for<4>([&](auto t) CP_ALWAYS_INLINE { out[otg * 4 + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st & 1][t][(int)r], in[it][(int)r], out[otg * 4 + t], 0, 0, 0); });
+    ars_for<4>([&](auto r) ARS_ALWAYS_INLINE {
+      ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { out[otg * 4 + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st & 1][t][(int)r], in[it][(int)r], out[otg * 4 + t], 0, 0, 0); });
     });
     __builtin_amdgcn_sched_barrier(0);
   });
@@ -455,134 +466,73 @@ template <int NIN, int HT> __device__ __forceinline__ void cp_layer_static(CpRin
 
 template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_kernel_static(CpArgs a) {
   static_assert(HT % 4 == 0 && HT <= CP_T && NIT <= CP_IT, "shape");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int jl = lane & 15, q = lane >> 4;
-  float* bias_lds = cp_lds + CP_NR * CP_CH * 256;
-  int* amap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);
-  int* fmap_lds = amap_lds + CP_IT * 16;
-  int* lay_lds = fmap_lds + a.NG * 8;
-  float* xw = reinterpret_cast<float*>(lay_lds + 3 * CP_MAXL) + (size_t)wave * 16 * a.xs;
-  if (tid == 0) {
-#pragma unroll
-    for (int l = 0; l < CP_MAXL; ++l) lay_lds[2 * CP_MAXL + l] = a.bias_off[l];
-  }
-  for (int i = tid; i < a.bias_floats; i += 256) bias_lds[i] = a.bias[i];
-  for (int i = tid; i < NIT * 16; i += 256) amap_lds[i] = a.amap[i];
-  for (int i = tid; i < a.NG * 8; i += 256) fmap_lds[i] = a.fmap[i];
+  const ArLane ln;
+  const int lane = ln.lane, wave = ln.wave, q = ln.q;
+  const CpLds lds(a, CP_CH, wave);
+  lds.stage<false>(a, ln.tid, NIT);
   CpRingS ring;
-  ring.lds = cp_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
-#pragma unroll
-  for (int i = 0; i < CP_NR - 1; ++i) ring.issue();
-  ring.slot = CP_NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)cp_lds);
-  ring.cur_off = ring.lds_off;
+  ring.start(cp_lds, a.stream, a.n_chunks, wave, lane);
   __syncthreads();
 
-  const int xs = a.xs;
-  float* xrow = xw + jl * xs;
-  const int DC = a.D + a.C;
-  unsigned long long ts[6] = {0, 0, 0, 0, 0, 0}, tacc[5] = {0, 0, 0, 0, 0};
-  int n_pass = 0;
+  float* const xw = lds.rows;
+  float* const xrow = xw + ln.j * a.xs;
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int64_t n0 = tile * 64 + wave * 16;
-    const int64_t n = n0 + jl;
-    const bool live = n < a.N;
-    if (ZK_CP_TIMING) ts[0] = __builtin_amdgcn_s_memtime();
-    if (!(ZK_CP_ABLATE & 4)) cp_stage_rows(a, xw, xs, n0, lane);
-    if (ZK_CP_TIMING) ts[1] = __builtin_amdgcn_s_memtime();
+    cp_stage_rows(a, xw, a.xs, n0, lane);
 
-    f32x4c out_lo[16], out_hi[16], in_lo[16], in_hi[16];
+    f32x4 out_lo[16], out_hi[16], in_lo[16], in_hi[16];
     const CpAct out{out_lo, out_hi}, in{in_lo, in_hi};
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      f32x4c v;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int src = amap_lds[it * 16 + 4 * q + r];
-        v[r] = src >= 0 ? xrow[src] : (src <= -2 ? xrow[a.D + (-2 - src)] : 0.f);
-      }
-      in[it] = v;
-    }
-    cp_layer_static<NIT, HT>(ring, bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL]) + 4 * q, in, out);
+    for (int it = 0; it < NIT; ++it) in[it] = cp_gather_inputs(a, lds.amap, xrow, it, q);
+    cp_layer_static<NIT, HT>(ring, lds.bias_of(0, q), in, out);
 #pragma unroll
     for (int t = 0; t < HT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) out[t][r] = out[t][r] < 0.f ? 0.f : out[t][r];
-    if (ZK_CP_TIMING) ts[2] = __builtin_amdgcn_s_memtime();
     for (int l = 1; l < a.L - 1; ++l) {
 #pragma unroll
       for (int t = 0; t < HT; ++t) in[t] = out[t];
-      cp_layer_static<HT, HT>(ring, bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + l]) + 4 * q, in, out);
+      cp_layer_static<HT, HT>(ring, lds.bias_of(l, q), in, out);
 #pragma unroll
       for (int t = 0; t < HT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[t][r] = out[t][r] < 0.f ? 0.f : out[t][r];
     }
-    if (ZK_CP_TIMING) ts[3] = __builtin_amdgcn_s_memtime();
-    const float* bias_last = bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + a.L - 1]) + 4 * q;
+    const float* bias_last = lds.bias_of(a.L - 1, q);
     float lacc = 0.f;
-    // groups are walked in pairs so that the tile positions are static: 2 * HT tiles per pair (HT = 32: 64 tiles, not a
-    // multiple of the chunk — the position is carried in a run-time base that only changes by multiples of the chunk)
+    // groups are walked in triples so that the tile positions are static: HT tiles per group (HT = 32: not a multiple of the chunk), 3 * HT per triple
     static_assert((3 * HT) % CP_CH == 0, "three groups of the last layer must fill whole chunks");
     for (int g3 = 0; g3 < a.NG; g3 += 3) {
-      cp_for<3>([&](auto gg_) CP_ALWAYS_INLINE {
+      ars_for<3>([&](auto gg_) ARS_ALWAYS_INLINE {
         constexpr int gg = gg_;
         const int g = g3 + gg;
         if (g < a.NG) {
-          const int f0 = fmap_lds[g * 8 + 2 * q], f1 = fmap_lds[g * 8 + 2 * q + 1];
-          const float x0 = xrow[f0 < 0 ? 0 : f0], x1 = xrow[f1 < 0 ? 0 : f1];
+          const CpSlots slots(lds.fmap, xrow, g, q);
           // four accumulators (one per tile of the step): a dependent MFMA every fourth issue, as in the hidden layers
-          f32x4c acc[4] = {*reinterpret_cast<const f32x4c*>(bias_last + g * 16), {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-          f32x4c w[2][4];  // four tiles per step, the next step requested before this step's MFMAs
-          cp_for<4>([&](auto t) CP_ALWAYS_INLINE { w[0][t] = ring.template read<gg * HT + decltype(t)::value>(); });
-          cp_for<HT / 4>([&](auto k_) CP_ALWAYS_INLINE {
+          f32x4 acc[4] = {*reinterpret_cast<const f32x4*>(bias_last + g * 16), {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+          f32x4 w[2][4];  // four tiles per step, the next step requested before this step's MFMAs
+          ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { w[0][t] = ring.template read<gg * HT + decltype(t)::value>(); });
+          ars_for<HT / 4>([&](auto k_) ARS_ALWAYS_INLINE {
             constexpr int k = k_, it = 4 * k;
             if constexpr (it + 4 < HT) {
-              cp_for<4>([&](auto t) CP_ALWAYS_INLINE { w[(k + 1) & 1][t] = ring.template read<gg * HT + it + 4 + decltype(t)::value>(); });
-              cp_settle<4>(w[k & 1][0], w[k & 1][1], w[k & 1][2], w[k & 1][3]);
+              ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { w[(k + 1) & 1][t] = ring.template read<gg * HT + it + 4 + decltype(t)::value>(); });
+              cp_settle<4>(w[k & 1]);
             } else {
-              cp_settle<0>(w[k & 1][0], w[k & 1][1], w[k & 1][2], w[k & 1][3]);
+              cp_settle<0>(w[k & 1]);
             }
             __builtin_amdgcn_sched_barrier(0);
-            cp_for<4>([&](auto r) CP_ALWAYS_INLINE {
-              cp_for<4>([&](auto t) CP_ALWAYS_INLINE { acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[k & 1][t][(int)r], out[it + t][(int)r], acc[t], 0, 0, 0); });
+            ars_for<4>([&](auto r) ARS_ALWAYS_INLINE {
+              ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[k & 1][t][(int)r], out[it + t][(int)r], acc[t], 0, 0, 0); });
             });
             __builtin_amdgcn_sched_barrier(0);
           });
-          const f32x4c p = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-          float y0, y1, l0, l1;
-          cp_affine(a, p[0], p[1], x0, y0, l0);
-          cp_affine(a, p[2], p[3], x1, y1, l1);
-          if (f0 >= 0) { xrow[f0] = y0; lacc += l0; }
-          if (f1 >= 0) { xrow[f1] = y1; lacc += l1; }
+          cp_group_epilogue(a, slots, (acc[0] + acc[1]) + (acc[2] + acc[3]), xrow, lacc);
         }
       });
     }
-    if (ZK_CP_TIMING) ts[4] = __builtin_amdgcn_s_memtime();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    if (!(ZK_CP_ABLATE & 4)) cp_store_rows(a, xw, xs, n0, lane);
-    if (a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    if (ZK_CP_TIMING) {
-      ts[5] = __builtin_amdgcn_s_memtime();
-      for (int i = 0; i < 5; ++i) tacc[i] += ts[i + 1] - ts[i];
-      ++n_pass;
-    }
+    cp_finish_rows(a, xw, n0, ln, lacc);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if ZK_CP_TIMING
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    printf("cp timing (memtime ticks, %d passes): stage %llu layer0 %llu hidden %llu last %llu store %llu | advance: wait %llu barrier %llu issue %llu\n", n_pass,
-           tacc[0], tacc[1], tacc[2], tacc[3], tacc[4], ring.t_wait, ring.t_bar, ring.t_iss);
-#endif
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
 
 // ---- operand-split twin of the static-shape path ----------------------------------------------------------------------------------
@@ -594,109 +544,75 @@ template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_ke
 // the accumulator registers, so a layer's D fragments become the next layer's B operands by an in-register conversion.  One
 // wavefront per SIMD: a step is 4 out tiles x 1 in pair (12 images, 24 matrix instructions issued term by term, so the same
 // accumulator is touched every fourth instruction and never waits for its predecessor).
-typedef __bf16 cbf16x8 __attribute__((ext_vector_type(8)));
 struct CpBv {  // B operands (h, m, l parts) of 16 activation pairs, as arrays small enough to be promoted to registers
-  cbf16x8 (&hlo)[8]; cbf16x8 (&hhi)[8]; cbf16x8 (&mlo)[8]; cbf16x8 (&mhi)[8]; cbf16x8 (&llo)[8]; cbf16x8 (&lhi)[8];
-  __device__ __forceinline__ cbf16x8& h(int p) const { return p < 8 ? hlo[p & 7] : hhi[p & 7]; }
-  __device__ __forceinline__ cbf16x8& m(int p) const { return p < 8 ? mlo[p & 7] : mhi[p & 7]; }
-  __device__ __forceinline__ cbf16x8& l(int p) const { return p < 8 ? llo[p & 7] : lhi[p & 7]; }
-};
-__device__ __forceinline__ void cp_split(const f32x4c& lo, const f32x4c& hi, cbf16x8& h, cbf16x8& m, cbf16x8& l) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = e < 4 ? lo[e] : hi[e - 4];
-    const __bf16 hh = (__bf16)v;
-    const float r1 = v - (float)hh;
-    const __bf16 mm = (__bf16)r1;
-    h[e] = hh; m[e] = mm; l[e] = (__bf16)(r1 - (float)mm);
+  bf16x8 (&hlo)[8]; bf16x8 (&hhi)[8]; bf16x8 (&mlo)[8]; bf16x8 (&mhi)[8]; bf16x8 (&llo)[8]; bf16x8 (&lhi)[8];
+  __device__ __forceinline__ bf16x8& h(int p) const { return p < 8 ? hlo[p & 7] : hhi[p & 7]; }
+  __device__ __forceinline__ bf16x8& m(int p) const { return p < 8 ? mlo[p & 7] : mhi[p & 7]; }
+  __device__ __forceinline__ bf16x8& l(int p) const { return p < 8 ? llo[p & 7] : lhi[p & 7]; }
+  __device__ __forceinline__ void split(int p, const f32x4& lo, const f32x4& hi) const {  // pair p = arx_split of two activation tiles
+    ArxB b;
+    arx_split(lo, hi, b);
+    h(p) = b.h; m(p) = b.m; l(p) = b.l;
   }
-}
-template <int N> __device__ __forceinline__ void cp_settle12(f32x4c (&a)[12]) {
-  asm volatile("s_waitcnt lgkmcnt(%12)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]), "+v"(a[9]), "+v"(a[10]), "+v"(a[11]) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void cp_settle6(f32x4c (&a)[6]) {
-  asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]) : "n"(N));
-}
-// the step's images together with the four bias tiles of an out-group's first step (read raw in front of the look-ahead images: see cp_layer_split)
-template <int N> __device__ __forceinline__ void cp_settle12o(f32x4c (&a)[12], f32x4c& o0, f32x4c& o1, f32x4c& o2, f32x4c& o3) {
-  asm volatile("s_waitcnt lgkmcnt(%16)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]), "+v"(a[9]), "+v"(a[10]), "+v"(a[11]),
-               "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3) : "n"(N));
-}
-template <int OFF> __device__ __forceinline__ f32x4c cp_lds_raw(unsigned addr) {
-  f32x4c v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-#define CP_XMFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cbf16x8, A), B, C, 0, 0, 0)
+};
 
 // one dense layer: out[ot] = bias + sum_ip W[ot, ip] in[ip]; NP in pairs, HT out tiles
 template <int NP, int HT> __device__ __forceinline__ void cp_layer_split(CpRingS& ring, const float* bias_q, const CpBv& in, const CpAct& out) {
   constexpr int STEPS = (HT / 4) * NP;
-  f32x4c a[2][12];  // images (t, part) of the step: a[.][3 t + part], part 0 = h, 1 = m, 2 = l
-  cp_for<12>([&](auto i) CP_ALWAYS_INLINE { a[0][i] = ring.template read<decltype(i)::value>(); });
+  f32x4 a[2][12];  // images (t, part) of the step: a[.][3 t + part], part 0 = h, 1 = m, 2 = l
+  ars_for<12>([&](auto i) ARS_ALWAYS_INLINE { a[0][i] = ring.template read<decltype(i)::value>(); });
   // The out-group's accumulators start at the bias, read RAW in front of the next step's images: older than those twelve, the counted wait of the
   // step settles them too.  (As compiler-visible loads their wait was lgkmcnt(0) — the compiler cannot count the raw reads — in front of the group's
   // first matrix instruction: the twelve look-ahead images drained with it, once per out-group, with no second wavefront on the SIMD to hide it.)
-  const unsigned bias_addr = (unsigned)(size_t)((const __attribute__((address_space(3))) float*)bias_q);
-  cp_for<STEPS>([&](auto st_) CP_ALWAYS_INLINE {
+  const unsigned bias_addr = arx_lds_addr(bias_q);
+  ars_for<STEPS>([&](auto st_) ARS_ALWAYS_INLINE {
     constexpr int st = st_, otg = st / NP, ip = st % NP;
     if constexpr (ip == 0) {
-      cp_for<4>([&](auto t) CP_ALWAYS_INLINE { out[otg * 4 + t] = cp_lds_raw<(otg * 4 + decltype(t)::value) * 64>(bias_addr); });
+      ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { out[otg * 4 + t] = arx_lds_raw<(otg * 4 + decltype(t)::value) * 64>(bias_addr); });
     }
     if constexpr (st + 1 < STEPS) {
-      cp_for<12>([&](auto i) CP_ALWAYS_INLINE { a[(st + 1) & 1][i] = ring.template read<(st + 1) * 12 + decltype(i)::value>(); });
-      if constexpr (ip == 0) cp_settle12o<12>(a[st & 1], out[otg * 4 + 0], out[otg * 4 + 1], out[otg * 4 + 2], out[otg * 4 + 3]);
-      else cp_settle12<12>(a[st & 1]);
+      ars_for<12>([&](auto i) ARS_ALWAYS_INLINE { a[(st + 1) & 1][i] = ring.template read<(st + 1) * 12 + decltype(i)::value>(); });
+      if constexpr (ip == 0) cp_settle<12>(a[st & 1], out[otg * 4 + 0], out[otg * 4 + 1], out[otg * 4 + 2], out[otg * 4 + 3]);
+      else cp_settle<12>(a[st & 1]);
     } else {
-      if constexpr (ip == 0) cp_settle12o<0>(a[st & 1], out[otg * 4 + 0], out[otg * 4 + 1], out[otg * 4 + 2], out[otg * 4 + 3]);
-      else cp_settle12<0>(a[st & 1]);
+      if constexpr (ip == 0) cp_settle<0>(a[st & 1], out[otg * 4 + 0], out[otg * 4 + 1], out[otg * 4 + 2], out[otg * 4 + 3]);
+      else cp_settle<0>(a[st & 1]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    const cbf16x8 bh = in.h(ip), bm = in.m(ip), bl = in.l(ip);
+    const bf16x8 bh = in.h(ip), bm = in.m(ip), bl = in.l(ip);
     // six partial products, smallest first, each over the four out tiles of the step
-    cp_for<4>([&](auto t) CP_ALWAYS_INLINE { CP_XMFMA(a[st & 1][3 * t + 2], bh, out[otg * 4 + t]); });
-    cp_for<4>([&](auto t) CP_ALWAYS_INLINE { CP_XMFMA(a[st & 1][3 * t + 0], bl, out[otg * 4 + t]); });
-    cp_for<4>([&](auto t) CP_ALWAYS_INLINE { CP_XMFMA(a[st & 1][3 * t + 1], bm, out[otg * 4 + t]); });
-    cp_for<4>([&](auto t) CP_ALWAYS_INLINE { CP_XMFMA(a[st & 1][3 * t + 1], bh, out[otg * 4 + t]); });
-    cp_for<4>([&](auto t) CP_ALWAYS_INLINE { CP_XMFMA(a[st & 1][3 * t + 0], bm, out[otg * 4 + t]); });
-    cp_for<4>([&](auto t) CP_ALWAYS_INLINE { CP_XMFMA(a[st & 1][3 * t + 0], bh, out[otg * 4 + t]); });
+    ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { ARX_MFMA(a[st & 1][3 * t + 2], bh, out[otg * 4 + t]); });
+    ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { ARX_MFMA(a[st & 1][3 * t + 0], bl, out[otg * 4 + t]); });
+    ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { ARX_MFMA(a[st & 1][3 * t + 1], bm, out[otg * 4 + t]); });
+    ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { ARX_MFMA(a[st & 1][3 * t + 1], bh, out[otg * 4 + t]); });
+    ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { ARX_MFMA(a[st & 1][3 * t + 0], bm, out[otg * 4 + t]); });
+    ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { ARX_MFMA(a[st & 1][3 * t + 0], bh, out[otg * 4 + t]); });
     __builtin_amdgcn_sched_barrier(0);
   });
 }
 
 // ReLU + conversion of the HT out tiles into the next layer's B operands
 template <int HT> __device__ __forceinline__ void cp_convert(const CpAct& out, const CpBv& in) {
-  cp_for<HT / 2>([&](auto p_) CP_ALWAYS_INLINE {
+  ars_for<HT / 2>([&](auto p_) ARS_ALWAYS_INLINE {
     constexpr int p = p_;
-    f32x4c lo = out[2 * p], hi = out[2 * p + 1];
+    f32x4 lo = out[2 * p], hi = out[2 * p + 1];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       lo[r] = lo[r] < 0.f ? 0.f : lo[r];  // NaN stays NaN, as torch.relu
       hi[r] = hi[r] < 0.f ? 0.f : hi[r];
     }
-    cp_split(lo, hi, in.h(p), in.m(p), in.l(p));
+    in.split(p, lo, hi);
   });
 }
 
 template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_kernel_split(CpArgs a) {
   static_assert(HT % 4 == 0 && HT <= CP_T && NIT <= CP_IT && NIT % 2 == 0 && (12 * (NIT / 2) * (HT / 4)) % CP_CH == 0 && (12 * (HT / 2) * (HT / 4)) % CP_CH == 0 && (3 * (HT / 2)) % CP_CH == 0,
                 "every layer and every group of the last layer fills whole chunks");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int jl = lane & 15, q = lane >> 4;
-  float* bias_lds = cp_lds + CP_NR * CP_CH * 256;
-  int* amap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);
-  int* fmap_lds = amap_lds + CP_IT * 16;
-  int* lay_lds = fmap_lds + a.NG * 8;
-  float* xw = reinterpret_cast<float*>(lay_lds + 3 * CP_MAXL) + (size_t)wave * 16 * a.xs;
-  if (tid == 0) {
-#pragma unroll
-    for (int l = 0; l < CP_MAXL; ++l) lay_lds[2 * CP_MAXL + l] = a.bias_off[l];
-  }
-  for (int i = tid; i < a.bias_floats; i += 256) bias_lds[i] = a.bias[i];
-  for (int i = tid; i < NIT * 16; i += 256) amap_lds[i] = a.amap[i];
-  for (int i = tid; i < a.NG * 8; i += 256) fmap_lds[i] = a.fmap[i];
-  CpRingS ring;
+  const ArLane ln;
+  const int lane = ln.lane, wave = ln.wave, q = ln.q;
+  const CpLds lds(a, CP_CH, wave);
+  lds.stage<false>(a, ln.tid, NIT);
+  CpRingS ring;  // (start-up written out: as ArRingS::start this kernel gains 8 registers and 27 vector instructions, profiles/coupling_frame/census.md)
   ring.lds = cp_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
   ring.load_chunk = 0; ring.load_slot = 0;
 #pragma unroll
@@ -706,85 +622,61 @@ template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_ke
   ring.cur_off = ring.lds_off;
   __syncthreads();
 
-  const int xs = a.xs;
-  float* xrow = xw + jl * xs;
+  float* const xw = lds.rows;
+  float* const xrow = xw + ln.j * a.xs;
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int64_t n0 = tile * 64 + wave * 16;
-    const int64_t n = n0 + jl;
-    const bool live = n < a.N;
-    cp_stage_rows(a, xw, xs, n0, lane);
+    cp_stage_rows(a, xw, a.xs, n0, lane);
 
-    f32x4c out_lo[16], out_hi[16];
-    cbf16x8 bhl[8], bhh[8], bml[8], bmh[8], bll[8], blh[8];
+    f32x4 out_lo[16], out_hi[16];
+    bf16x8 bhl[8], bhh[8], bml[8], bmh[8], bll[8], blh[8];
     const CpAct out{out_lo, out_hi};
     const CpBv in{bhl, bhh, bml, bmh, bll, blh};
     // first layer: B operands gathered from the row image through idx_a, converted pair by pair
-    cp_for<NIT / 2>([&](auto p_) CP_ALWAYS_INLINE {
+    ars_for<NIT / 2>([&](auto p_) ARS_ALWAYS_INLINE {
       constexpr int p = p_;
-      f32x4c v[2];
-#pragma unroll
-      for (int hlf = 0; hlf < 2; ++hlf)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int src = amap_lds[(2 * p + hlf) * 16 + 4 * q + r];
-          v[hlf][r] = src >= 0 ? xrow[src] : (src <= -2 ? xrow[a.D + (-2 - src)] : 0.f);
-        }
-      cp_split(v[0], v[1], in.h(p), in.m(p), in.l(p));
+      const f32x4 lo = cp_gather_inputs(a, lds.amap, xrow, 2 * p, q), hi = cp_gather_inputs(a, lds.amap, xrow, 2 * p + 1, q);
+      in.split(p, lo, hi);
     });
-    cp_layer_split<NIT / 2, HT>(ring, bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL]) + 4 * q, in, out);
+    cp_layer_split<NIT / 2, HT>(ring, lds.bias_of(0, q), in, out);
     cp_convert<HT>(out, in);
     for (int l = 1; l < a.L - 1; ++l) {
-      cp_layer_split<HT / 2, HT>(ring, bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + l]) + 4 * q, in, out);
+      cp_layer_split<HT / 2, HT>(ring, lds.bias_of(l, q), in, out);
       cp_convert<HT>(out, in);
     }
     // last layer + affine map: one group of 8 moved features = one out tile = HT / 2 blocks, two blocks per step on six accumulators
-    const float* bias_last = bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + a.L - 1]) + 4 * q;
+    const float* bias_last = lds.bias_of(a.L - 1, q);
     float lacc = 0.f;
     for (int g = 0; g < a.NG; ++g) {
-      const int f0 = fmap_lds[g * 8 + 2 * q], f1 = fmap_lds[g * 8 + 2 * q + 1];
-      const float x0 = xrow[f0 < 0 ? 0 : f0], x1 = xrow[f1 < 0 ? 0 : f1];
-      const f32x4c zero = {0.f, 0.f, 0.f, 0.f};
-      f32x4c cH[2] = {*reinterpret_cast<const f32x4c*>(bias_last + g * 16), zero}, cM[2] = {zero, zero}, cS[2] = {zero, zero};
-      f32x4c w[2][6];  // images of the step's two blocks: w[.][3 b + part]
+      const CpSlots slots(lds.fmap, xrow, g, q);
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+      f32x4 cH[2] = {*reinterpret_cast<const f32x4*>(bias_last + g * 16), zero}, cM[2] = {zero, zero}, cS[2] = {zero, zero};
+      f32x4 w[2][6];  // images of the step's two blocks: w[.][3 b + part]
       constexpr int KS = HT / 4;  // steps per group
-      cp_for<6>([&](auto i) CP_ALWAYS_INLINE { w[0][i] = ring.template read<decltype(i)::value>(); });
-      cp_for<KS>([&](auto k_) CP_ALWAYS_INLINE {
+      ars_for<6>([&](auto i) ARS_ALWAYS_INLINE { w[0][i] = ring.template read<decltype(i)::value>(); });
+      ars_for<KS>([&](auto k_) ARS_ALWAYS_INLINE {
         constexpr int k = k_;
         if constexpr (k + 1 < KS) {
-          cp_for<6>([&](auto i) CP_ALWAYS_INLINE { w[(k + 1) & 1][i] = ring.template read<(k + 1) * 6 + decltype(i)::value>(); });
-          cp_settle6<6>(w[k & 1]);
+          ars_for<6>([&](auto i) ARS_ALWAYS_INLINE { w[(k + 1) & 1][i] = ring.template read<(k + 1) * 6 + decltype(i)::value>(); });
+          cp_settle<6>(w[k & 1]);
         } else {
-          cp_settle6<0>(w[k & 1]);
+          cp_settle<0>(w[k & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        cp_for<2>([&](auto b) CP_ALWAYS_INLINE { CP_XMFMA(w[k & 1][3 * b + 2], in.h(2 * k + b), cS[b]); });
-        cp_for<2>([&](auto b) CP_ALWAYS_INLINE { CP_XMFMA(w[k & 1][3 * b + 1], in.h(2 * k + b), cM[b]); });
-        cp_for<2>([&](auto b) CP_ALWAYS_INLINE { CP_XMFMA(w[k & 1][3 * b + 0], in.h(2 * k + b), cH[b]); });
-        cp_for<2>([&](auto b) CP_ALWAYS_INLINE { CP_XMFMA(w[k & 1][3 * b + 0], in.l(2 * k + b), cS[b]); });
-        cp_for<2>([&](auto b) CP_ALWAYS_INLINE { CP_XMFMA(w[k & 1][3 * b + 0], in.m(2 * k + b), cM[b]); });
-        cp_for<2>([&](auto b) CP_ALWAYS_INLINE { CP_XMFMA(w[k & 1][3 * b + 1], in.m(2 * k + b), cS[b]); });
+        ars_for<2>([&](auto b) ARS_ALWAYS_INLINE { ARX_MFMA(w[k & 1][3 * b + 2], in.h(2 * k + b), cS[b]); });
+        ars_for<2>([&](auto b) ARS_ALWAYS_INLINE { ARX_MFMA(w[k & 1][3 * b + 1], in.h(2 * k + b), cM[b]); });
+        ars_for<2>([&](auto b) ARS_ALWAYS_INLINE { ARX_MFMA(w[k & 1][3 * b + 0], in.h(2 * k + b), cH[b]); });
+        ars_for<2>([&](auto b) ARS_ALWAYS_INLINE { ARX_MFMA(w[k & 1][3 * b + 0], in.l(2 * k + b), cS[b]); });
+        ars_for<2>([&](auto b) ARS_ALWAYS_INLINE { ARX_MFMA(w[k & 1][3 * b + 0], in.m(2 * k + b), cM[b]); });
+        ars_for<2>([&](auto b) ARS_ALWAYS_INLINE { ARX_MFMA(w[k & 1][3 * b + 1], in.m(2 * k + b), cS[b]); });
         __builtin_amdgcn_sched_barrier(0);
       });
-      asm volatile("s_nop 15" : "+v"(cS[1]));  // wait states behind the group's last matrix instruction: one wavefront per SIMD, accumulators may sit in AGPRs (csrc/fused_ar_split_impl.h: arx_mfma_guard)
-      const f32x4c p = ((cS[0] + cS[1]) + (cM[0] + cM[1])) + (cH[0] + cH[1]);  // (shift, scale) of slot 2 q, then of slot 2 q + 1
-      float y0, y1, l0, l1;
-      cp_affine(a, p[0], p[1], x0, y0, l0);
-      cp_affine(a, p[2], p[3], x1, y1, l1);
-      if (f0 >= 0) { xrow[f0] = y0; lacc += l0; }
-      if (f1 >= 0) { xrow[f1] = y1; lacc += l1; }
+      arx_mfma_guard<true>(cS[1]);  // wait states behind the group's last matrix instruction: one wavefront per SIMD, accumulators may sit in AGPRs
+      cp_group_epilogue(a, slots, ((cS[0] + cS[1]) + (cM[0] + cM[1])) + (cH[0] + cH[1]), xrow, lacc);
     }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    cp_store_rows(a, xw, xs, n0, lane);
-    if (a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    cp_finish_rows(a, xw, n0, ln, lacc);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
 
 
@@ -796,47 +688,13 @@ template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_ke
 // One wavefront per SIMD, more than 256 registers: the accumulators of a step are pinned to VGPRs and the step's matrix instructions are ONE
 // assembly block (hipcc under-counts the wait states behind a v_mfma_f32_16x16x32_f16 whose destination is an AGPR: profiles/r06/inverse.md),
 // with 12 wait states in front of the vector instructions that read them.
-typedef _Float16 cf16x8 __attribute__((ext_vector_type(8)));
-#define CPH_CH 16
-struct CpRingH {
-  float* lds;
-  const float* stream;
-  unsigned cur_off, lds_off;
-  int n_chunks, slot, load_chunk, load_slot, wave, lane;
-  static constexpr int kPerWave = CPH_CH / CP_WAVES;
-  template <int I> __device__ __forceinline__ void dma(const float* g, float* l) {
-    if constexpr (I < kPerWave) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, (I - 2) * 1024, 0);
-      dma<I + 1>(g, l);
-    }
-  }
-  __device__ __forceinline__ void issue() {
-    const int b2 = wave * kPerWave + 2;
-    dma<0>(stream + ((size_t)load_chunk * CPH_CH + b2) * 256 + lane * 4, lds + (load_slot * CPH_CH + b2) * 256);
-    load_chunk = (load_chunk + 1 == n_chunks) ? 0 : load_chunk + 1;
-    load_slot = (load_slot + 1 == CP_NR) ? 0 : load_slot + 1;
-  }
-  __device__ __forceinline__ void advance() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((CP_NR - 2) * (CPH_CH / CP_WAVES)) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    issue();
-    slot = (slot + 1 == CP_NR) ? 0 : slot + 1;
-    cur_off = lds_off + (unsigned)(slot * CPH_CH * 1024 + lane * 16);
-  }
-  template <int S> __device__ __forceinline__ f32x4c read() {
-    if constexpr (S % CPH_CH == 0) advance();
-    f32x4c v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(cur_off), "n"((S % CPH_CH) * 1024));
-    return v;
-  }
-};
 struct CpBh {  // B operands (h, l parts) of 16 activation pairs
-  cf16x8 (&hlo)[8]; cf16x8 (&hhi)[8]; cf16x8 (&llo)[8]; cf16x8 (&lhi)[8];
-  __device__ __forceinline__ cf16x8& h(int p) const { return p < 8 ? hlo[p & 7] : hhi[p & 7]; }
-  __device__ __forceinline__ cf16x8& l(int p) const { return p < 8 ? llo[p & 7] : lhi[p & 7]; }
+  f16x8 (&hlo)[8]; f16x8 (&hhi)[8]; f16x8 (&llo)[8]; f16x8 (&lhi)[8];
+  __device__ __forceinline__ f16x8& h(int p) const { return p < 8 ? hlo[p & 7] : hhi[p & 7]; }
+  __device__ __forceinline__ f16x8& l(int p) const { return p < 8 ? llo[p & 7] : lhi[p & 7]; }
 };
-__device__ __forceinline__ void cph_split(const f32x4c& lo, const f32x4c& hi, float s, cf16x8& h, cf16x8& l) {
+// (plain expressions: arh_split's pinned instruction pairs are another instruction sequence)
+__device__ __forceinline__ void cph_split(const f32x4& lo, const f32x4& hi, float s, f16x8& h, f16x8& l) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float v = (e < 4 ? lo[e] : hi[e - 4]) * s;
@@ -844,25 +702,9 @@ __device__ __forceinline__ void cph_split(const f32x4c& lo, const f32x4c& hi, fl
     h[e] = hh; l[e] = (_Float16)(v - (float)hh);
   }
 }
-// s = 2^ea with amax 2^ea in [2^14, 2^15) (|ea| <= 90; zero / non-finite amax: ea = 15), inv_s = 2^-ea   (arh_scale of fused_ar_half_impl.h)
-__device__ __forceinline__ void cph_scale(float amax, float& s, float& inv_s) {
-  amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-  amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-  int ea = 15 - __builtin_amdgcn_frexp_expf(amax);
-  ea = ea > 90 ? 90 : (ea < -90 ? -90 : ea);
-  s = __builtin_amdgcn_ldexpf(1.0f, ea);
-  inv_s = __builtin_amdgcn_ldexpf(1.0f, -ea);
-}
-template <int N> __device__ __forceinline__ void cph_settle8(f32x4c (&a)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void cph_settle8o(f32x4c (&a)[8], f32x4c& o0, f32x4c& o1, f32x4c& o2, f32x4c& o3) {
-  asm volatile("s_waitcnt lgkmcnt(%12)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void cph_settle4(f32x4c (&a)[4]) { asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "n"(N)); }
 // the twelve matrix instructions of a step (4 out tiles x 3 partial products, term by term: an accumulator is touched every fourth instruction),
 // images a[2 t] = h, a[2 t + 1] = l of out tile t; FIRST: the accumulators start at zero; LAST: wait states for the vector instructions that follow
-template <bool FIRST, bool LAST> __device__ __forceinline__ void cph_step(f32x4c (&acc)[4], f32x4c (&a)[8], const cf16x8& bh, const cf16x8& bl) {
+template <bool FIRST, bool LAST> __device__ __forceinline__ void cph_step(f32x4 (&acc)[4], f32x4 (&a)[8], const f16x8& bh, const f16x8& bl) {
   if constexpr (FIRST) {
     asm volatile("s_nop 1\n\t"
                  "v_mfma_f32_16x16x32_f16 %0, %5, %12, 0\n\tv_mfma_f32_16x16x32_f16 %1, %7, %12, 0\n\tv_mfma_f32_16x16x32_f16 %2, %9, %12, 0\n\tv_mfma_f32_16x16x32_f16 %3, %11, %12, 0\n\t"
@@ -884,29 +726,29 @@ template <bool FIRST, bool LAST> __device__ __forceinline__ void cph_step(f32x4c
 // one dense layer: out[ot] = fma(W' in', d, bias) over (4 out tiles, 1 in pair) steps; NP in pairs, HT out tiles
 template <int NP, int HT> __device__ __forceinline__ void cph_layer(CpRingH& ring, const float* bias_q, const CpBh& in, const CpAct& out, float d) {
   constexpr int STEPS = (HT / 4) * NP;
-  f32x4c a[2][8];
-  f32x4c acc[4], bs[4];
-  cp_for<8>([&](auto i) CP_ALWAYS_INLINE { a[0][i] = ring.template read<decltype(i)::value>(); });
-  const unsigned bias_addr = (unsigned)(size_t)((const __attribute__((address_space(3))) float*)bias_q);
-  cp_for<STEPS>([&](auto st_) CP_ALWAYS_INLINE {
+  f32x4 a[2][8];
+  f32x4 acc[4], bs[4];
+  ars_for<8>([&](auto i) ARS_ALWAYS_INLINE { a[0][i] = ring.template read<decltype(i)::value>(); });
+  const unsigned bias_addr = arx_lds_addr(bias_q);
+  ars_for<STEPS>([&](auto st_) ARS_ALWAYS_INLINE {
     constexpr int st = st_, otg = st / NP, ip = st % NP;
     constexpr bool first = ip == 0, last = ip == NP - 1;
     if constexpr (last) {  // the out-group's bias tiles: raw reads in front of the look-ahead request of the group's LAST step, whose counted wait settles them
-      cp_for<4>([&](auto t) CP_ALWAYS_INLINE { bs[t] = cp_lds_raw<(otg * 4 + decltype(t)::value) * 64>(bias_addr); });
+      ars_for<4>([&](auto t) ARS_ALWAYS_INLINE { bs[t] = arx_lds_raw<(otg * 4 + decltype(t)::value) * 64>(bias_addr); });
     }
     if constexpr (st + 1 < STEPS) {
-      cp_for<8>([&](auto i) CP_ALWAYS_INLINE { a[(st + 1) & 1][i] = ring.template read<(st + 1) * 8 + decltype(i)::value>(); });
-      if constexpr (last) cph_settle8o<8>(a[st & 1], bs[0], bs[1], bs[2], bs[3]);
-      else cph_settle8<8>(a[st & 1]);
+      ars_for<8>([&](auto i) ARS_ALWAYS_INLINE { a[(st + 1) & 1][i] = ring.template read<(st + 1) * 8 + decltype(i)::value>(); });
+      if constexpr (last) cp_settle<8>(a[st & 1], bs[0], bs[1], bs[2], bs[3]);
+      else cp_settle<8>(a[st & 1]);
     } else {
-      if constexpr (last) cph_settle8o<0>(a[st & 1], bs[0], bs[1], bs[2], bs[3]);
-      else cph_settle8<0>(a[st & 1]);
+      if constexpr (last) cp_settle<0>(a[st & 1], bs[0], bs[1], bs[2], bs[3]);
+      else cp_settle<0>(a[st & 1]);
     }
     __builtin_amdgcn_sched_barrier(0);
     cph_step<first, last>(acc, a[st & 1], in.h(ip), in.l(ip));
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (last) {
-      cp_for<4>([&](auto t) CP_ALWAYS_INLINE {
+      ars_for<4>([&](auto t) ARS_ALWAYS_INLINE {
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[otg * 4 + t][r] = __builtin_fmaf(acc[t][r], d, bs[t][r]);
       });
@@ -917,7 +759,7 @@ template <int NP, int HT> __device__ __forceinline__ void cph_layer(CpRingH& rin
 // ReLU + per-sample scale + conversion of the HT out tiles into the next layer's B operands; returns 2^-ea
 template <int HT> __device__ __forceinline__ float cph_convert(const CpAct& out, const CpBh& in) {
   float amax = 0.f;
-  cp_for<HT>([&](auto t_) CP_ALWAYS_INLINE {
+  ars_for<HT>([&](auto t_) ARS_ALWAYS_INLINE {
     constexpr int t = t_;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -926,8 +768,8 @@ template <int HT> __device__ __forceinline__ float cph_convert(const CpAct& out,
     }
   });
   float s, inv_s;
-  cph_scale(amax, s, inv_s);
-  cp_for<HT / 2>([&](auto p_) CP_ALWAYS_INLINE {
+  arh_scale(amax, s, inv_s);
+  ars_for<HT / 2>([&](auto p_) ARS_ALWAYS_INLINE {
     constexpr int p = p_;
     cph_split(out[2 * p], out[2 * p + 1], s, in.h(p), in.l(p));
   });
@@ -937,85 +779,62 @@ template <int HT> __device__ __forceinline__ float cph_convert(const CpAct& out,
 template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_kernel_half(CpArgs a) {
   static_assert(HT % 4 == 0 && HT <= CP_T && NIT <= CP_IT && NIT % 2 == 0 && (8 * (NIT / 2) * (HT / 4)) % CPH_CH == 0 && (8 * (HT / 2) * (HT / 4)) % CPH_CH == 0 && (2 * (HT / 2)) % CPH_CH == 0,
                 "every layer and every group of the last layer fills whole chunks");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int jl = lane & 15, q = lane >> 4;
-  float* bias_lds = cp_lds + CP_NR * CPH_CH * 256;
-  int* amap_lds = reinterpret_cast<int*>(bias_lds + a.bias_floats);
-  int* fmap_lds = amap_lds + CP_IT * 16;
-  int* lay_lds = fmap_lds + a.NG * 8;
-  float* xw = reinterpret_cast<float*>(lay_lds + 3 * CP_MAXL) + (size_t)wave * 16 * a.xs;
-  if (tid == 0) {
-#pragma unroll
-    for (int l = 0; l < CP_MAXL; ++l) lay_lds[2 * CP_MAXL + l] = a.bias_off[l];
-  }
-  for (int i = tid; i < a.bias_floats; i += 256) bias_lds[i] = a.bias[i];
-  for (int i = tid; i < NIT * 16; i += 256) amap_lds[i] = a.amap[i];
-  for (int i = tid; i < a.NG * 8; i += 256) fmap_lds[i] = a.fmap[i];
+  const ArLane ln;
+  const int lane = ln.lane, wave = ln.wave, q = ln.q;
+  const CpLds lds(a, CPH_CH, wave);
+  lds.stage<false>(a, ln.tid, NIT);
   CpRingH ring;
-  ring.lds = cp_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
-#pragma unroll
-  for (int i = 0; i < CP_NR - 1; ++i) ring.issue();
-  ring.slot = CP_NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)cp_lds);
-  ring.cur_off = ring.lds_off;
+  ring.start(cp_lds, a.stream, a.n_chunks, wave, lane);
   __syncthreads();
 
-  const int xs = a.xs;
-  float* xrow = xw + jl * xs;
+  float* const xw = lds.rows;
+  float* const xrow = xw + ln.j * a.xs;
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const int64_t n0 = tile * 64 + wave * 16;
-    const int64_t n = n0 + jl;
-    const bool live = n < a.N;
-    cp_stage_rows(a, xw, xs, n0, lane);
+    cp_stage_rows(a, xw, a.xs, n0, lane);
 
-    f32x4c out_lo[16], out_hi[16];
-    cf16x8 bhl[8], bhh[8], bll[8], blh[8];
+    f32x4 out_lo[16], out_hi[16];
+    f16x8 bhl[8], bhh[8], bll[8], blh[8];
     const CpAct out{out_lo, out_hi};
     const CpBh in{bhl, bhh, bll, blh};
     float inv_s;
     {  // first layer: B operands gathered from the row image through idx_a, scaled by the sample's own power of two, converted pair by pair
-      f32x4c v[NIT];
+      f32x4 v[NIT];
       float amax = 0.f;
-      cp_for<NIT>([&](auto t_) CP_ALWAYS_INLINE {
+      ars_for<NIT>([&](auto t_) ARS_ALWAYS_INLINE {
         constexpr int t = t_;
+        v[t] = cp_gather_inputs(a, lds.amap, xrow, t, q);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int src = amap_lds[t * 16 + 4 * q + r];
-          v[t][r] = src >= 0 ? xrow[src] : (src <= -2 ? xrow[a.D + (-2 - src)] : 0.f);
-          amax = fmaxf(amax, fabsf(v[t][r]));
-        }
+        for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(v[t][r]));
       });
       float s;
-      cph_scale(amax, s, inv_s);
-      cp_for<NIT / 2>([&](auto p_) CP_ALWAYS_INLINE { constexpr int p = p_; cph_split(v[2 * p], v[2 * p + 1], s, in.h(p), in.l(p)); });
+      arh_scale(amax, s, inv_s);
+      ars_for<NIT / 2>([&](auto p_) ARS_ALWAYS_INLINE { constexpr int p = p_; cph_split(v[2 * p], v[2 * p + 1], s, in.h(p), in.l(p)); });
     }
-    cph_layer<NIT / 2, HT>(ring, bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL]) + 4 * q, in, out, a.wdescale[0] * inv_s);
+    cph_layer<NIT / 2, HT>(ring, lds.bias_of(0, q), in, out, a.wdescale[0] * inv_s);
     inv_s = cph_convert<HT>(out, in);
     for (int l = 1; l < a.L - 1; ++l) {
-      cph_layer<HT / 2, HT>(ring, bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + l]) + 4 * q, in, out, a.wdescale[l] * inv_s);
+      cph_layer<HT / 2, HT>(ring, lds.bias_of(l, q), in, out, a.wdescale[l] * inv_s);
       inv_s = cph_convert<HT>(out, in);
     }
     // last layer + affine map: one group of 8 moved features = one out tile = HT / 2 blocks, two blocks per step on two accumulators
-    const float* bias_last = bias_lds + __builtin_amdgcn_readfirstlane(lay_lds[2 * CP_MAXL + a.L - 1]) + 4 * q;
+    const float* bias_last = lds.bias_of(a.L - 1, q);
     const float dl = a.wdescale[a.L - 1] * inv_s;
     float lacc = 0.f;
     for (int g = 0; g < a.NG; ++g) {
-      const int f0 = fmap_lds[g * 8 + 2 * q], f1 = fmap_lds[g * 8 + 2 * q + 1];
-      const float x0 = xrow[f0 < 0 ? 0 : f0], x1 = xrow[f1 < 0 ? 0 : f1];
-      const f32x4c bg = *reinterpret_cast<const f32x4c*>(bias_last + g * 16);
-      f32x4c c0, c1;
-      f32x4c w[2][4];  // images of the step's two blocks: w[.][2 b + part]
+      const CpSlots slots(lds.fmap, xrow, g, q);
+      const f32x4 bg = *reinterpret_cast<const f32x4*>(bias_last + g * 16);
+      f32x4 c0, c1;
+      f32x4 w[2][4];  // images of the step's two blocks: w[.][2 b + part]
       constexpr int KS = HT / 4;  // steps per group
-      cp_for<4>([&](auto i) CP_ALWAYS_INLINE { w[0][i] = ring.template read<decltype(i)::value>(); });
-      cp_for<KS>([&](auto k_) CP_ALWAYS_INLINE {
+      ars_for<4>([&](auto i) ARS_ALWAYS_INLINE { w[0][i] = ring.template read<decltype(i)::value>(); });
+      ars_for<KS>([&](auto k_) ARS_ALWAYS_INLINE {
         constexpr int k = k_;
         if constexpr (k + 1 < KS) {
-          cp_for<4>([&](auto i) CP_ALWAYS_INLINE { w[(k + 1) & 1][i] = ring.template read<(k + 1) * 4 + decltype(i)::value>(); });
-          cph_settle4<4>(w[k & 1]);
+          ars_for<4>([&](auto i) ARS_ALWAYS_INLINE { w[(k + 1) & 1][i] = ring.template read<(k + 1) * 4 + decltype(i)::value>(); });
+          cp_settle<4>(w[k & 1]);
         } else {
-          cph_settle4<0>(w[k & 1]);
+          cp_settle<0>(w[k & 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (k == 0) {
@@ -1036,27 +855,14 @@ template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_ke
         __builtin_amdgcn_sched_barrier(0);
       });
       asm volatile("s_nop 11" : "+v"(c0), "+v"(c1));
-      f32x4c p;
+      f32x4 p;
 #pragma unroll
       for (int r = 0; r < 4; ++r) p[r] = __builtin_fmaf(c0[r] + c1[r], dl, bg[r]);  // (shift, scale) of slot 2 q, then of slot 2 q + 1
-      float y0, y1, l0, l1;
-      cp_affine(a, p[0], p[1], x0, y0, l0);
-      cp_affine(a, p[2], p[3], x1, y1, l1);
-      if (f0 >= 0) { xrow[f0] = y0; lacc += l0; }
-      if (f1 >= 0) { xrow[f1] = y1; lacc += l1; }
+      cp_group_epilogue(a, slots, p, xrow, lacc);
     }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    cp_store_rows(a, xw, xs, n0, lane);
-    if (a.ladj) {
-      lacc += __shfl_xor(lacc, 16, 64);
-      lacc += __shfl_xor(lacc, 32, 64);
-      if (live && q == 0) a.ladj[n] = a.accumulate ? a.ladj[n] + lacc : lacc;
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    cp_finish_rows(a, xw, n0, ln, lacc);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
 
 }  // namespace zk
@@ -1069,7 +875,7 @@ extern "C" {
 // n_layers linear layers; tiles / widths: HOST arrays with the output tiles and widths of the n_layers - 1 hidden layers;
 // bias_off: HOST array of n_layers offsets into the bias image; amap [nit * 16], fmap [n_groups * 8]: DEVICE index maps;
 // wstream / bias: the plan of zuko_amd/coupling_plan.py.  Limits: D + C <= 1024 columns in the row image with
-// 4 * 16 * (D + C + 4) * 4 bytes of LDS beside the 72 KiB ring, conditioner inputs <= 256, hidden widths <= 512.
+// 4 * 16 * (D + C + 4) * 4 bytes of LDS beside the ring (CpLds::bytes: at most 160 KiB with the 72 KiB ring of 24-image chunks), conditioner inputs <= 256, hidden widths <= 512.
 static int cp_launch(int inverse, int64_t N, int D, int C, const void* x, int64_t ldx, const void* ctx, int64_t ldc, void* y, int64_t ldy, void* ladj, int accumulate,
                         const void* wstream, const void* bias, int bias_floats, const int32_t* bias_off, const int32_t* amap, int nit, const int32_t* fmap,
                         int n_groups, int n_layers, const int32_t* tiles, const int32_t* widths, int n_chunks, int act, double slope, int static_ok, void* stream,
@@ -1092,57 +898,34 @@ static int cp_launch(int inverse, int64_t N, int D, int C, const void* x, int64_
               (C == 0 || ((C % 4 == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(ctx) & 15) == 0)));
   a.ls = (float)log(slope);
   a.n_tiles = (N + 63) / 64;
-  const int lds = (CP_NR * CP_CH * 256 + bias_floats + CP_IT * 16 + n_groups * 8 + 3 * CP_MAXL + CP_WAVES * 16 * a.xs) * (int)sizeof(float);
-  if (lds > 160 * 1024) return ZK_EINVAL;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)coupling_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
+  if (CpLds::bytes(CP_CH, bias_floats, n_groups, a.xs) > 160 * 1024) return ZK_EINVAL;
   // static-shape instantiation: ReLU, every hidden layer 512 wide (32 tiles), 128 conditioner inputs (8 tiles), groups in
   // whole triples padded by the plan (cfg4 of BASELINE.json: RealNVP(256, hidden [512] * 3)); `static_ok` is the plan's word
   // that its stream has the matching layout (every layer and every triple of groups starts on a chunk boundary)
   bool same = act == 1 && nit == 8;
   for (int l = 0; l < n_layers - 1; ++l) same = same && tiles[l] == 32 && widths[l] == 512;
+  const void* fn = (const void*)coupling_kernel;
+  int chunk = CP_CH;
   if (static_ok == 3) {  // the plan's TWO-PART stream (coupling_plan.py: half stream): f16 images, 16-image chunks, per-layer descale factors
     if (!same || n_layers > 4 || !wdescale) return ZK_EINVAL;
     for (int l = 0; l < n_layers; ++l) {
       if (!(wdescale[l] > 0.0) || !(wdescale[l] < 1e38)) return ZK_EINVAL;
       a.wdescale[l] = (float)wdescale[l];
     }
-    static bool attr4 = false;
-    if (!attr4) {
-      hipError_t e = hipFuncSetAttribute((const void*)coupling_kernel_half<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr4 = true;
-    }
-    hipLaunchKernelGGL((coupling_kernel_half<8, 32>), dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-    return ZK_LAUNCH_CHECK();
+    fn = (const void*)coupling_kernel_half<8, 32>;
+    chunk = CPH_CH;
+  } else if (static_ok == 2) {  // the plan's stream is the operand-split one (coupling_plan.py: split_gather): bf16 images, (4 out tiles, in pair) steps
+    if (!same) return ZK_EINVAL;  // a split stream cannot be read by the f32 kernels
+    fn = (const void*)coupling_kernel_split<8, 32>;
+  } else if (same && static_ok) {
+    fn = (const void*)coupling_kernel_static<8, 32>;
   }
-  if (same && static_ok == 2) {  // the plan's stream is the operand-split one (coupling_plan.py: split_gather): bf16 images, (4 out tiles, in pair) steps
-    static bool attr3 = false;
-    if (!attr3) {
-      hipError_t e = hipFuncSetAttribute((const void*)coupling_kernel_split<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr3 = true;
-    }
-    hipLaunchKernelGGL((coupling_kernel_split<8, 32>), dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-    return ZK_LAUNCH_CHECK();
-  }
-  if (static_ok == 2) return ZK_EINVAL;  // a split stream cannot be read by the f32 kernels
-  if (same && static_ok) {
-    static bool attr2 = false;
-    if (!attr2) {
-      hipError_t e = hipFuncSetAttribute((const void*)coupling_kernel_static<8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr2 = true;
-    }
-    hipLaunchKernelGGL((coupling_kernel_static<8, 32>), dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-    return ZK_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(coupling_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+  const int lds = CpLds::bytes(chunk, bias_floats, n_groups, a.xs);
+  hipError_t e = grant_dyn_lds(fn, lds);
+  if (e != hipSuccess) return (int)e;
+  void* kargs[] = {&a};
+  e = hipLaunchKernel(fn, dim3((unsigned)(a.n_tiles < 256 ? a.n_tiles : 256)), dim3(256), kargs, lds, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
   return ZK_LAUNCH_CHECK();
 }
 

@@ -6,8 +6,6 @@
 #include "zk_univariate.h"
 #include <cstddef>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
 namespace zk {
 
@@ -373,21 +371,10 @@ template <bool PREFETCHED = false> __device__ __forceinline__ void ar_ladj_store
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-// Grant, launch, check.  The opt-in to > 64 KiB of dynamic LDS is per function: set once, and again only if a larger size is asked for.  (static:
-// every translation unit — the library's two, each generated kernel's shared object — keeps its own map.)
+// Grant (zk_common.h: grant_dyn_lds), launch, check.
 static inline int ar_launch_dyn_lds(const void* fn, int max_grid, int block, int lds_bytes, ArArgs& a, void* stream) {
-  hipError_t e = hipSuccess;
-  {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds_bytes) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-      if (e != hipSuccess) return (int)e;
-      g = lds_bytes;
-    }
-  }
+  hipError_t e = grant_dyn_lds(fn, lds_bytes);
+  if (e != hipSuccess) return (int)e;
   const unsigned grid = (unsigned)(a.n_tiles < max_grid ? a.n_tiles : max_grid);
   void* kargs[] = {&a};
   e = hipLaunchKernel(fn, dim3(grid), dim3((unsigned)block), kargs, lds_bytes, (hipStream_t)stream);

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #define ZK_DTYPE_F32 0
 #define ZK_DTYPE_F64 1
 #define ZK_DTYPE_BF16 2  /* storage type of x / phi / y / weights; arithmetic and ladj stay fp32 */
@@ -65,6 +68,19 @@ template <typename T> __device__ __forceinline__ T segment_sum(T v, int seg, int
     if (lane_in_seg + off < seg) v += o;
   }
   return v;
+}
+
+// The opt-in to more than 64 KiB of dynamic LDS is per function: granted once, and again only when a larger size is asked for.  (static: every
+// translation unit of the library and every generated kernel's shared object keeps its own map.)
+static inline hipError_t grant_dyn_lds(const void* fn, int lds_bytes) {
+  static std::mutex mu;
+  static std::unordered_map<const void*, int> granted;
+  std::lock_guard<std::mutex> lock(mu);
+  int& g = granted[fn];
+  if (g >= lds_bytes) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  if (e == hipSuccess) g = lds_bytes;
+  return e;
 }
 
 static inline int grid_for(int64_t nblocks) {

@@ -4,8 +4,6 @@
 #pragma once
 #include "../../include/zuko_amd.h"
 #include "zk_common.h"
-#include <mutex>
-#include <unordered_map>
 #include <utility>
 
 namespace zk {
@@ -121,21 +119,10 @@ template <bool INVERSE, class P, class A, class Own> static inline int mnn_prepa
 }
 
 // Grant, launch of MNN_THREADS-wide blocks over the kernel's one argument `args`, check — as ar_launch_dyn_lds of csrc/zk_ar_common.h (whose signature
-// is tied to ArArgs and a one-dimensional grid): the opt-in to more than 64 KiB of dynamic LDS is per function, set under a lock, once, and again
-// only if a larger size is asked for.  (static: each translation unit keeps its own map.)
+// is tied to ArArgs and a one-dimensional grid); the grant is grant_dyn_lds of zk_common.h.
 static inline int mnn_launch_dyn_lds(const void* fn, dim3 grid, int lds_bytes, void* args, hipStream_t st) {
-  hipError_t e = hipSuccess;
-  {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> granted;
-    std::lock_guard<std::mutex> lock(mu);
-    int& g = granted[fn];
-    if (g < lds_bytes) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-      if (e != hipSuccess) return (int)e;
-      g = lds_bytes;
-    }
-  }
+  hipError_t e = grant_dyn_lds(fn, lds_bytes);
+  if (e != hipSuccess) return (int)e;
   void* kargs[] = {args};
   e = hipLaunchKernel(fn, grid, dim3(MNN_THREADS), kargs, lds_bytes, st);
   if (e != hipSuccess) return (int)e;
