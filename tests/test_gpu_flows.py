@@ -204,6 +204,14 @@ def test_sampling_paths(dev, name):
     flow, entry = build_flow(name)
     spec = oracle_spec(flow, entry)
     flow = flow.to(dev)
+    # which inverse this samples through (inc_cases.expects_incremental: the conditions of incremental_state, evaluated on the host): NOT the incremental
+    # launch — nsf_cfg1 and maf_doc spread 128 / 64 hidden units over three degrees, more than the 16 of an aligned tile, so the partial sweeps serve
+    # them; nice_small is a coupling flow
+    from inc_cases import expects_incremental
+
+    served = [expects_incremental(t) for t in flow.transform.transforms if hasattr(t, "incremental_state")]
+    assert served == {"nsf_cfg1": [False] * 3, "maf_doc": [False] * 3, "nice_small": []}[name]
+    assert [t.incremental_state(dev) is not None for t in flow.transform.transforms if hasattr(t, "incremental_state")] == served
     C = entry[1].get("context", 0)
     gen = torch.Generator().manual_seed(5)
     c = torch.randn(33, C, generator=gen) if C else None
@@ -320,12 +328,15 @@ def test_polynomial_flows_invert_in_one_incremental_launch(dev, name, monkeypatc
     with torch.no_grad():
         xo = O.flow_inverse(spec, z.cpu())
     assert (xi.cpu() - xo).abs().max().item() < 5e-5, f"{name}: incremental inverse vs the oracle's sweep loop: {(xi.cpu() - xo).abs().max().item():.2e}"
-    # a non-finite input poisons its own row only
+    # a non-finite input touches its own row only, and that row as in the reference: its bisection never returns a NaN (every comparison with a NaN is
+    # false, the bracket closes on its lower end), so the row stays finite (tests/test_gpu_inc_envelope.py compares the values)
     zz = z[:8].clone()
     zz[1, 3] = float("nan")
     with torch.no_grad():
         xb = flow().transform.inv(zz).cpu()
-    assert torch.isnan(xb[1]).any() and torch.isfinite(xb[0]).all() and torch.isfinite(xb[2:]).all()
+        xbo = O.flow_inverse(spec, zz.cpu())
+    keep = [0, 2, 3, 4, 5, 6, 7]
+    assert torch.equal(xb[keep], xi[:8].cpu()[keep]) and torch.isfinite(xbo).all() and torch.equal(torch.isfinite(xb), torch.isfinite(xbo))
 
 
 def test_inverse_with_a_per_unit_activation(dev):
@@ -369,6 +380,12 @@ def test_fused_extra_spline_layouts(dev, kind, kw):
     with torch.no_grad():
         t = flow.transform.transforms[0](cg)
         assert t._fused(x.to(dev)) is not None
+        # the inverse below is one incremental launch per layer for the 16-bin NSF only: the 4-bin one puts 24 hidden units (6 per degree, 4 degrees)
+        # into a group's tile of 16, the circular spline (kind 4) has no incremental kernel — the partial sweeps serve both
+        from inc_cases import expects_incremental
+
+        served = [expects_incremental(l) for l in flow.transform.transforms]
+        assert served == [kw.get("bins") == 16] * 2 and [l.incremental_state(dev) is not None for l in flow.transform.transforms] == served
         z, ladj = flow(cg).transform.call_and_ladj(x.to(dev))
         oz, ol = O.flow_forward(spec, x, c)
         spec64 = to_f64(spec)
@@ -648,6 +665,12 @@ def test_passes2_without_context_round_trip(dev, kind, D):
     sd = {k: v.detach().cpu() for k, v in flow.state_dict().items() if v is not None}
     spec = O.spec_from_state_dict(sd, "ar", O.uni_rqs(8) if kind == "nsf" else O.UNI_AFFINE, D, passes=2)
     x = torch.randn(333, D, generator=torch.Generator().manual_seed(1))
+    # the inverse below is NOT the incremental launch: with two degrees the 64 hidden units of a layer fall into two tiles of 32, twice an aligned tile's
+    # 16 — the partial sweeps the docstring speaks of serve all three flows (tests/inc_cases.py holds passes=2 conditioners the incremental kernel takes)
+    from inc_cases import expects_incremental
+
+    served = [expects_incremental(t) for t in flow.transform.transforms]
+    assert served == [False] * 3 and all(t.incremental_state(dev) is None for t in flow.transform.transforms)
     with torch.no_grad():
         z = flow().transform(x.to(dev))
         xr = flow().transform.inv(z)

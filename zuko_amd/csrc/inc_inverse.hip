@@ -205,8 +205,15 @@ template <int N, class F> __device__ __forceinline__ void inc_for(F&& f) { inc_f
     _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) (acc) = __builtin_amdgcn_mfma_f32_16x16x4f32((a)[r_], (b)[r_], (acc), 0, 0, 0); \
   }
 
+// POISON: what a non-finite input does to its row.  The closed-form maps hand a non-finite y on as a non-finite x, and the reference's next sweep turns
+// every parameter of the row into NaN (0 * NaN in the masked product, zuko/nn.py:217-218): 2 = any non-finite y or context makes the row NaN; 3 = the
+// same, except that the spline under NaN parameters still passes y = -inf through (its first knot is the constant -B, so -inf lies outside the box —
+// zuko/transforms.py:534-548 — while +inf falls into bin 0 and becomes NaN).  The reference's bisection (zuko/utils.py:170-178) never returns a NaN —
+// every comparison with a NaN is false, the bracket closes on its lower end — so its rows stay finite: the parameters of EVERY feature are NaN from its
+// second sweep on when the context is non-finite (0: only then; a non-finite y inverts to an end of [-B, B] and poisons nothing) or, for the bounded
+// Bernstein map whose linear tails invert y = +-inf to x = +-inf, when a y is infinite (1).
 struct IncAffine {
-  static constexpr int TOTAL = 2, NT = 1;
+  static constexpr int TOTAL = 2, NT = 1, POISON = 2;
   template <typename A> static __device__ __forceinline__ void inv(const float* p, const A& a, float y, float& x, float& lj) {
     const float lsc = softclip<float, MathFast>(p[1], a.ls);
     x = MathFast::div_safe(y - p[0], MathFast::exp(lsc));
@@ -214,7 +221,7 @@ struct IncAffine {
   }
 };
 template <int K> struct IncRqs {
-  static constexpr int TOTAL = 3 * K - 1, NT = (TOTAL + 3) / 4;
+  static constexpr int TOTAL = 3 * K - 1, NT = (TOTAL + 3) / 4, POISON = 3;
   template <typename A> static __device__ __forceinline__ void inv(const float* p, const A& a, float y, float& x, float& lj) {
     int k;
     rqs_lean<K, true, true>([&](int j) { return p[j]; }, [&](int j) { return p[K + j]; }, [&](int j) { return p[2 * K + j]; }, a.lc, y, x, lj, k);
@@ -241,7 +248,7 @@ template <int K> struct IncRqs {
 #define INC_BERN_TRUST 1
 #endif
 struct IncSos3x5 {  // ShiftedSOSPolynomialTransform, 3 polynomials of degree 4 + the learned constant (zuko/flows/polynomial.py:51-70)
-  static constexpr int TOTAL = 16, NT = 4;
+  static constexpr int TOTAL = 16, NT = 4, POISON = 0;
   template <typename A> static __device__ __forceinline__ void inv(const float* p, const A& a, float y, float& x, float& lj) {
     auto ld = [&](int j) { return p[j]; };
     const float yy = y - p[15];
@@ -287,7 +294,7 @@ struct IncSos3x5 {  // ShiftedSOSPolynomialTransform, 3 polynomials of degree 4 
   }
 };
 struct IncBern17 {  // BoundedBernsteinTransform of degree 16: 17 unconstrained parameters -> 22 constrained coefficients (zuko/transforms.py:779-831)
-  static constexpr int TOTAL = 17, NT = 5;
+  static constexpr int TOTAL = 17, NT = 5, POISON = 1;
   template <typename A> static __device__ __forceinline__ void inv(const float* p, const A& a, float y, float& x, float& lj) {
     constexpr int NC = 22, n = NC - 1;
     float th[NC];
@@ -386,7 +393,9 @@ template <typename Uni, int NH, bool HALF = false> __global__ __launch_bounds__(
         float xv = 0.f, yv = 0.f;
         if (col < a.D) yv = a.yin[nc * a.ldy + col];
         else if (col < a.DIN) xv = a.ctx[nc * a.ldc + (col - a.D)];
-        bad |= !(fabsf(xv) < __builtin_inff()) | !(fabsf(yv) < __builtin_inff());
+        bad |= !(fabsf(xv) < __builtin_inff());
+        if constexpr (Uni::POISON >= 2) bad |= !(fabsf(yv) < __builtin_inff());
+        if constexpr (Uni::POISON == 1) bad |= fabsf(yv) == __builtin_inff();
         xrow[col] = xv;
         xrow[col + 16 * xs] = yv;  // (the y tile sits 16 rows behind the x tile)
       }
@@ -404,6 +413,7 @@ template <typename Uni, int NH, bool HALF = false> __global__ __launch_bounds__(
     f32x4i ev1 = {0.f, 0.f, 0.f, 0.f}, ev2 = ev1, ev3 = ev1;
     float am1 = 0.f, am2 = 0.f, am3 = 0.f;
     float lacc = 0.f;
+    const float nanv = __builtin_nanf("");
 
     // one statically indexed copy of the group step per group (a generic lambda over integral constants: `#pragma unroll`
     // does not unroll a loop of this size, and a run-time j would put the activation arrays in scratch memory)
@@ -521,6 +531,12 @@ template <typename Uni, int NH, bool HALF = false> __global__ __launch_bounds__(
 #pragma unroll
             for (int e = 0; e < 4; ++e) p[4 * tt + e] = c[e];
           }
+          if constexpr (Uni::POISON < 2) {  // the bisection maps: a poisoned row inverts NaN parameters, as the reference's later sweeps do
+            if (bad) {
+#pragma unroll
+              for (int e = 0; e < 4 * NT; ++e) p[e] = nanv;
+            }
+          }
           float xv, lj;
           Uni::inv(p, a, yv, xv, lj);
           if (q == r && f >= 0) {
@@ -558,14 +574,17 @@ template <typename Uni, int NH, bool HALF = false> __global__ __launch_bounds__(
     static_assert(IN_T == 17, "one ZK_INC_STEP per group");
 
     // ---- results: x rows (16-byte stores where possible), ladj reduced over the four lanes of a sample -------------
-    const float nanv = __builtin_nanf("");
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     if (live) {
       for (int c0 = 4 * q; c0 < a.D; c0 += 16) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          if (c0 + e < a.D) a.x[n * a.ldx + c0 + e] = bad ? nanv : xrow[c0 + e];
+          if (c0 + e < a.D) {
+            float v = xrow[c0 + e];
+            if (bad && Uni::POISON >= 2) v = (Uni::POISON == 3 && yrow[c0 + e] == -__builtin_inff()) ? -__builtin_inff() : nanv;
+            a.x[n * a.ldx + c0 + e] = v;
+          }
       }
     }
     if (a.ladj) {

@@ -463,8 +463,9 @@ class IncAR:
         self.h_descale = [1.0] + [2.0 ** -e for _, e in scales[1:]] + [1.0] * (4 - len(scales))
         self.h_ok = True
 
-    def run(self, y, ctx, want_ladj: bool = False):
-        """y [N, D] contiguous fp32 (values to invert), ctx [N, C] or None -> (x [N, D], ladj [N] or None)."""
+    def run(self, y, ctx, want_ladj: bool = False, out=None):
+        """y [N, D] fp32 with unit column stride (values to invert), ctx [N, C] likewise or None -> (x [N, D], ladj [N] or None).
+        `out`: (x [N, D] fp32 with unit column stride, ladj [N] contiguous or None) to write into instead of new tensors."""
         import torch
 
         from . import _C
@@ -472,8 +473,12 @@ class IncAR:
 
         p = self.plan
         N = y.shape[0]
-        x = torch.empty((N, p.features), dtype=torch.float32, device=y.device)
-        ladj = torch.empty(N, dtype=torch.float32, device=y.device) if want_ladj else None
+        if out is None:
+            x = torch.empty((N, p.features), dtype=torch.float32, device=y.device)
+            ladj = torch.empty(N, dtype=torch.float32, device=y.device) if want_ladj else None
+        else:
+            x, ladj = out[0], (out[1] if want_ladj else None)
+            assert x.shape == (N, p.features) and x.dtype == torch.float32 and x.stride(1) == 1 and (ladj is None or (ladj.shape == (N,) and ladj.is_contiguous()))
         C = 0 if ctx is None else ctx.shape[1]
         from . import fused
 
@@ -494,7 +499,7 @@ class IncAR:
             else:
                 extra["eps"] = eps
         a = _C.args("zk_ar_inc_args_v1", uni_kind=p.layout.kind, n_hidden=p.n_hidden, N=N, D=p.features, C=C, y=_ptr(y), ldy=y.stride(0), ctx=_ptr(ctx),
-                    ldc=0 if ctx is None else ctx.stride(0), x=_ptr(x), ldx=p.features, ladj=_ptr(ladj), wstream=_ptr(self.h_stream if half else self.stream), bias=_ptr(self.bias),
+                    ldc=0 if ctx is None else ctx.stride(0), x=_ptr(x), ldx=x.stride(0), ladj=_ptr(ladj), wstream=_ptr(self.h_stream if half else self.stream), bias=_ptr(self.bias),
                     bias_floats=self.bias.numel(), bias_off=self.bias_off, featmap=_ptr(self.featmap), prog=_ptr(self.prog), n_groups=p.n_groups,
                     n_chunks=self.half.n_chunks if half else p.n_chunks, act=self.act, bound=self.bound, slope=self.slope, **extra)
         err = _C.lib().zk_ar_inverse_incremental(a, _stream())
