@@ -705,6 +705,71 @@ int zk_umnn_inverse(const zk_umnn_args_v1* args, void* stream);
 /* The launch geometry of zk_umnn_forward / zk_umnn_inverse: the rule, arguments and return values of zk_mnn_launch_geometry (one function behind both). */
 int zk_umnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block);
 
+/* ---- Gaussian mixture model (GMM; zuko/mixtures.py, zuko/distributions.py: Mixture; float32 and float64) ------------------------------------
+ * One row of phi, as the model's MLP (or the concatenated parameter list) lays it out, with Lc = 1 if tied else K, Dd = 1 for spherical
+ * covariance and D otherwise:
+ *     logits[K] | loc[K, D] | diag[Lc, Dd] | tril[Lc, D (D - 1) / 2]          (tril for full covariance only)
+ * tril is the strict lower triangle row by row: (1,0), (2,0), (2,1), (3,0), ...  The scale factor of component k is L_ii = exp(diag_i) + epsilon,
+ * L_ij = tril (i > j); spherical covariance uses the one diag value for every i, tied covariance the one factor for every k.
+ *
+ * zk_gmm_log_prob replaces diag_embed + masked_scatter + MultivariateNormal.log_prob (or DiagNormal.log_prob) + log_softmax + logsumexp:
+ *     d_k = x - loc_k,   z_k = L_k^{-1} d_k  (forward substitution, i = 0 .. D - 1, the inner sum in the order j = 0 .. i - 1)
+ *     logN_k = -1/2 (D log 2 pi + sum_i z_ki^2) - sum_i log L_kii
+ *     out = logsumexp_k(log_softmax(logits)_k + logN_k)     (the maximum is subtracted; -inf when every term is -inf)
+ * zk_gmm_backward recomputes these from x and phi and writes, for the upstream gradient g[N], with w = softmax(logits),
+ * r_k = softmax_k(log w_k + logN_k) and a_k = L_k^{-T} z_k:
+ *     d/dlogits_k = g (r_k - w_k),  d/dloc_k = g r_k a_k,  d/dx = -sum_k g r_k a_k,  d/dtril_kij = g r_k a_ki z_kj,
+ *     d/ddiag_ki = g r_k (a_ki z_ki - 1 / L_kii) exp(diag_ki)      (tied: summed over k = 0, 1, ...; spherical: summed over i = 0, 1, ...)
+ * One wave per block, one lane per row; phi and gphi move through LDS in coalesced segments, nothing of size [N, K] or [N, K, D, D] exists
+ * in device memory.  No atomics: the same inputs give the same bits, and a row's result depends on its own x, phi row and g only (not on N,
+ * the launch geometry or its neighbours).
+ *
+ *   x      [N, D], row stride ldx >= D (elements)
+ *   phi    [N, total], row stride ld_phi >= total = zk_gmm_total(D, K, covariance, tied); ld_phi = 0: ONE row shared by all N (the
+ *          unconditional model).  Rows need 4-byte (float64: 8-byte) alignment only
+ *   out    zk_gmm_log_prob: [N]
+ *   g      zk_gmm_backward: [N]
+ *   gphi   zk_gmm_backward, or NULL: [N, total] with row stride ld_gphi >= total; with ld_phi = 0 ONE row [total] = the sum over the N rows:
+ *          every block adds its rows in order into a partial vector in `work`, a second launch adds the partials in block order (bitwise
+ *          reproducible for a given N).  work: zk_gmm_workspace_floats(dtype, N, D, K, covariance, tied) elements of the call's dtype
+ *   gx     zk_gmm_backward, or NULL: [N, D] with row stride ld_gx >= D.  gphi and gx may not both be NULL
+ *   limits 1 <= D <= 64, 1 <= K <= 64, N >= 1.
+ * The block follows the ARGUMENT BLOCK conventions above: a foreign struct_size or version, a non-zero reserved field, a shape outside the
+ * limits, a NULL required pointer or a stride below its minimum is rejected with hipErrorInvalidValue before anything touches the device. */
+typedef struct zk_gmm_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_gmm_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t dtype;           /* ZK_DTYPE_F32 or ZK_DTYPE_F64 */
+  int32_t D;               /* features */
+  int32_t K;               /* components */
+  int32_t covariance;      /* 0 full, 1 diagonal, 2 spherical */
+  int32_t tied;            /* 0 or 1 */
+  int32_t reserved;        /* 0 */
+  int64_t N;
+  int64_t ldx;
+  int64_t ld_phi;          /* 0: one shared row */
+  int64_t ld_gphi;
+  int64_t ld_gx;
+  double epsilon;
+  const void* x;
+  const void* phi;
+  void* out;               /* zk_gmm_log_prob */
+  const void* g;           /* zk_gmm_backward */
+  void* gphi;              /* zk_gmm_backward, or NULL */
+  void* gx;                /* zk_gmm_backward, or NULL */
+  void* work;              /* zk_gmm_backward with ld_phi = 0 and gphi */
+} zk_gmm_args_v1;
+int zk_gmm_log_prob(const zk_gmm_args_v1* args, void* stream);
+int zk_gmm_backward(const zk_gmm_args_v1* args, void* stream);
+/* Elements per row of phi, or -1 outside the limits (host only). */
+int zk_gmm_total(int D, int K, int covariance, int tied);
+/* Elements of `work` the shared-row backward needs for N rows, or -1 for unsupported arguments (host only). */
+int zk_gmm_workspace_floats(int dtype, int64_t N, int D, int K, int covariance, int tied);
+/* The launch geometry of both entry points (host only): a block covers rows_per_block consecutive rows (64, or a smaller power of two where
+ * 64 rows of this shape and dtype do not fit 64 KiB of LDS).  Results do not depend on it; the query exists so that tests can name row
+ * counts that straddle a block boundary.  hipErrorInvalidValue for a shape outside the limits or a NULL pointer. */
+int zk_gmm_launch_geometry(int dtype, int D, int K, int covariance, int tied, int* rows_per_block);
+
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *
  * out[n] = sum_d Normal(loc[d], scale[d]).log_prob(z[n, d]) (+ ladj[n] if ladj != NULL). */
 int zk_diag_normal_log_prob(int dtype, int64_t N, int64_t D, const void* z, const void* loc, const void* scale,

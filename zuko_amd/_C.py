@@ -50,7 +50,7 @@ def _parse_structs(path: str) -> dict:
 
 
 STRUCTS = _parse_structs(_HEADER)
-_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_umnn_args_v1": 1}
+_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_umnn_args_v1": 1, "zk_gmm_args_v1": 1}
 
 
 def args(struct: str, **fields):
@@ -98,6 +98,7 @@ def gather_multi(items, stream) -> None:
 _AR, _CP, _INC = POINTER(STRUCTS["zk_ar_args_v1"]), POINTER(STRUCTS["zk_coupling_args_v1"]), POINTER(STRUCTS["zk_ar_inc_args_v1"])
 _MNN = POINTER(STRUCTS["zk_mnn_args_v1"])
 _UMNN = POINTER(STRUCTS["zk_umnn_args_v1"])
+_GMM = POINTER(STRUCTS["zk_gmm_args_v1"])
 
 # symbol -> argument types (return type is always int = hipError_t)
 SIGNATURES = {
@@ -161,6 +162,11 @@ SIGNATURES = {
     "zk_umnn_forward": [_UMNN, P],
     "zk_umnn_inverse": [_UMNN, P],
     "zk_umnn_launch_geometry": [L, L, POINTER(c_int), POINTER(c_int)],
+    "zk_gmm_log_prob": [_GMM, P],
+    "zk_gmm_backward": [_GMM, P],
+    "zk_gmm_total": [I, I, I, I],
+    "zk_gmm_workspace_floats": [I, L, I, I, I, I],
+    "zk_gmm_launch_geometry": [I, I, I, I, I, POINTER(c_int)],
 }
 
 

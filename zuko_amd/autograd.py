@@ -379,3 +379,25 @@ class DiagNormalLogProbFn(torch.autograd.Function):
         err = _C.lib().zk_diag_normal_backward(z2.shape[0], D, _ptr(z2), _ptr(loc.contiguous()), _ptr(scale.contiguous()), _ptr(gc), _ptr(gz), _stream())
         _C.check(err, "zk_diag_normal_backward")
         return gz.reshape(z.shape), None, None, (g if ctx.has_ladj else None)
+
+
+class GmmLogProbFn(torch.autograd.Function):
+    """log_prob of a Gaussian mixture (ops.gmm_log_prob): zk_gmm_log_prob forward, ONE zk_gmm_backward launch backward, which recomputes
+    everything from x and phi (nothing else is saved) and skips the gradient no input asks for."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, phi: Tensor, components: int, covariance_type: str, tied: bool, epsilon: float):
+        from . import ops
+
+        ctx.meta = (components, covariance_type, tied, epsilon)
+        ctx.save_for_backward(x, phi)
+        return ops.gmm_forward_kernel(x.detach(), phi.detach(), components, covariance_type, tied, epsilon)
+
+    @staticmethod
+    @once_differentiable  # raw-pointer HIP kernels on detached data: double backward (create_graph=True) must raise, not return graph-less grads
+    def backward(ctx, g):
+        from . import ops
+
+        x, phi = ctx.saved_tensors
+        gx, gphi = ops.gmm_backward(x, phi, g, *ctx.meta, need_x=ctx.needs_input_grad[0], need_phi=ctx.needs_input_grad[1])
+        return gx, gphi, None, None, None, None

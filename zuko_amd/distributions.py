@@ -13,13 +13,13 @@ import os
 
 import torch
 from torch import Size, Tensor
-from torch.distributions import Distribution, Independent, Normal, Transform, Uniform
+from torch.distributions import Categorical, Distribution, Independent, MultivariateNormal, Normal, Transform, Uniform
 from torch.distributions.utils import _sum_rightmost
 
 from . import ops
 from .transforms import ComposedTransform
 
-__all__ = ["BoxUniform", "DiagNormal", "NormalizingFlow"]
+__all__ = ["BoxUniform", "DiagNormal", "GaussianMixture", "NormalizingFlow"]
 
 # the reference switches argument validation off globally (zuko/distributions.py:35-36); NaNs propagate
 Distribution._validate_args = False
@@ -131,3 +131,57 @@ class NormalizingFlow(Distribution):
         x, ladj = self.transform.inv.call_and_ladj(z)
         ladj = _sum_rightmost(ladj, self.reinterpreted)
         return x, self.base.log_prob(z) - ladj
+
+
+class GaussianMixture(Distribution):
+    """p(X = x) = sum_k w_k N(x | loc_k, L_k L_k^T): what zuko.mixtures.GMM(...)(c) describes (a Mixture of a MultivariateNormal or DiagNormal),
+    held as the packed parameter rows phi = logits | loc | diag [| tril] the model's MLP emits.  phi [total] is ONE mixture (the unconditional
+    model); it stays one row under `expand`.  `log_prob` is ops.gmm_log_prob: one HIP launch that reads phi in place.  `sample` follows the
+    reference on torch ops: every component is drawn, a Categorical index picks one."""
+
+    has_rsample = False
+
+    def __init__(self, phi: Tensor, features: int, components: int, covariance_type: str = "full", tied: bool = False, epsilon: float = 1e-6,
+                 batch_shape: Size | None = None) -> None:
+        total = sum(ops.gmm_sizes(features, components, covariance_type, tied))
+        assert phi.shape[-1] == total, f"phi has {phi.shape[-1]} columns, expected {total}"
+        self.phi, self.features, self.components = phi, features, components
+        self.covariance_type, self.tied, self.epsilon = covariance_type, tied, epsilon
+        super().__init__(batch_shape=Size(phi.shape[:-1] if batch_shape is None else batch_shape), event_shape=Size((features,)), validate_args=False)
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(components: {self.components}, features: {self.features}, covariance: {self.covariance_type}{', tied' if self.tied else ''})"
+
+    def expand(self, batch_shape: Size, new: Distribution | None = None) -> Distribution:
+        batch_shape = Size(batch_shape)
+        phi = self.phi if self.phi.dim() == 1 or self.phi.shape[:-1] == batch_shape else self.phi.expand(batch_shape + self.phi.shape[-1:])
+        return GaussianMixture(phi, self.features, self.components, self.covariance_type, self.tied, self.epsilon, batch_shape=batch_shape)
+
+    def log_prob(self, x: Tensor) -> Tensor:
+        lp = ops.gmm_log_prob(x, self.phi, self.components, self.covariance_type, self.tied, self.epsilon)
+        shape = torch.broadcast_shapes(lp.shape, self.batch_shape)
+        return lp if lp.shape == shape else lp.expand(shape)
+
+    def _base(self) -> tuple[Distribution, Tensor]:
+        """(the K component normals, batch shape self.batch_shape + (K,); the logits) as torch distributions."""
+        D, K, lead = self.features, self.components, 1 if self.tied else self.components
+        parts = self.phi.split(ops.gmm_sizes(D, K, self.covariance_type, self.tied), dim=-1)
+        batch = self.phi.shape[:-1]
+        loc = parts[1].reshape(*batch, K, D)
+        scale = parts[2].reshape(*batch, lead, -1).exp() + self.epsilon
+        if self.covariance_type == "full":
+            factor = torch.diag_embed(scale)
+            factor = factor.masked_scatter(torch.ones_like(factor, dtype=torch.bool).tril(-1), parts[3].reshape(*batch, lead, -1))
+            base = MultivariateNormal(loc, scale_tril=factor, validate_args=False)
+        else:
+            base = DiagNormal(loc, scale.expand(loc.shape))
+        return base.expand(self.batch_shape + (K,)), parts[0]
+
+    def sample(self, shape: Size = ()) -> Tensor:
+        shape = Size(shape)
+        with torch.no_grad():
+            base, logits = self._base()
+            x = base.sample(shape)  # shape + batch + (K, D)
+            i = Categorical(logits=logits).expand(self.batch_shape).sample(shape)  # shape + batch
+            i = i[..., None, None].expand(*i.shape, 1, self.features)
+            return x.gather(-2, i).squeeze(-2)

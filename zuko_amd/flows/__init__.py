@@ -1,6 +1,7 @@
 r"""Flow factories of the hot path: MAF / NSF (autoregressive), NICE / RealNVP (coupling),
-SOSPF / BPF (polynomial), NAF / UNAF (monotone networks).  Same constructor signatures and module trees as zuko.flows."""
+SOSPF / BPF (polynomial), NAF / UNAF (monotone networks); GMM is an alias of zuko_amd.mixtures.GMM, as in the reference.  Same constructor signatures and module trees as zuko.flows."""
 
+from ..mixtures import GMM
 from .autoregressive import MAF, MaskedAutoregressiveTransform
 from .coupling import NICE, GeneralCouplingTransform, RealNVP
 from .elementwise import ElementWiseTransform
@@ -10,6 +11,7 @@ from .spline import NCSF, NSF
 
 __all__ = [
     "BPF",
+    "GMM",
     "MAF",
     "MNN",
     "NAF",

@@ -4,7 +4,8 @@ shape bookkeeping only; every arithmetic result comes out of a HIP kernel in lib
 All functions require tensors on a HIP device (`tensor.is_cuda`) in float32 or float64 and raise
 otherwise — there is no CPU or eager-PyTorch fallback.  One documented exception: the monotone networks of a neural autoregressive
 flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shapes their kernel does not serve, for float64 and for
-calls that need gradients (no adjoint kernel yet).
+calls that need gradients (no adjoint kernel yet).  Likewise the Gaussian mixture density (gmm_log_prob) runs the reference's expressions as torch ops
+ON THE DEVICE outside its kernels' envelope (features or components above 64, sample dimensions broadcast over a batch of mixtures).
 """
 
 from __future__ import annotations
@@ -878,3 +879,140 @@ def umnn_inverse(y: Tensor, signal: Tensor, constant, network, feat=None, bound:
     _C.check(_C.lib().zk_umnn_inverse(a, _stream()), "zk_umnn_inverse")
     del data
     return x.reshape(shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# Gaussian mixture model: zk_gmm_log_prob / zk_gmm_backward, torch ops when the kernel does not serve the call
+# ------------------------------------------------------------------------------------------------
+
+GMM_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_gmm.py measures the kernels against it; double backward needs it)
+GMM_COVARIANCE = {"full": 0, "diagonal": 1, "spherical": 2}
+
+
+def gmm_sizes(D: int, K: int, covariance_type: str, tied: bool) -> list[int]:
+    """Lengths of the segments of one row of phi: logits | loc | diag [| tril] (include/zuko_amd.h: zk_gmm_args_v1)."""
+    if covariance_type not in GMM_COVARIANCE:
+        raise NotImplementedError(f"Unknown covariance type '{covariance_type}'.")
+    lead = 1 if tied else K
+    sizes = [K, K * D, lead * (1 if covariance_type == "spherical" else D)]
+    if covariance_type == "full":
+        sizes.append(lead * (D * (D - 1) // 2))
+    return sizes
+
+
+def gmm_supported(D: int, K: int, covariance_type: str, tied: bool, dtype=torch.float32) -> bool:
+    """True when zk_gmm_log_prob / zk_gmm_backward serve the shape: 1 <= D <= 64, 1 <= K <= 64, float32 / float64 (bfloat16 is widened)."""
+    return (covariance_type in GMM_COVARIANCE and dtype in (torch.float32, torch.float64, torch.bfloat16)
+            and _C.lib().zk_gmm_total(int(D), int(K), GMM_COVARIANCE[covariance_type], int(bool(tied))) > 0)
+
+
+def _gmm_torch_log_prob(x: Tensor, phi: Tensor, K: int, covariance_type: str, tied: bool, epsilon: float) -> Tensor:
+    """The reference's expressions on torch ops (zuko/mixtures.py: GMM.forward, zuko/distributions.py: Mixture.log_prob): the path of every
+    call the kernel does not serve, and the baseline of scripts/bench_gmm.py.  phi [..., total] broadcasts against x [..., D]."""
+    D, lead, full = x.shape[-1], 1 if tied else K, covariance_type == "full"
+    parts = phi.split(gmm_sizes(D, K, covariance_type, tied), dim=-1)
+    batch = phi.shape[:-1]
+    logits, loc = parts[0], parts[1].reshape(*batch, K, D)
+    scale = parts[2].reshape(*batch, lead, -1).exp() + epsilon
+    xk = x.unsqueeze(-2)
+    if full:
+        factor = torch.diag_embed(scale)
+        below = torch.ones_like(factor, dtype=torch.bool).tril(-1)
+        factor = factor.masked_scatter(below, parts[3].reshape(*batch, lead, -1))
+        log_p = torch.distributions.MultivariateNormal(loc, scale_tril=factor, validate_args=False).log_prob(xk)
+    else:
+        log_p = torch.distributions.Normal(loc, scale, validate_args=False).log_prob(xk).sum(dim=-1)
+    return torch.logsumexp(torch.log_softmax(logits, dim=-1) + log_p, dim=-1)
+
+
+def _gmm_rows(t: Tensor, width: int) -> tuple[Tensor, int]:
+    """t [..., width] as a [N, width] block the kernels can address (unit column stride, row stride >= width): a view where possible."""
+    t2 = t.reshape(-1, width)
+    if t2.stride(1) != 1 or (t2.shape[0] > 1 and t2.stride(0) < width):
+        t2 = t2.contiguous()
+    return t2, (t2.stride(0) if t2.shape[0] > 1 else max(t2.stride(0), width))
+
+
+def _gmm_kernel_serves(x: Tensor, phi: Tensor, K: int, covariance_type: str, tied: bool) -> bool:
+    D = x.shape[-1]
+    return (GMM_KERNEL and x.dtype == phi.dtype and gmm_supported(D, K, covariance_type, tied, x.dtype) and x.numel() > 0
+            and (phi.dim() == 1 or phi.shape[:-1] == x.shape[:-1]))
+
+
+def _gmm_args(x2: Tensor, ldx: int, phi2: Tensor, ld_phi: int, K: int, covariance_type: str, tied: bool, epsilon: float, **extra):
+    return _C.args("zk_gmm_args_v1", dtype=_dtype_code(x2), N=x2.shape[0], D=x2.shape[1], K=K, covariance=GMM_COVARIANCE[covariance_type], tied=int(bool(tied)),
+                   epsilon=float(epsilon), x=x2.data_ptr(), ldx=ldx, phi=phi2.data_ptr(), ld_phi=ld_phi, **extra)
+
+
+def _gmm_operands(x: Tensor, phi: Tensor, K: int, covariance_type: str, tied: bool):
+    D = x.shape[-1]
+    total = sum(gmm_sizes(D, K, covariance_type, tied))
+    if phi.shape[-1] != total:
+        raise ValueError(f"zuko_amd: phi has {phi.shape[-1]} columns, a {covariance_type} mixture of {K} components in {D} features needs {total}")
+    x2, ldx = _gmm_rows(x, D)
+    if phi.dim() == 1:
+        return x2, ldx, phi.contiguous(), 0, total
+    phi2, ld_phi = _gmm_rows(phi, total)
+    return x2, ldx, phi2, ld_phi, total
+
+
+def gmm_forward_kernel(x: Tensor, phi: Tensor, components: int, covariance_type: str, tied: bool, epsilon: float) -> Tensor:
+    """One zk_gmm_log_prob launch on detached operands (the caller checked _gmm_kernel_serves)."""
+    x2, ldx, phi2, ld_phi, _ = _gmm_operands(x, phi, components, covariance_type, tied)
+    out = torch.empty(x2.shape[0], dtype=x.dtype, device=x.device)
+    a = _gmm_args(x2, ldx, phi2, ld_phi, components, covariance_type, tied, epsilon, out=out.data_ptr())
+    _C.check(_C.lib().zk_gmm_log_prob(a, _stream()), "zk_gmm_log_prob")
+    return out.reshape(x.shape[:-1])
+
+
+def gmm_backward(x: Tensor, phi: Tensor, g: Tensor, components: int, covariance_type: str = "full", tied: bool = False, epsilon: float = 1e-6,
+                 need_x: bool = True, need_phi: bool = True, gx: Tensor | None = None, gphi: Tensor | None = None):
+    """(gx, gphi) of sum(g * gmm_log_prob(x, phi)) in one zk_gmm_backward launch (plus the reduction of the partial sums when phi is one shared
+    row).  gx [N, D] / gphi [N, total] may be given as views with a row stride (unit column stride); an output that is not needed is None."""
+    _require_device(x, phi, g)
+    if not _gmm_kernel_serves(x, phi, components, covariance_type, tied):
+        raise RuntimeError("zuko_amd: zk_gmm_backward does not serve this call (shape outside 1 <= D, K <= 64, mixed dtypes, or phi not one row per row of x)")
+    x2, ldx, phi2, ld_phi, total = _gmm_operands(x, phi, components, covariance_type, tied)
+    N, D = x2.shape
+    gc = g.expand(x.shape[:-1]).reshape(-1).contiguous()
+    extra = {}
+    if need_x:
+        if gx is None:
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        gx2, ld_gx = _gmm_rows(gx, D)
+        assert gx2.data_ptr() == gx.data_ptr() and gx.dtype == x.dtype, "gx must be addressable in place"
+        extra.update(gx=gx2.data_ptr(), ld_gx=ld_gx)
+    work = None
+    if need_phi:
+        if gphi is None:
+            gphi = torch.empty(phi.shape, dtype=phi.dtype, device=phi.device)
+        if ld_phi == 0:
+            assert gphi.is_contiguous() and gphi.numel() == total
+            n = _C.lib().zk_gmm_workspace_floats(_dtype_code(x2), N, D, components, GMM_COVARIANCE[covariance_type], int(bool(tied)))
+            work = torch.empty(n, dtype=x.dtype, device=x.device)
+            extra.update(gphi=gphi.data_ptr(), work=work.data_ptr())
+        else:
+            gphi2, ld_gphi = _gmm_rows(gphi, total)
+            assert gphi2.data_ptr() == gphi.data_ptr() and gphi.dtype == x.dtype, "gphi must be addressable in place"
+            extra.update(gphi=gphi2.data_ptr(), ld_gphi=ld_gphi)
+    a = _gmm_args(x2, ldx, phi2, ld_phi, components, covariance_type, tied, epsilon, g=gc.data_ptr(), **extra)
+    _C.check(_C.lib().zk_gmm_backward(a, _stream()), "zk_gmm_backward")
+    del work  # (stream-ordered allocator: the block is reused only by later work of this stream)
+    return (gx if need_x else None), (gphi if need_phi else None)
+
+
+def gmm_log_prob(x: Tensor, phi: Tensor, components: int, covariance_type: str = "full", tied: bool = False, epsilon: float = 1e-6) -> Tensor:
+    """log p(x) of the Gaussian mixture whose parameters are the rows of phi = logits | loc | diag [| tril] (zuko/mixtures.py: _get_gmm_shapes).
+    x [..., D]; phi [total] (one mixture for every row) or [..., total].  zk_gmm_log_prob (and zk_gmm_backward under autograd) when
+    1 <= D, components <= 64 and phi is one row or has x's batch shape; otherwise — sample dimensions broadcast over a batch of mixtures, larger
+    shapes, GMM_KERNEL = False — the reference's expressions as torch ops on the device."""
+    _require_device(x, phi)
+    if x.dtype == torch.bfloat16 or phi.dtype == torch.bfloat16:  # storage type only: the density is evaluated and returned in fp32
+        x, phi = x.float(), phi.float()
+    if not _gmm_kernel_serves(x, phi, components, covariance_type, tied):
+        return _gmm_torch_log_prob(x, phi, components, covariance_type, tied, epsilon)
+    from . import autograd as AG
+
+    if AG.needs_grad(x, phi):
+        return AG.GmmLogProbFn.apply(x, phi, components, covariance_type, tied, epsilon)
+    return gmm_forward_kernel(x, phi, components, covariance_type, tied, epsilon)
