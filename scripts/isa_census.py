@@ -71,7 +71,8 @@ def main(parent: str, branch: str, files) -> int:
         print(f"\n### {f}\n\n| kernel | " + " | ".join(COLS) + " | gate |\n|---|" + "---|" * (len(COLS) + 1))
         for name in sorted(set(a) | set(b)):
             if name not in a or name not in b:
-                print(f"| `{pretty[name]}` | only in {'parent' if name in a else 'branch'} |")
+                one = a.get(name) or b[name]  # (a kernel that was renamed or replaced: its own counts, so that the two sides can be read next to each other)
+                print(f"| `{pretty[name]}` | " + " | ".join(str(one[c]) for c in COLS) + f" | only in {'parent' if name in a else 'branch'} |")
                 bad += 1
                 continue
             pa, br = a[name], b[name]

@@ -101,10 +101,10 @@ def test_rqs_golden(dev, tag):
             close(t1.inv(yl), g["x_lin"], "roundtrip", 1e-9)
 
 
-@pytest.mark.parametrize("shape,K", [((1000, 64), 8), ((257, 3), 8), ((33, 200), 8), ((5, 7, 11), 4), ((64, 16), 16), ((40, 6), 5), ((0, 8), 8), ((3, 1), 8)])
+@pytest.mark.parametrize("shape,K", [((1000, 64), 8), ((257, 3), 8), ((33, 200), 8), ((5, 7, 11), 4), ((64, 16), 16), ((40, 6), 5), ((0, 8), 8), ((3, 1), 8), ((40, 6), 64)])
 def test_rqs_vs_oracle_shapes(dev, shape, K):
     """Packed phi (LDS-staged path), ragged / non-power-of-two feature counts, D > 64, 3-d batches,
-    generic bin counts, empty input."""
+    generic bin counts (K = 5, and K = 64: the cap of the run-time path), empty input."""
     import zuko_amd.transforms as ZT
     from zuko_amd.utils import unpack
 
@@ -284,6 +284,110 @@ def test_bernstein_eps_is_a_run_time_argument(dev, bounded, eps):
         ry, rl = O.bern_forward(theta.float(), x.float(), bounded, eps=eps)
         assert_parity(y32, ry, oy, f"bernstein eps={eps} bounded={bounded} f32: y")
         assert_parity(l32, rl, ol, f"bernstein eps={eps} bounded={bounded} f32: ladj")
+
+
+def test_rqs_bin_count_above_the_cap_fails_cleanly(dev):
+    """K = 65 is one more than the run-time path is built for (ZK_RQS_KMAX): an error from the entry point, no launch."""
+    import zuko_amd.transforms as ZT
+
+    K = 65
+    gen = torch.Generator().manual_seed(65)
+    phi = torch.randn(40, 6, 3 * K - 1, generator=gen).to(dev)
+    x = torch.randn(40, 6, generator=gen).to(dev)
+    t = ZT.MonotonicRQSTransform(phi[..., :K], phi[..., K : 2 * K], phi[..., 2 * K :])
+    with torch.no_grad():
+        with pytest.raises(RuntimeError, match="zk_rqs_forward"):
+            t.call_and_ladj(x)
+        with pytest.raises(RuntimeError, match="zk_rqs_inverse"):
+            t.inv(x)
+
+
+# Coefficient counts with no register-resident instantiation (csrc/elementwise.hip: launch_bern) take the run-time count: NC = 9 is the
+# smallest such count both maps reach, NC = 42 a middle one, NC = 72 the cap.  D = 70 > 64 takes the segmented path of the driver.
+# float64 bars: 1e-12 up to NC = 42; at NC = 72 the oracle's lgamma-based Beta density of degree 71 is itself 2.6e-12 from a float64
+# emulation of the closed forms in ladj (5.3e-13 in y), so the bar there is 1e-10 — 40x that distance, far below any wrong coefficient.
+BERN_RUNTIME_CASES = [(False, 7, (40, 6), 1e-12), (True, 4, (40, 6), 1e-12), (False, 40, (40, 6), 1e-12), (False, 70, (40, 6), 1e-10), (True, 67, (40, 6), 1e-10),
+                      (False, 7, (3, 70), 1e-12)]
+
+
+@pytest.mark.parametrize("bounded,M,shape,tol64", BERN_RUNTIME_CASES)
+def test_bernstein_run_time_coefficient_counts(dev, bounded, M, shape, tol64):
+    """Forward, ladj and inverse of the run-time-count path in float64 and float32 against the oracle, with inputs in both linear tails and
+    beyond the bound; strided parameters take the other instantiation and give the same numbers."""
+    import zuko_amd.transforms as ZT
+
+    g = torch.Generator().manual_seed(1000 * M + shape[1] + int(bounded))
+    theta = torch.randn(*shape, M, generator=g, dtype=torch.float64)
+    x = torch.randn(*shape, generator=g, dtype=torch.float64) * 3.5
+    x[0, 0], x[0, 1], x[1, 0], x[1, 1] = 4.999995, -4.999996, 5.2, -5.5  # both tails (|u - 1/2| >= 1/2 - eps), beyond the bound
+    cls = ZT.BoundedBernsteinTransform if bounded else ZT.BernsteinTransform
+    what = f"bernstein M={M} bounded={bounded} {shape}"
+    oy, ol = O.bern_forward(theta, x, bounded)
+    ox = O.bern_inverse(theta, oy, bounded)
+    with torch.no_grad():
+        for dt, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+            th = theta.to(dt).to(dev)
+            wide = torch.zeros(*shape, M + 3, dtype=dt, device=dev)
+            wide[..., :M] = th
+            t, ts = cls(th), cls(wide[..., :M])  # one packed buffer / element stride M + 3
+            xin, yin = x.to(dt).to(dev), oy.to(dt).to(dev)
+            y, ladj = t.call_and_ladj(xin)
+            xi = t.inv(yin)
+            y2, l2 = ts.call_and_ladj(xin)
+            close(y2, y, f"{what} {tag}: strided y", 0)
+            close(l2, ladj, f"{what} {tag}: strided ladj", 0)
+            close(ts.inv(yin), xi, f"{what} {tag}: strided inverse", 0)
+            if tag == "f64":
+                assert_f64(y, oy, f"{what} f64: y", tol64)
+                assert_f64(ladj, ol, f"{what} f64: ladj", tol64)
+                assert_f64(xi, ox, f"{what} f64: inverse (24-step bisection: interval 10 / 2^24)", 10.0 / 2**24)
+            else:
+                ry, rl = O.bern_forward(theta.float(), x.float(), bounded)
+                assert_parity(y, ry, oy, f"{what} f32: y")
+                assert_parity(ladj, rl, ol, f"{what} f32: ladj")
+                assert_parity(xi, O.bern_inverse(theta.float(), oy.float(), bounded), O.bern_inverse(theta, oy.float().double(), bounded), f"{what} f32: inverse (24-step bisection)")
+
+
+def test_bernstein_above_the_cap_is_refused():
+    import zuko_amd.transforms as ZT
+
+    with pytest.raises(NotImplementedError):
+        ZT.BernsteinTransform(torch.zeros(4, 2, 71))  # NC = 73 > 72 constrained coefficients
+
+
+@pytest.mark.parametrize("P,L1", [(2, 3), (4, 2)])
+@pytest.mark.parametrize("shifted", [False, True])
+def test_sos_run_time_shapes(dev, P, L1, shifted):
+    """Any layout other than SOSPF's 3 x 5 takes the run-time counts of sos_f / sos_g / sos_inv: float64 and float32 against the oracle,
+    with and without the shift constant."""
+    import zuko_amd.transforms as ZT
+
+    g = torch.Generator().manual_seed(100 * P + L1)
+    a = torch.randn(40, 6, P, L1, generator=g, dtype=torch.float64)
+    x = torch.randn(40, 6, generator=g, dtype=torch.float64) * 4.0
+    c = torch.randn(40, 6, generator=g, dtype=torch.float64) if shifted else None
+    shift = lambda v, cc: v if cc is None else v + cc
+    what = f"sos {P}x{L1} shifted={shifted}"
+    oy, ol = O.sos_forward(a, x)
+    oy = shift(oy, c)
+    ox = O.sos_inverse(a, oy if c is None else oy - c)
+    with torch.no_grad():
+        for dt, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+            ad, cd = a.to(dt).to(dev), None if c is None else c.to(dt).to(dev)
+            t = ZT.ShiftedSOSPolynomialTransform(ad, cd) if shifted else ZT.SOSPolynomialTransform(ad)
+            y, ladj = t.call_and_ladj(x.to(dt).to(dev))
+            xi = t.inv(oy.to(dt).to(dev))
+            if tag == "f64":
+                assert_f64(y, oy, f"{what} f64: y")
+                assert_f64(ladj, ol, f"{what} f64: ladj")
+                assert_f64(xi, ox, f"{what} f64: inverse (25-step bisection: interval 20 / 2^25)", 20.0 / 2**25)
+            else:
+                c32 = None if c is None else c.float()
+                ry, rl = O.sos_forward(a.float(), x.float())
+                assert_parity(y, shift(ry, c32), oy, f"{what} f32: y")
+                assert_parity(ladj, rl, ol, f"{what} f32: ladj")
+                y32 = oy.float()
+                assert_parity(xi, O.sos_inverse(a.float(), y32 if c32 is None else y32 - c32), O.sos_inverse(a, y32.double() if c is None else y32.double() - c32.double()), f"{what} f32: inverse (25-step bisection)")
 
 
 def test_normal_log_prob_and_sum(dev):

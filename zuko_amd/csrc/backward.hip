@@ -13,6 +13,7 @@
 // are sparse: only the two knots of the active bin receive gradient).
 // Data movement mirrors the forward kernel: a wave owns 64 consecutive elements, phi comes in and
 // g_phi goes out through a wave-private LDS image with 16-byte global accesses.
+#include "zk_stage.h"
 #include "zk_univariate_bwd.h"
 
 namespace zk {
@@ -48,19 +49,7 @@ template <int KIND, int K> __global__ __launch_bounds__(256) void uni_backward_k
     const int shift = (int)(((uintptr_t)src / 4) % 4);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    // stage phi (alignment-preserving image, as the forward kernel)
-    {
-      const int64_t n = cnt * TOTAL;
-      int head = shift ? 4 - shift : 0;
-      if (head > n) head = (int)n;
-      if (lane < head) wsh[shift + lane] = src[lane];
-      const int64_t body = (n - head) / 4;
-      const float4* vs = reinterpret_cast<const float4*>(src + head);
-      float4* vd = reinterpret_cast<float4*>(wsh + shift + head);
-      for (int64_t i = lane; i < body; i += 64) vd[i] = vs[i];
-      const int64_t done = head + body * 4;
-      if (lane < n - done) wsh[shift + done + lane] = src[done + lane];
-    }
+    stage_contiguous<float>(src, wsh, cnt * TOTAL, lane);  // (alignment-preserving image, as the forward kernel)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     const bool valid = lane < cnt;
@@ -86,19 +75,7 @@ template <int KIND, int K> __global__ __launch_bounds__(256) void uni_backward_k
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    {
-      float* dst = a.gphi + e0 * TOTAL;
-      const int64_t n = cnt * TOTAL;
-      int head = shift ? 4 - shift : 0;
-      if (head > n) head = (int)n;
-      if (lane < head) dst[lane] = wsh[shift + lane];
-      const int64_t body = (n - head) / 4;
-      float4* vd = reinterpret_cast<float4*>(dst + head);
-      const float4* vs = reinterpret_cast<const float4*>(wsh + shift + head);
-      for (int64_t i = lane; i < body; i += 64) vd[i] = vs[i];
-      const int64_t done = head + body * 4;
-      if (lane < n - done) dst[done + lane] = wsh[shift + done + lane];
-    }
+    unstage_contiguous<float>(wsh, shift, a.gphi + e0 * TOTAL, cnt * TOTAL, lane);
   }
 }
 

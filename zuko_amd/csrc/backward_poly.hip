@@ -26,8 +26,9 @@ template <int NV> __global__ __launch_bounds__(128) void sos_backward_kernel(Pol
     for (int i = 0; i < a.L1; ++i) { c.node[i] = T((float)a.node[i]); c.weight[i] = T((float)a.weight[i]); }
     auto ld = [&](int j) { return T::var(pe[j], 1 + j); };
     const T X = T::var(a.x[e], 0);
-    const T y = sos_f<T>(c, ld, X);
-    const T l = t_log<T>(sos_g<T>(c, ld, X));
+    const SosDyn<T> n(c);
+    const T y = sos_f<T>(n.P, n.L1, c, ld, X);
+    const T l = t_log<T>(sos_g<T>(n.P, n.L1, c, ld, X));
     const float gyv = a.gy ? a.gy[e] : 0.f;
     const float glv = a.gl ? (a.gl_reduced ? a.gl[e / a.D] : a.gl[e]) : 0.f;
     a.gx[e] = gyv * y.d[0] + glv * l.d[0];

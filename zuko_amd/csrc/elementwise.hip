@@ -18,6 +18,7 @@
 // instantiation which reads them straight from global memory.
 #include <stdlib.h>
 
+#include "zk_stage.h"
 #include "zk_univariate.h"
 
 namespace zk {
@@ -56,20 +57,25 @@ template <typename T> struct Ld {
 
 // ---- ops ---------------------------------------------------------------------------------------
 
+// the spline from its unconstrained parameters under math policy M, for a static or a run-time bin count
+template <typename T, class M, bool INV, class C, typename A>
+__device__ __forceinline__ void rqs_from_params(C K, const A& a, const Ld<T> (&ld)[3], T in, T& out, T& ladj, int& k) {
+  T kx[C::cap + 1], ky[C::cap + 1], kd[C::cap + 1];
+  rqs_axis_knots<T, M>(K, ld[0], T(a.bound), T(a.ls), kx);
+  rqs_axis_knots<T, M>(K, ld[1], T(a.bound), T(a.ls), ky);
+  rqs_slopes<T, M>(K, ld[2], T(a.ls), kd);
+  if (INV) { rqs_inv<T, M>(K, kx, ky, kd, in, out, k); ladj = T(0); }
+  else rqs_fwd<T, M>(K, kx, ky, kd, in, out, ladj, k);
+}
+
 template <typename T, int K, bool INV> struct RqsOp {
   static constexpr int NSEG = 3;
   static __device__ __forceinline__ int off(int s, int) { return s * K; }  // packed offsets 0, K, 2K
   template <typename A> static __device__ __forceinline__ void run(const A& a, const Ld<T> (&ld)[3], T in, T& out, T& ladj, int& k, int64_t e) {
-    typedef typename MathStd<T>::type M;
-    T kx[K + 1], ky[K + 1], kd[K + 1];
     if constexpr (sizeof(T) == 4) {  // fp32: the same arithmetic as the stream kernel and the fused epilogue
       rqs_lean<K, INV>(ld[0], ld[1], ld[2], a.lc, in, out, ladj, k, a.knots_out ? a.knots_out + e * (K + 1) : nullptr);
     } else {
-      rqs_axis_knots<T, K, M>(ld[0], T(a.bound), T(a.ls), kx);
-      rqs_axis_knots<T, K, M>(ld[1], T(a.bound), T(a.ls), ky);
-      rqs_slopes<T, K, M>(ld[2], T(a.ls), kd);
-      if (INV) { rqs_inv<T, K, M>(kx, ky, kd, in, out, k); ladj = T(0); }
-      else rqs_fwd<T, K, M>(kx, ky, kd, in, out, ladj, k);
+      rqs_from_params<T, typename MathStd<T>::type, INV>(Fixed<K>{}, a, ld, in, out, ladj, k);
     }
   }
 };
@@ -83,60 +89,18 @@ template <typename T, int K, bool INV> struct RqsKnotsOp {
     T kx[K + 1], ky[K + 1], kd[K + 1];
 #pragma unroll
     for (int j = 0; j <= K; ++j) { kx[j] = ld[0](j); ky[j] = ld[1](j); kd[j] = ld[2](j); }
-    if (INV) { rqs_inv<T, K>(kx, ky, kd, in, out, k); ladj = T(0); }
-    else rqs_fwd<T, K>(kx, ky, kd, in, out, ladj, k);
+    if (INV) { rqs_inv<T>(Fixed<K>{}, kx, ky, kd, in, out, k); ladj = T(0); }
+    else rqs_fwd<T>(Fixed<K>{}, kx, ky, kd, in, out, ladj, k);
   }
 };
 
-// any bin count up to 64: knots live in local arrays addressed at run time (slow path)
-#define ZK_RQS_KMAX 64
-template <typename T, bool INV> struct RqsGenericOp {
+// any bin count up to ZK_RQS_KMAX: the same functions with a run-time count, IEEE policy in both dtypes (slow path: the knots
+// live in local arrays addressed at run time)
+template <typename T, bool INV> struct RqsDynOp {
   static constexpr int NSEG = 3;
   static __device__ __forceinline__ int off(int s, int K) { return s * K; }
   template <typename A> static __device__ void run(const A& a, const Ld<T> (&ld)[3], T in, T& out, T& ladj, int& k, int64_t e) {
-    const int K = a.K;
-    const T bound = T(a.bound), ls = T(a.ls);
-    T kn[2][ZK_RQS_KMAX + 1], kd[ZK_RQS_KMAX + 1];
-    for (int ax = 0; ax < 2; ++ax) {
-      T m = softclip2<T>(ld[ax](0), ls);
-      for (int j = 1; j < K; ++j) { T v = softclip2<T>(ld[ax](j), ls); m = v > m ? v : m; }
-      T s = T(0);
-      for (int j = 0; j < K; ++j) { T e = t_exp(softclip2<T>(ld[ax](j), ls) - m); kn[ax][j + 1] = e; s += e; }
-      T r = T(1) / s, cum = T(0);
-      kn[ax][0] = bound * (T(2) * cum - T(1));
-      for (int j = 0; j < K; ++j) { cum += kn[ax][j + 1] * r; kn[ax][j + 1] = bound * (T(2) * cum - T(1)); }
-    }
-    kd[0] = T(1); kd[K] = T(1);
-    for (int j = 1; j < K; ++j) kd[j] = t_exp(softclip<T>(ld[2](j - 1), ls));
-    const T* srch = INV ? kn[1] : kn[0];
-    int cnt = 0;
-    for (int j = 0; j <= K; ++j) cnt += (srch[j] < in) ? 1 : 0;
-    k = cnt - 1;
-    bool inside = (k >= 0) && (k < K);
-    int kw = k < 0 ? k + K : (k >= K ? k - K : k);
-    T x0 = kn[0][kw], x1 = kn[0][kw + 1], y0 = kn[1][kw], y1 = kn[1][kw + 1], d0 = kd[kw], d1 = kd[kw + 1];
-    T m = inside ? T(1) : T(0);
-    T s = (y1 - y0) / (x1 - x0);
-    T t = (d0 + d1) - T(2) * s;
-    if (INV) {
-      T y_ = m * (in - y0);
-      T qa = (y1 - y0) * (s - d0) + y_ * t;
-      T qb = (y1 - y0) * d0 - y_ * t;
-      T qc = (-s) * y_;
-      T z = (T(2) * qc) / ((-qb) - t_sqrt(qb * qb - (T(4) * qa) * qc));
-      T xx = x0 + z * (x1 - x0);
-      out = inside ? xx : in;
-      ladj = T(0);
-    } else {
-      T z = (m * (in - x0)) / (x1 - x0);
-      T omz = T(1) - z;
-      T den = s + (t * z) * omz;
-      T num = s * (z * z) + (d0 * z) * omz;
-      T yy = y0 + ((y1 - y0) * num) / den;
-      T jac = ((s * s) * ((((T(2) * s) * z) * omz + d0 * (omz * omz)) + d1 * (z * z))) / (den * den);
-      out = inside ? yy : in;
-      ladj = m * t_log(jac);
-    }
+    rqs_from_params<T, MathIEEE<T>, INV>(Dyn<ZK_RQS_KMAX>{a.K}, a, ld, in, out, ladj, k);
   }
 };
 
@@ -165,163 +129,60 @@ template <typename T, bool INV> struct SosOp {
     k = 0;
     T cst = has_const ? ld[1](0) : T(0);
     if (c.P == 3 && c.L1 == 5) {
-      // SOSPF's layout (3 polynomials of degree 4): the 15 coefficients once into registers, the fully unrolled twins of sos_f / sos_g (same expression trees) —
-      // the generic path below re-reads every coefficient at each of the quadrature's nodes (and at each of the 25 bisection steps): 0.36 ms per layer at 2^16 x 64
+      // SOSPF's layout (3 polynomials of degree 4): the 15 coefficients once into registers and fixed counts — the run-time counts below re-read every
+      // coefficient at each of the quadrature's nodes (and at each of the 25 bisection steps): 0.36 ms per layer at 2^16 x 64
       T cf[15];
 #pragma unroll
       for (int j = 0; j < 15; ++j) cf[j] = ld[0](j);
-      auto lr = [&](int j) { return cf[j]; };
-      if (INV) {
-        const T yy = in - cst;
-        T lo = -c.bound, hi = c.bound;
-        for (int it = 0; it < a.n_bisect; ++it) {
-          const T mid = (lo + hi) / T(2);
-          const bool below = sos_f_static<T, 3, 5>(c, lr, mid) < yy;
-          lo = below ? mid : lo;
-          hi = below ? hi : mid;
-        }
-        out = (lo + hi) / T(2);
-        ladj = T(0);
-      } else {
-        out = sos_f_static<T, 3, 5>(c, lr, in) + cst;
-        ladj = t_log(sos_g_static<T, 3, 5>(c, lr, in));
-      }
-      return;
+      eval(Fixed<3>{}, Fixed<5>{}, a, [&](int j) { return cf[j]; }, in, cst, out, ladj);
+    } else {
+      const SosDyn<T> n(c);
+      eval(n.P, n.L1, a, ld[0], in, cst, out, ladj);
     }
+  }
+  template <class CP, class CL, typename A, typename LdA> __device__ __forceinline__ void eval(CP P, CL L1, const A& a, LdA lda, T in, T cst, T& out, T& ladj) const {
     if (INV) {
-      out = sos_inv<T>(c, ld[0], in - cst, a.n_bisect);
+      out = sos_inv<T>(P, L1, c, lda, in - cst, a.n_bisect);
       ladj = T(0);
     } else {
-      out = sos_f<T>(c, ld[0], in) + cst;
-      ladj = t_log(sos_g<T>(c, ld[0], in));
+      out = sos_f<T>(P, L1, c, lda, in) + cst;
+      ladj = t_log(sos_g<T>(P, L1, c, lda, in));
     }
   }
 };
+
+template <typename T, bool INV, class C, typename A> __device__ __forceinline__ void bern_from_params(C NC, const A& a, const Ld<T>& ld, T in, T& out, T& ladj) {
+  T th[C::cap];
+  const T bound = T(a.bound);
+  if (a.bounded) bern_theta_bounded<T>(NC, ld, bound, th);
+  else bern_theta_unbounded<T>(NC, ld, th);
+  const T eps = T(a.eps);
+  BernTails<T> t = bern_tails<T>(NC, th, a.bounded != 0, bound, eps);
+  if (INV) { out = bern_inv<T>(NC, th, t, bound, in, a.n_bisect, eps); ladj = T(0); }
+  else { T d; bern_fwd<T>(NC, th, t, bound, in, out, d, eps); ladj = t_log(d); }
+}
 
 template <typename T, int NC, bool INV> struct BernOp {
   static constexpr int NSEG = 1;
   static __device__ __forceinline__ int off(int, int) { return 0; }
   template <typename A> static __device__ __forceinline__ void run(const A& a, const Ld<T> (&ld)[3], T in, T& out, T& ladj, int& k, int64_t e) {
     k = 0;
-    T th[NC];
-    const T bound = T(a.bound);
-    if (a.bounded) bern_theta_bounded<T, NC>(ld[0], bound, th);
-    else bern_theta_unbounded<T, NC>(ld[0], th);
-    const T eps = T(a.eps);
-    BernTails<T> t = bern_tails<T, NC>(th, a.bounded != 0, bound, eps);
-    if (INV) { out = bern_inv<T, NC>(th, t, bound, in, a.n_bisect, eps); ladj = T(0); }
-    else { T d; bern_fwd<T, NC>(th, t, bound, in, out, d, eps); ladj = t_log(d); }
+    bern_from_params<T, INV>(Fixed<NC>{}, a, ld[0], in, out, ladj);
   }
 };
 
-// any number of coefficients up to ZK_BERN_NCMAX: same expression trees as bern_* with run-time loops over local
-// arrays (slow path; the register-resident instantiations above cover BPF's default degree and the tested ones)
-#define ZK_BERN_NCMAX 72
-template <typename T, bool INV> struct BernGenericOp {
+// any number of constrained coefficients up to ZK_BERN_NCMAX (a.K): the same functions with a run-time count (slow path: the coefficients
+// live in local arrays addressed at run time; the register-resident instantiations above cover BPF's default degree and the tested ones)
+template <typename T, bool INV> struct BernDynOp {
   static constexpr int NSEG = 1;
   static __device__ __forceinline__ int off(int, int) { return 0; }
-  static __device__ void eval(const T* th, int NC, T u, T& val, T& dval) {
-    T b[ZK_BERN_NCMAX];
-    for (int i = 0; i < NC; ++i) b[i] = th[i];
-    const T v = T(1) - u;
-    for (int r = 1; r < NC - 1; ++r)
-      for (int i = 0; i < NC - r; ++i) b[i] = v * b[i] + u * b[i + 1];
-    dval = T(NC - 1) * (b[1] - b[0]);
-    val = v * b[0] + u * b[1];
-  }
-  static __device__ void fwd(const T* th, int NC, const BernTails<T>& t, T bound, T x, T& y, T& dydx, T eps) {
-    T u = (x + bound) / (T(2) * bound);
-    bool lo = u <= eps;
-    bool hi = u >= T(1) - eps;
-    T safe = (lo || hi) ? T(0.5) : u;
-    T val, dval;
-    eval(th, NC, safe, val, dval);
-    T ylo = t.slp0 * (u - eps) + t.off0;
-    T yhi = t.slp1 * ((u - T(1)) + eps) + t.off1;
-    y = lo ? ylo : val;
-    y = hi ? yhi : y;
-    T du = lo ? t.slp0 : dval;
-    du = hi ? t.slp1 : du;
-    dydx = du / (T(2) * bound);
-  }
   template <typename A> static __device__ void run(const A& a, const Ld<T> (&ld)[3], T in, T& out, T& ladj, int& k, int64_t e) {
     k = 0;
-    const int NC = a.K;  // constrained coefficients
-    const T bound = T(a.bound), eps = T(a.eps);
-    T th[ZK_BERN_NCMAX];
-    if (a.bounded) {  // bern_theta_bounded
-      const int n = NC - 5;
-      const T edge = (T(2) * bound) / T(n + 4);
-      const T span = T(2) * bound - T(4) * edge;
-      T m = ld[0](0);
-      for (int j = 1; j < n; ++j) { T v = ld[0](j); m = v > m ? v : m; }
-      T s = T(0);
-      for (int j = 0; j < n; ++j) { T ev = t_exp(ld[0](j) - m); th[3 + j] = ev; s += ev; }
-      T r = T(1) / s;
-      T cum = -bound;
-      th[0] = cum;
-      cum += edge; th[1] = cum;
-      cum += edge; th[2] = cum;
-      for (int j = 0; j < n; ++j) { cum += (th[3 + j] * r) * span; th[3 + j] = cum; }
-      cum += edge; th[n + 3] = cum;
-      cum += edge; th[n + 4] = cum;
-    } else {  // bern_theta_unbounded
-      const int n = NC - 2;
-      const T shift = T(0.69314718055994530942 * n / 2.0);
-      T cum = ld[0](0);
-      th[0] = cum - shift;
-      cum += softplus<T>(ld[0](1));
-      th[1] = cum - shift;
-      for (int j = 1; j < n; ++j) { cum += softplus<T>(ld[0](j)); th[j + 1] = cum - shift; }
-      cum += softplus<T>(ld[0](n - 1));
-      th[n + 1] = cum - shift;
-    }
-    BernTails<T> t;
-    if (a.bounded) { t.off0 = -bound; t.off1 = bound; t.slp0 = T(2) * bound; t.slp1 = T(2) * bound; }
-    else { eval(th, NC, eps, t.off0, t.slp0); eval(th, NC, T(1) - eps, t.off1, t.slp1); }
-    if (INV) {
-      T lo = -bound, hi = bound;
-      for (int it = 0; it < a.n_bisect; ++it) {
-        T mid = (lo + hi) / T(2);
-        T fy, d;
-        fwd(th, NC, t, bound, mid, fy, d, eps);
-        bool below = fy < in;
-        lo = below ? mid : lo;
-        hi = below ? hi : mid;
-      }
-      T x = (lo + hi) / T(2);
-      T xlo = (((in - t.off0) / t.slp0 + eps) * T(2)) * bound - bound;
-      T xhi = ((((in - t.off1) / t.slp1 - eps) + T(1)) * T(2)) * bound - bound;
-      x = (in <= t.off0) ? xlo : x;
-      x = (in >= t.off1) ? xhi : x;
-      out = x;
-      ladj = T(0);
-    } else {
-      T d;
-      fwd(th, NC, t, bound, in, out, d, eps);
-      ladj = t_log(d);
-    }
+    bern_from_params<T, INV>(Dyn<ZK_BERN_NCMAX>{a.K}, a, ld[0], in, out, ladj);
   }
 };
 
 // ---- the streaming driver ------------------------------------------------------------------------
-
-// copy `count` consecutive T's starting at global `src` into LDS `dst` such that dst keeps src's
-// alignment modulo 16 bytes; returns nothing, caller adds `shift` = ((uintptr_t)src / sizeof(T)) % VEC.
-template <typename T> __device__ __forceinline__ void stage_contiguous(const T* src, T* dst_aligned, int64_t count, int lane) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int shift = (int)(((uintptr_t)src / sizeof(T)) % VEC);
-  int head = shift ? (VEC - shift) : 0;
-  if (head > count) head = (int)count;
-  if (lane < head) dst_aligned[shift + lane] = src[lane];
-  const int64_t body = (count - head) / VEC;
-  const float4* vsrc = reinterpret_cast<const float4*>(src + head);
-  float4* vdst = reinterpret_cast<float4*>(dst_aligned + shift + head);
-  for (int64_t i = lane; i < body; i += ZK_WAVE) vdst[i] = vsrc[i];
-  const int64_t done = head + body * VEC;
-  const int tail = (int)(count - done);
-  if (lane < tail) dst_aligned[shift + done + lane] = src[done + lane];
-}
 
 template <typename T, bool PACKED, typename Op, typename RunFn>
 __device__ __forceinline__ void uni_driver(const UniArgs& a, T* sh, RunFn run) {
@@ -493,7 +354,7 @@ template <typename T, bool INV> static int launch_rqs(UniArgs a, int K, hipStrea
     case 16: return launch_uni<T, RqsOp<T, 16, INV>, RqsOp<T, 16, INV>>(a, lens, 3, st);
     default:
       if (K < 2 || K > ZK_RQS_KMAX) return ZK_EINVAL;
-      return launch_uni<T, RqsGenericOp<T, INV>, RqsGenericOp<T, INV>>(a, lens, 3, st);
+      return launch_uni<T, RqsDynOp<T, INV>, RqsDynOp<T, INV>>(a, lens, 3, st);
   }
 }
 
@@ -530,7 +391,7 @@ template <typename T, bool INV> static int launch_bern(UniArgs a, int M, hipStre
       if (NC < 3 || NC > ZK_BERN_NCMAX || (a.bounded ? M < 1 : M < 2)) return ZK_EINVAL;
       const int lens[1] = {M};
       a.K = NC;
-      return launch_uni<T, BernGenericOp<T, INV>, BernGenericOp<T, INV>>(a, lens, 1, st);
+      return launch_uni<T, BernDynOp<T, INV>, BernDynOp<T, INV>>(a, lens, 1, st);
     }
   }
 }

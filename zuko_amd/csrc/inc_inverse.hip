@@ -284,13 +284,13 @@ struct IncSos3x5 {  // ShiftedSOSPolynomialTransform, 3 polynomials of degree 4 
         fm = mid * h;
         sure = fabsf(fm - yy) > 3.8147e-6f * (fabsf(mid) * ha);  // 64 * 2^-24 of the magnitudes that enter either evaluation (a NaN is never sure)
       }
-      if (!sure) fm = sos_f_static<float, 3, 5>(a.sos, ld, mid);
+      if (!sure) fm = sos_f<float>(Fixed<3>{}, Fixed<5>{}, a.sos, ld, mid);
       const bool below = fm < yy;
       lo = below ? mid : lo;
       hi = below ? hi : mid;
     }
     x = (lo + hi) / 2.f;
-    lj = t_log(sos_g_static<float, 3, 5>(a.sos, ld, x));
+    lj = t_log(sos_g<float>(Fixed<3>{}, Fixed<5>{}, a.sos, ld, x));
   }
 };
 struct IncBern17 {  // BoundedBernsteinTransform of degree 16: 17 unconstrained parameters -> 22 constrained coefficients (zuko/transforms.py:779-831)
@@ -298,8 +298,8 @@ struct IncBern17 {  // BoundedBernsteinTransform of degree 16: 17 unconstrained 
   template <typename A> static __device__ __forceinline__ void inv(const float* p, const A& a, float y, float& x, float& lj) {
     constexpr int NC = 22, n = NC - 1;
     float th[NC];
-    bern_theta_bounded<float, NC>([&](int j) { return p[j]; }, a.bound, th);
-    const BernTails<float> t = bern_tails<float, NC>(th, true, a.bound, a.eps);
+    bern_theta_bounded<float>(Fixed<NC>{}, [&](int j) { return p[j]; }, a.bound, th);
+    const BernTails<float> t = bern_tails<float>(Fixed<NC>{}, th, true, a.bound, a.eps);
     // C(21, i) th_i (the binomials are exact in float)
     constexpr float BIN[NC] = {1.f, 21.f, 210.f, 1330.f, 5985.f, 20349.f, 54264.f, 116280.f, 203490.f, 293930.f, 352716.f,
                                352716.f, 293930.f, 203490.f, 116280.f, 54264.f, 20349.f, 5985.f, 1330.f, 210.f, 21.f, 1.f};
@@ -330,7 +330,7 @@ struct IncBern17 {  // BoundedBernsteinTransform of degree 16: 17 unconstrained 
       }
       if (!sure) {
         float d;
-        bern_fwd<float, NC>(th, t, a.bound, mid, fm, d, a.eps);
+        bern_fwd<float>(Fixed<NC>{}, th, t, a.bound, mid, fm, d, a.eps);
       }
       const bool below = fm < y;
       lo = below ? mid : lo;
@@ -342,7 +342,7 @@ struct IncBern17 {  // BoundedBernsteinTransform of degree 16: 17 unconstrained 
     x = (y <= t.off0) ? xlo : x;
     x = (y >= t.off1) ? xhi : x;
     float fy, d;
-    bern_fwd<float, NC>(th, t, a.bound, x, fy, d, a.eps);
+    bern_fwd<float>(Fixed<NC>{}, th, t, a.bound, x, fy, d, a.eps);
     lj = t_log(d);
   }
 };

@@ -158,8 +158,8 @@ template <int P, int L1> struct UniSos {
   }
   template <typename Pa, typename A> static __device__ __forceinline__ void fwd(const Pa& p, int base, const A& a, float x, float& y, float& lj, int* k = nullptr, float* ks = nullptr) {
     auto ld = [&](int j) { return p(base + j); };
-    y = sos_f_static<float, P, L1>(a.sos, ld, x) + p(base + P * L1);
-    lj = t_log(sos_g_static<float, P, L1>(a.sos, ld, x));
+    y = sos_f<float>(Fixed<P>{}, Fixed<L1>{}, a.sos, ld, x) + p(base + P * L1);
+    lj = t_log(sos_g<float>(Fixed<P>{}, Fixed<L1>{}, a.sos, ld, x));
   }
 };
 // Bounded Bernstein polynomial (zuko/transforms.py:779-831) with NC - 5 unconstrained parameters.  FORWARD only.
@@ -168,10 +168,10 @@ template <int NC> struct UniBernBounded {
   template <bool INV> static __device__ __forceinline__ void poison(float* p, int base, float nan_or_zero) { p[base] += nan_or_zero; }  // (softmax: one NaN makes every coefficient NaN)
   template <typename Pa, typename A> static __device__ __forceinline__ void fwd(const Pa& p, int base, const A& a, float x, float& y, float& lj, int* k = nullptr, float* ks = nullptr) {
     float th[NC];
-    bern_theta_bounded<float, NC>([&](int j) { return p(base + j); }, a.bound, th);
-    const BernTails<float> t = bern_tails<float, NC>(th, true, a.bound, a.eps);
+    bern_theta_bounded<float>(Fixed<NC>{}, [&](int j) { return p(base + j); }, a.bound, th);
+    const BernTails<float> t = bern_tails<float>(Fixed<NC>{}, th, true, a.bound, a.eps);
     float d;
-    bern_fwd<float, NC>(th, t, a.bound, x, y, d, a.eps);
+    bern_fwd<float>(Fixed<NC>{}, th, t, a.bound, x, y, d, a.eps);
     lj = t_log(d);
   }
 };

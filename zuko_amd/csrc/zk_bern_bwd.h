@@ -14,12 +14,12 @@ template <int NC, int M, bool BOUNDED> __global__ __launch_bounds__(64) void ber
     auto ld = [&](int j) { return T::var(pe[j], 1 + j); };
     T th[NC];
     const T bound = T(a.bound);
-    if (BOUNDED) bern_theta_bounded<T, NC>(ld, bound, th);
-    else bern_theta_unbounded<T, NC>(ld, th);
+    if (BOUNDED) bern_theta_bounded<T>(Fixed<NC>{}, ld, bound, th);
+    else bern_theta_unbounded<T>(Fixed<NC>{}, ld, th);
     const T eps = T(a.eps);
-    const BernTails<T> tails = bern_tails<T, NC>(th, BOUNDED, bound, eps);
+    const BernTails<T> tails = bern_tails<T>(Fixed<NC>{}, th, BOUNDED, bound, eps);
     T y, dydx;
-    bern_fwd<T, NC>(th, tails, bound, T::var(a.x[e], 0), y, dydx, eps);
+    bern_fwd<T>(Fixed<NC>{}, th, tails, bound, T::var(a.x[e], 0), y, dydx, eps);
     const T l = t_log<T>(dydx);
     const float gyv = a.gy ? a.gy[e] : 0.f;
     const float glv = a.gl ? (a.gl_reduced ? a.gl[e / a.D] : a.gl[e]) : 0.f;
@@ -49,8 +49,8 @@ template <int NC, int M, bool BOUNDED> __global__ __launch_bounds__(128) void be
 #pragma unroll
     for (int j = 0; j < M; ++j) t[j] = pe[j];
     float th[NC];
-    if (BOUNDED) bern_theta_bounded<float, NC>([&](int j) { return t[j]; }, B, th);
-    else bern_theta_unbounded<float, NC>([&](int j) { return t[j]; }, th);
+    if (BOUNDED) bern_theta_bounded<float>(Fixed<NC>{}, [&](int j) { return t[j]; }, B, th);
+    else bern_theta_unbounded<float>(Fixed<NC>{}, [&](int j) { return t[j]; }, th);
     const float x = a.x[e];
     const float gyv = a.gy ? a.gy[e] : 0.f;
     const float glv = a.gl ? (a.gl_reduced ? a.gl[e / a.D] : a.gl[e]) : 0.f;

@@ -20,7 +20,7 @@ namespace zk {
 
 // ---------------------------------------------------------------------------------------------
 // math policies.  MathIEEE: correctly rounded division, ocml exp/log (<= 1 ulp) — the fp64 kernels and
-// the generic-K fp32 spline.  MathFast (fp32): v_rcp/v_exp/v_log based (a few ulp) — the affine
+// the fp32 spline with a run-time bin count (RqsDynOp).  MathFast (fp32): v_rcp/v_exp/v_log based (a few ulp) — the affine
 // epilogue of the fused conditioner kernel, whose parameters already carry ~1e-6 relative GEMM
 // summation-order noise.
 // ---------------------------------------------------------------------------------------------
@@ -75,6 +75,25 @@ struct MathFast {
 };
 
 // ---------------------------------------------------------------------------------------------
+// sizes.  Every function below that loops over bins / coefficients takes its size as a COUNT object: Fixed<N> is a
+// compile-time constant (the loops unroll fully and the local arrays live in registers), Dyn<CAP> carries a run-time
+// value <= CAP (the loops run to the value; the local arrays are sized by CAP and addressed at run time — the slow
+// paths of the standalone kernels for sizes that have no instantiation).  One body serves both; `unroll` is what its
+// loops hand to `#pragma unroll`: N, which no trip count exceeds, unrolls fully; 1 leaves a run-time loop as it is.
+// ---------------------------------------------------------------------------------------------
+template <int N> struct Fixed {
+  static constexpr int cap = N, unroll = N;
+  __device__ __forceinline__ constexpr operator int() const { return N; }
+};
+template <int CAP> struct Dyn {
+  static constexpr int cap = CAP, unroll = 1;
+  int n;
+  __device__ __forceinline__ operator int() const { return n; }
+};
+#define ZK_RQS_KMAX 64    /* bins of the generic spline path (Dyn<ZK_RQS_KMAX>) */
+#define ZK_BERN_NCMAX 72  /* constrained Bernstein coefficients of the generic path (Dyn<ZK_BERN_NCMAX>); ops.BERN_NC_MAX mirrors it */
+
+// ---------------------------------------------------------------------------------------------
 // soft clipping of unconstrained parameters (transforms.py:436, :480-482)
 // ---------------------------------------------------------------------------------------------
 template <typename T, class M = MathIEEE<T>> __device__ __forceinline__ T softclip(T v, T ls) { return M::div(v, T(1) + t_abs(M::div(v, ls))); }
@@ -99,16 +118,16 @@ template <typename T, class M = MathIEEE<T>> __device__ __forceinline__ T affine
 
 // softmax over K soft-clipped values followed by the padded cumulative sum mapped to [-B, B]
 // (transforms.py:480-481, 484-485, 488-489).  `ld(j)` returns the j-th unconstrained value.
-template <typename T, int K, class M = MathIEEE<T>, typename Ld> __device__ __forceinline__ void rqs_axis_knots(Ld ld, T bound, T ls, T (&knot)[K + 1]) {
-  T v[K];
+template <typename T, class M = MathIEEE<T>, class C, typename Ld> __device__ __forceinline__ void rqs_axis_knots(C K, Ld ld, T bound, T ls, T (&knot)[C::cap + 1]) {
+  T v[C::cap];
   T m;
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 0; j < K; ++j) {
     v[j] = softclip2<T, M>(ld(j), ls);
     m = (j == 0) ? v[0] : M::max(m, v[j]);
   }
   T s = T(0);
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 0; j < K; ++j) {
     v[j] = M::exp(v[j] - m);
     s += v[j];
@@ -116,7 +135,7 @@ template <typename T, int K, class M = MathIEEE<T>, typename Ld> __device__ __fo
   T r = M::div(T(1), s);
   T cum = T(0);
   knot[0] = M::knot(cum, bound);
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 0; j < K; ++j) {
     cum += v[j] * r;
     knot[j + 1] = M::knot(cum, bound);
@@ -126,10 +145,10 @@ template <typename T, int K, class M = MathIEEE<T>, typename Ld> __device__ __fo
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // knot slopes: exp(softclip(d)) inside, 1 at both ends (transforms.py:482, 486, 490)
-template <typename T, int K, class M = MathIEEE<T>, typename Ld> __device__ __forceinline__ void rqs_slopes(Ld ld, T ls, T (&kd)[K + 1]) {
+template <typename T, class M = MathIEEE<T>, class C, typename Ld> __device__ __forceinline__ void rqs_slopes(C K, Ld ld, T ls, T (&kd)[C::cap + 1]) {
   kd[0] = T(1);
   kd[K] = T(1);
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 1; j < K; ++j) kd[j] = M::exp(softclip<T, M>(ld(j - 1), ls));
 }
 
@@ -139,12 +158,13 @@ template <typename T, int K, class M = MathIEEE<T>, typename Ld> __device__ __fo
 // [first, last] knot (k = -1 or K, or NaN) the reference gathers the wrapped bin k % K
 // (transforms.py:502) and then masks the result; any finite bin gives the same masked outputs
 // (y = v, ladj = 0 * log(finite) or NaN for non-finite v), so the first / last bin is used here.
-template <typename T, int K>
-__device__ __forceinline__ int rqs_locate(const T (&ks)[K + 1], const T (&kx)[K + 1], const T (&ky)[K + 1], const T (&kd)[K + 1], T v, bool& inside, T& x0,
-                                          T& x1, T& y0, T& y1, T& d0, T& d1) {
+template <typename T, class C>
+__device__ __forceinline__ int rqs_locate(C count, const T (&ks)[C::cap + 1], const T (&kx)[C::cap + 1], const T (&ky)[C::cap + 1], const T (&kd)[C::cap + 1], T v,
+                                          bool& inside, T& x0, T& x1, T& y0, T& y1, T& d0, T& d1) {
+  const int K = count;  // (a plain int: with the conversion left in the loop bounds, backward.hip — built with FMA contraction — contracts other products)
   int cnt = (ks[0] < v) ? 1 : 0;
   x0 = kx[0]; x1 = kx[1]; y0 = ky[0]; y1 = ky[1]; d0 = kd[0]; d1 = kd[1];
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 1; j < K; ++j) {
     const bool c = ks[j] < v;
     cnt += c ? 1 : 0;
@@ -163,11 +183,11 @@ __device__ __forceinline__ int rqs_locate(const T (&ks)[K + 1], const T (&kx)[K 
 
 // forward value + log|dy/dx| (transforms.py:554-567).  Out-of-range / NaN / inf behaviour is
 // inherited from the literal `mask * ...` arithmetic of the reference.
-template <typename T, int K, class M = MathIEEE<T>>
-__device__ __forceinline__ void rqs_fwd(const T (&kx)[K + 1], const T (&ky)[K + 1], const T (&kd)[K + 1], T x, T& y, T& ladj, int& k) {
+template <typename T, class M = MathIEEE<T>, class C>
+__device__ __forceinline__ void rqs_fwd(C K, const T (&kx)[C::cap + 1], const T (&ky)[C::cap + 1], const T (&kd)[C::cap + 1], T x, T& y, T& ladj, int& k) {
   bool inside;
   T x0, x1, y0, y1, d0, d1;
-  k = rqs_locate<T, K>(kx, kx, ky, kd, x, inside, x0, x1, y0, y1, d0, d1);
+  k = rqs_locate<T>(K, kx, kx, ky, kd, x, inside, x0, x1, y0, y1, d0, d1);
   T m = inside ? T(1) : T(0);
   T s = M::div(y1 - y0, x1 - x0);
   T z = M::div(m * (x - x0), x1 - x0);
@@ -182,11 +202,11 @@ __device__ __forceinline__ void rqs_fwd(const T (&kx)[K + 1], const T (&ky)[K + 
 }
 
 // inverse value (transforms.py:534-548): bin search on the vertical knots, stable quadratic root
-template <typename T, int K, class M = MathIEEE<T>>
-__device__ __forceinline__ void rqs_inv(const T (&kx)[K + 1], const T (&ky)[K + 1], const T (&kd)[K + 1], T y, T& x, int& k) {
+template <typename T, class M = MathIEEE<T>, class C>
+__device__ __forceinline__ void rqs_inv(C K, const T (&kx)[C::cap + 1], const T (&ky)[C::cap + 1], const T (&kd)[C::cap + 1], T y, T& x, int& k) {
   bool inside;
   T x0, x1, y0, y1, d0, d1;
-  k = rqs_locate<T, K>(ky, kx, ky, kd, y, inside, x0, x1, y0, y1, d0, d1);
+  k = rqs_locate<T>(K, ky, kx, ky, kd, y, inside, x0, x1, y0, y1, d0, d1);
   T m = inside ? T(1) : T(0);
   T s = M::div(y1 - y0, x1 - x0);
   T y_ = m * (y - y0);
@@ -364,44 +384,22 @@ template <typename T> struct SosConst {
 };
 
 // g(x) = mean_p (1 + sum_j a_pj (x/B)^j)^2 + slope   (transforms.py:958-963)
-template <typename T, typename Ld> __device__ __forceinline__ T sos_g(const SosConst<T>& c, Ld ld, T x) {
+// The polynomial count P and the degree + 1, L1, are counts (above).  Fixed counts are for callers whose coefficients live in registers (the
+// fused kernels' epilogue, SOSPF's 3 x 5 layout: a run-time loop would index the register array through scratch memory); SosDyn reads both
+// from the constants (any other layout: every coefficient is re-read through `ld` at each of the quadrature's nodes).
+template <typename T> struct SosDyn {
+  Dyn<0> P;                  // (no array is sized by the number of polynomials)
+  Dyn<ZK_SOS_MAX_NODES> L1;
+  __device__ __forceinline__ SosDyn(const SosConst<T>& c) : P{c.P}, L1{c.L1} {}
+};
+template <typename T, class CP, class CL, typename Ld> __device__ __forceinline__ T sos_g(CP P, CL L1, const SosConst<T>& c, Ld ld, T x) {
   T u = x / c.bound;
   T acc = T(0);
-  for (int p = 0; p < c.P; ++p) {
+#pragma unroll CP::unroll
+  for (int p = 0; p < P; ++p) {
     T pw = T(1);  // u**0 == 1 for every u, NaN included (IEEE pow)
     T dot = T(0);
-    for (int j = 0; j < c.L1; ++j) {
-      dot += ld(p * c.L1 + j) * pw;
-      pw *= u;
-    }
-    T q = T(1) + dot;
-    acc += q * q;
-  }
-  return acc / T(c.P) + c.slope;
-}
-
-// f(x) = int_0^x g  by Gauss-Legendre on [0, x]  (transforms.py:911-918, utils.py:349-363)
-template <typename T, typename Ld> __device__ __forceinline__ T sos_f(const SosConst<T>& c, Ld ld, T x) {
-  T acc = T(0);
-  for (int i = 0; i < c.L1; ++i) {
-    T w = c.node[i];
-    // torch.lerp(0, x, w): a + w*(b-a) below one half, b - (b-a)*(1-w) above
-    T pt = (w < T(0.5)) ? (T(0) + w * (x - T(0))) : (x - (x - T(0)) * (T(1) - w));
-    acc += c.weight[i] * sos_g<T>(c, ld, pt);
-  }
-  return (x - T(0)) * acc;
-}
-
-// sos_g / sos_f with the polynomial count and the degree as template arguments (same expression trees, fully unrolled): for callers whose
-// coefficients live in registers (the fused kernels' epilogue: a run-time loop would index the register array through scratch memory)
-template <typename T, int P, int L1, typename Ld> __device__ __forceinline__ T sos_g_static(const SosConst<T>& c, Ld ld, T x) {
-  T u = x / c.bound;
-  T acc = T(0);
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    T pw = T(1);
-    T dot = T(0);
-#pragma unroll
+#pragma unroll CL::unroll
     for (int j = 0; j < L1; ++j) {
       dot += ld(p * L1 + j) * pw;
       pw *= u;
@@ -409,25 +407,28 @@ template <typename T, int P, int L1, typename Ld> __device__ __forceinline__ T s
     T q = T(1) + dot;
     acc += q * q;
   }
-  return acc / T(P) + c.slope;
+  return acc / T(int(P)) + c.slope;
 }
-template <typename T, int P, int L1, typename Ld> __device__ __forceinline__ T sos_f_static(const SosConst<T>& c, Ld ld, T x) {
+
+// f(x) = int_0^x g  by Gauss-Legendre on [0, x]  (transforms.py:911-918, utils.py:349-363)
+template <typename T, class CP, class CL, typename Ld> __device__ __forceinline__ T sos_f(CP P, CL L1, const SosConst<T>& c, Ld ld, T x) {
   T acc = T(0);
-#pragma unroll
+#pragma unroll CL::unroll
   for (int i = 0; i < L1; ++i) {
     T w = c.node[i];
+    // torch.lerp(0, x, w): a + w*(b-a) below one half, b - (b-a)*(1-w) above
     T pt = (w < T(0.5)) ? (T(0) + w * (x - T(0))) : (x - (x - T(0)) * (T(1) - w));
-    acc += c.weight[i] * sos_g_static<T, P, L1>(c, ld, pt);
+    acc += c.weight[i] * sos_g<T>(P, L1, c, ld, pt);
   }
   return (x - T(0)) * acc;
 }
 
 // fixed-count bisection on [-B, B] (utils.py:170-180; n = ceil(log2(2B/eps)), transforms.py:615)
-template <typename T, typename Ld> __device__ __forceinline__ T sos_inv(const SosConst<T>& c, Ld ld, T y, int n) {
+template <typename T, class CP, class CL, typename Ld> __device__ __forceinline__ T sos_inv(CP P, CL L1, const SosConst<T>& c, Ld ld, T y, int n) {
   T a = -c.bound, b = c.bound;
   for (int it = 0; it < n; ++it) {
     T mid = (a + b) / T(2);
-    bool below = sos_f<T>(c, ld, mid) < y;
+    bool below = sos_f<T>(P, L1, c, ld, mid) < y;
     a = below ? mid : a;
     b = below ? b : mid;
   }
@@ -445,14 +446,14 @@ template <typename T> __device__ __forceinline__ T softplus(T v) {  // torch sof
 
 // unbounded: theta = cumsum([t0, sp(t1), sp(t1), sp(t2), ..., sp(t_last), sp(t_last)]) - log(2) * n / 2
 // (transforms.py:703-727); n unconstrained -> NC = n + 2
-template <typename T, int NC, typename Ld> __device__ __forceinline__ void bern_theta_unbounded(Ld ld, T (&th)[NC]) {
-  constexpr int n = NC - 2;
+template <typename T, class C, typename Ld> __device__ __forceinline__ void bern_theta_unbounded(C NC, Ld ld, T (&th)[C::cap]) {
+  const int n = NC - 2;
   const T shift = T(0.69314718055994530942 * n / 2.0);
   T cum = ld(0);
   th[0] = cum - shift;
   cum += softplus<T>(ld(1));
   th[1] = cum - shift;
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 1; j < n; ++j) {
     cum += softplus<T>(ld(j));
     th[j + 1] = cum - shift;
@@ -463,19 +464,19 @@ template <typename T, int NC, typename Ld> __device__ __forceinline__ void bern_
 
 // bounded: theta = cumsum([-B, e, e, softmax(t) * (2B - 4e), e, e]),  e = 2B / (n + 4)
 // (transforms.py:797-818); n unconstrained -> NC = n + 5
-template <typename T, int NC, typename Ld> __device__ __forceinline__ void bern_theta_bounded(Ld ld, T bound, T (&th)[NC]) {
-  constexpr int n = NC - 5;
+template <typename T, class C, typename Ld> __device__ __forceinline__ void bern_theta_bounded(C NC, Ld ld, T bound, T (&th)[C::cap]) {
+  const int n = NC - 5;
   const T edge = (T(2) * bound) / T(n + 4);
   const T span = T(2) * bound - T(4) * edge;
-  T v[n];
+  T v[C::cap - 5];
   T m;
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 0; j < n; ++j) {
     v[j] = ld(j);
     m = (j == 0) ? v[0] : (v[j] > m ? v[j] : m);
   }
   T s = T(0);
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 0; j < n; ++j) {
     v[j] = t_exp(v[j] - m);
     s += v[j];
@@ -485,7 +486,7 @@ template <typename T, int NC, typename Ld> __device__ __forceinline__ void bern_
   th[0] = cum;
   cum += edge; th[1] = cum;
   cum += edge; th[2] = cum;
-#pragma unroll
+#pragma unroll C::unroll
   for (int j = 0; j < n; ++j) {
     cum += (v[j] * r) * span;
     th[3 + j] = cum;
@@ -494,13 +495,13 @@ template <typename T, int NC, typename Ld> __device__ __forceinline__ void bern_
   cum += edge; th[n + 4] = cum;
 }
 
-// binomial C(n, k) at compile time (exact in double up to n = 56)
+// binomial C(n, k): folded into constants for a Fixed count (exact in double up to n = 56), evaluated in place for a Dyn count
 constexpr double zk_binom(int n, int k) {
   double c = 1.0;
   for (int i = 1; i <= k; ++i) c = c * (double)(n - k + i) / (double)i;
   return c;
 }
-template <typename T> __device__ __forceinline__ T zk_ipow(T w, int n) {  // w^n, n a compile-time constant at every call site
+template <typename T> __device__ __forceinline__ T zk_ipow(T w, int n) {  // w^n
   T r = T(1), b = w;
   for (int e = n; e > 0; e >>= 1) {
     if (e & 1) r = r * b;
@@ -516,15 +517,15 @@ template <typename T> __device__ __forceinline__ T zk_ipow(T w, int n) {  // w^n
 // numbers of size |theta| that agree in their leading digits wherever the polynomial is flat — the one comparison of the golden sets whose log-derivative sat
 // 2.9x further from float64 than the float32 reference's; a second de Casteljau sweep over the differences fixed that at +30 % on the fused BPF layer, this form
 // at no cost.)
-template <typename T, int NC> __device__ __forceinline__ void bern_eval(const T (&th)[NC], T u, T& val, T& dval) {
-  constexpr int M = NC - 1;
+template <typename T, class C> __device__ __forceinline__ void bern_eval(C NC, const T (&th)[C::cap], T u, T& val, T& dval) {
+  const int M = NC - 1;
   const T v = T(1) - u;
   // the derivative first, straight from theta (no array of differences: with one the fused Bernstein layer spilled 30 registers, and a spilled
   // accumulator of the matrix instruction came back wrong in 1 launch of 8 — tests/test_gpu_flows.py::test_polynomial_flows_run_on_a_fused_split_kernel)
   {
     const T sr = u / v, rr = v / u;
     T hA = (th[M] - th[M - 1]) * T(zk_binom(M - 1, M - 1)), hB = (th[1] - th[0]) * T(zk_binom(M - 1, 0));
-#pragma unroll
+#pragma unroll C::unroll
     for (int i = 1; i < M; ++i) {
       hA = hA * sr + (th[M - i] - th[M - 1 - i]) * T(zk_binom(M - 1, M - 1 - i));
       hB = hB * rr + (th[i + 1] - th[i]) * T(zk_binom(M - 1, i));
@@ -532,12 +533,12 @@ template <typename T, int NC> __device__ __forceinline__ void bern_eval(const T 
     const bool low = u <= T(0.5);
     dval = T(M) * ((low ? hA : hB) * zk_ipow<T>(low ? v : u, M - 1));
   }
-  T b[NC];
-#pragma unroll
+  T b[C::cap];
+#pragma unroll C::unroll
   for (int i = 0; i < NC; ++i) b[i] = th[i];
-#pragma unroll
+#pragma unroll C::unroll
   for (int r = 1; r < NC - 1; ++r) {
-#pragma unroll
+#pragma unroll C::unroll
     for (int i = 0; i < NC - r; ++i) b[i] = v * b[i] + u * b[i + 1];
   }
   val = v * b[0] + u * b[1];
@@ -546,26 +547,26 @@ template <typename T, int NC> __device__ __forceinline__ void bern_eval(const T 
 template <typename T> struct BernTails { T off0, off1, slp0, slp1; };
 
 // offsets/slopes of the linear continuation (transforms.py:685-701 unbounded, :820-831 bounded)
-template <typename T, int NC> __device__ __forceinline__ BernTails<T> bern_tails(const T (&th)[NC], bool bounded, T bound, T eps) {
+template <typename T, class C> __device__ __forceinline__ BernTails<T> bern_tails(C NC, const T (&th)[C::cap], bool bounded, T bound, T eps) {
   BernTails<T> t;
   if (bounded) {
     t.off0 = -bound; t.off1 = bound; t.slp0 = T(2) * bound; t.slp1 = T(2) * bound;
   } else {
-    bern_eval<T, NC>(th, eps, t.off0, t.slp0);
-    bern_eval<T, NC>(th, T(1) - eps, t.off1, t.slp1);
+    bern_eval<T>(NC, th, eps, t.off0, t.slp0);
+    bern_eval<T>(NC, th, T(1) - eps, t.off1, t.slp1);
   }
   return t;
 }
 
 // y = f(x) and dy/dx (transforms.py:742-760; derivative = what autograd yields at :623-637)
-template <typename T, int NC>
-__device__ __forceinline__ void bern_fwd(const T (&th)[NC], const BernTails<T>& t, T bound, T x, T& y, T& dydx, T eps) {
+template <typename T, class C>
+__device__ __forceinline__ void bern_fwd(C NC, const T (&th)[C::cap], const BernTails<T>& t, T bound, T x, T& y, T& dydx, T eps) {
   T u = (x + bound) / (T(2) * bound);
   bool lo = u <= eps;
   bool hi = u >= T(1) - eps;
   T safe = (lo || hi) ? T(0.5) : u;
   T val, dval;
-  bern_eval<T, NC>(th, safe, val, dval);
+  bern_eval<T>(NC, th, safe, val, dval);
   T ylo = t.slp0 * (u - eps) + t.off0;
   T yhi = t.slp1 * ((u - T(1)) + eps) + t.off1;
   y = lo ? ylo : val;
@@ -576,12 +577,12 @@ __device__ __forceinline__ void bern_fwd(const T (&th)[NC], const BernTails<T>& 
 }
 
 // x = f^{-1}(y): n-step bisection on [-B, B] + closed-form tails (transforms.py:762-777, :609-617)
-template <typename T, int NC> __device__ __forceinline__ T bern_inv(const T (&th)[NC], const BernTails<T>& t, T bound, T y, int n, T eps) {
+template <typename T, class C> __device__ __forceinline__ T bern_inv(C NC, const T (&th)[C::cap], const BernTails<T>& t, T bound, T y, int n, T eps) {
   T a = -bound, b = bound;
   for (int it = 0; it < n; ++it) {
     T mid = (a + b) / T(2);
     T fy, d;
-    bern_fwd<T, NC>(th, t, bound, mid, fy, d, eps);
+    bern_fwd<T>(NC, th, t, bound, mid, fy, d, eps);
     bool below = fy < y;
     a = below ? mid : a;
     b = below ? b : mid;

@@ -94,7 +94,7 @@ template <int K> __device__ __forceinline__ void rqs_backward_element(const floa
   }
   bool inside;
   float x0, x1, y0, y1, d0, d1;
-  const int k = rqs_locate<float, K>(kx, kx, ky, kd, x, inside, x0, x1, y0, y1, d0, d1);
+  const int k = rqs_locate<float>(Fixed<K>{}, kx, kx, ky, kd, x, inside, x0, x1, y0, y1, d0, d1);
 #pragma unroll
   for (int i = 0; i < TOTAL; ++i) g[i] = 0.f;
   if (!inside) { gxv = gyv; return; }  // identity outside [-B, B]: y = x, ladj = 0, no parameter gradient

@@ -350,7 +350,7 @@ def sos_inverse(y: Tensor, a: Tensor, constant: Tensor | None = None, slope: flo
 # ------------------------------------------------------------------------------------------------
 
 BERN_EPS = 1e-6
-BERN_NC_MAX = 72  # ZK_BERN_NCMAX of csrc/elementwise.hip
+BERN_NC_MAX = 72  # ZK_BERN_NCMAX of csrc/zk_univariate.h
 
 
 @_bf16_trains_in_f32
