@@ -770,6 +770,59 @@ int zk_gmm_workspace_floats(int dtype, int64_t N, int D, int K, int covariance, 
  * counts that straddle a block boundary.  hipErrorInvalidValue for a shape outside the limits or a NULL pointer. */
 int zk_gmm_launch_geometry(int dtype, int D, int K, int covariance, int tied, int* rows_per_block);
 
+/* ---- continuous normalizing flow (CNF; zuko/flows/continuous.py, zuko/transforms.py: FreeFormJacobianTransform, zuko/utils.py: dopri45; fp32) ----
+ * zk_cnf_step makes ONE attempted Dormand-Prince 5(4) step of size dt (either sign) from time t for all N rows in one launch.  The vector field is
+ *     f(t, x) = MLP(cat(cos(freqs t), sin(freqs t), x, c)),   MLP: (2 freqs + features + context) -> width0 [-> width1 [-> width2]] -> features, ELU(alpha = 1)
+ * with the first layer split as W0 = [W0t | W0x | W0c]: the caller passes pre = c W0c^T + b0, which does not change during an integration, and the
+ * kernel forms the time embedding and W0t emb for the seven stage times itself.  With n_tangents = features every stage also carries the exact trace
+ * of df/dx in forward mode (tangent seeds D1 o W0x, T_{l+1} = D_{l+1} o (W_l T_l), trace = sum_i W_last[i, :] T[:, i]); the log-determinant
+ * component of the state integrates trace * trace_scale.  The stage and result sums add their terms left to right, as the reference writes them.
+ *
+ *   x        [N, features], row stride ldx >= features
+ *   l        n_tangents = features: [N], the log-determinant component of the state
+ *   pre      [N, width0], row stride ld_pre >= width0, a multiple of 4, 16-byte aligned; ld_pre = 0: ONE row shared by all N (no context)
+ *   image    zk_cnf_image_floats(...) floats: the weights as the kernel reads them (zuko_amd/cnf_plan.py: layout)
+ *   y        [N, features], row stride ldy >= features: the fifth-order result;  l_next [N] likewise (n_tangents = features)
+ *   err      ONE float the caller has zeroed: the maximum over all rows of
+ *                ratio = max_j |next_j - star_j| / (atol + rtol max(|state_j|, |next_j|))      (j over the features, and l with tangents),
+ *            combined across blocks by an integer atomic maximum on the bits of |ratio|: NaN and inf propagate, block order does not matter
+ *   err_rows [N] the per-row ratio, or NULL
+ *   limits   1 <= features <= 16, 1 <= freqs <= 8, n_hidden 1..3, widths multiples of 16 up to 128, n_tangents 0 or features, atol, rtol >= 0.
+ * A row's outputs depend on its own x, l and pre row only.  Refusals (hipErrorInvalidValue) come before any launch; N = 0 returns 0 without
+ * examining the pointers. */
+typedef struct zk_cnf_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_cnf_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t features;
+  int32_t freqs;           /* time-embedding frequencies */
+  int32_t n_hidden;        /* hidden layers, 1..3 */
+  int32_t width0;          /* hidden widths; 0 behind n_hidden */
+  int32_t width1;
+  int32_t width2;
+  int32_t image_floats;    /* = zk_cnf_image_floats(features, freqs, n_hidden, width0, width1, width2) */
+  int32_t n_tangents;      /* features: value, trace and l; 0: the value alone */
+  int64_t N;
+  int64_t ldx;
+  int64_t ldy;
+  int64_t ld_pre;          /* 0: one shared row */
+  double t;
+  double dt;
+  double atol;
+  double rtol;
+  double trace_scale;
+  const void* x;
+  const void* l;           /* n_tangents = features */
+  const void* pre;
+  const void* image;
+  void* y;
+  void* l_next;            /* n_tangents = features */
+  void* err;
+  void* err_rows;          /* or NULL */
+} zk_cnf_args_v1;
+int zk_cnf_step(const zk_cnf_args_v1* args, void* stream);
+/* Floats of the weight image, or -1 outside the limits (host only). */
+int zk_cnf_image_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2);
+
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *
  * out[n] = sum_d Normal(loc[d], scale[d]).log_prob(z[n, d]) (+ ladj[n] if ladj != NULL). */
 int zk_diag_normal_log_prob(int dtype, int64_t N, int64_t D, const void* z, const void* loc, const void* scale,

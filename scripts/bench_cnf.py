@@ -1,0 +1,126 @@
+r"""CNF(features=5, context=3), hidden (64, 64): `log_prob` at batch 2^16 and sampling at batch 2^14 on one GPU, the fused Dormand-Prince step kernel
+(zk_cnf_step) against the torch-op path of the same integration (zuko_amd.ops.CNF_KERNEL = False: what a call that needs gradients runs — seven
+field evaluations per attempted step, each with a batched autograd Jacobian for the trace), alternating in one process.  Device events over
+>= 0.5 s of work per measurement after a warm-up.  The kernel path's attempt counts are in the output.
+
+    python scripts/bench_cnf.py                 # prints one JSON line
+    rocprofv3 --kernel-trace --stats -- python scripts/bench_cnf.py --trace     # per-launch kernel times (kernel path only, few calls)
+
+FLOP per row and attempted step from the shapes, seven stages each: the value 2 [(2 Q + F) H1 + sum_l H_l H_{l+1} + H_last F] (the context's share
+of the first layer is one GEMM per integration, not counted) and F tangents of 2 [sum_l H_l H_{l+1} + H_last] each (a tangent enters the first
+layer as a column, and meets one row of the last) = 362 880 for F = 5, Q = 3, hidden (64, 64).  The f32 matrix instruction's peak is 157.3
+TFLOP/s; a row moves 120 bytes plus its 256-byte `pre` row per step, so the bound is compute."""
+
+from __future__ import annotations
+
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+import zuko_amd
+from zuko_amd import _C, ops
+from zuko_amd.flows import CNF
+
+PEAK_F32_MATRIX = 157.3e12
+
+
+def flop_per_row_step(F: int, Q: int, hidden, tangents: bool = True) -> int:
+    h = list(hidden)
+    inner = sum(a * b for a, b in zip(h[:-1], h[1:]))
+    value = 2 * ((2 * Q + F) * h[0] + inner + h[-1] * F)
+    return 7 * (value + (F * 2 * (inner + h[-1]) if tangents else 0))
+
+
+def timed(fn, min_seconds: float = 0.5, warmup: int = 2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    total = 0.0
+    while total < min_seconds or len(times) < 3:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b) * 1e-3)
+        total += times[-1]
+    times.sort()
+    return {"median_ms": 1e3 * times[len(times) // 2], "min_ms": 1e3 * times[0], "max_ms": 1e3 * times[-1], "calls": len(times)}
+
+
+def main() -> None:
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    F, C, Q, hidden = 5, 3, 3, (64, 64)
+    flow = CNF(F, C).to(dev).eval().requires_grad_(False)
+    g = torch.Generator().manual_seed(1)
+    x, c = torch.randn(2**16, F, generator=g).to(dev), torch.randn(2**16, C, generator=g).to(dev)
+    n_sample = 2**14
+    cs = c[:n_sample]
+
+    def log_prob():
+        with torch.no_grad():
+            return flow(c).log_prob(x)
+
+    def sample():
+        with torch.no_grad():
+            return flow(cs).sample()
+
+    def with_kernel(on, fn):
+        def run():
+            ops.CNF_KERNEL = on
+            try:
+                return fn()
+            finally:
+                ops.CNF_KERNEL = True
+
+        return run
+
+    if "--trace" in sys.argv:
+        for _ in range(3):
+            log_prob()
+        sample()
+        torch.cuda.synchronize()
+        return
+    out = {"workload": f"CNF({F}, {C}), freqs {Q}, hidden {hidden}, weights as initialised (seed 0)", "log_prob_batch": x.shape[0], "sample_batch": n_sample}
+    lp_k = with_kernel(True, log_prob)()
+    out["log_prob_attempts_kernel"] = {k: ops.CNF_STATS[k] for k in ("attempts", "accepted")}
+    lp_t = with_kernel(False, log_prob)()
+    out["log_prob_max_abs_diff_kernel_vs_torch"] = float((lp_k - lp_t).abs().max())
+    # alternate the two paths (two rounds each): neither sees a systematically warmer or cooler device
+    res = {}
+    for rnd in range(2):
+        for name, on in (("kernel", True), ("torch", False)):
+            res.setdefault(("log_prob", name), []).append(timed(with_kernel(on, log_prob)))
+    for name, on in (("kernel", True), ("torch", False)):
+        res[("sample", name)] = [timed(with_kernel(on, sample), warmup=1)]
+    with_kernel(True, sample)()
+    out["sample_attempts_kernel"] = {k: ops.CNF_STATS[k] for k in ("attempts", "accepted")}
+    for (what, name), runs in res.items():
+        out[f"{what}_{name}"] = min(runs, key=lambda r: r["median_ms"]) | {"medians_ms": [round(r["median_ms"], 3) for r in runs]}
+    out["log_prob_speedup"] = out["log_prob_torch"]["median_ms"] / out["log_prob_kernel"]["median_ms"]
+    out["sample_speedup"] = out["sample_torch"]["median_ms"] / out["sample_kernel"]["median_ms"]
+    # per-launch time of the step kernel by events around the entry point (the kernel-trace run gives the same without the launch gap)
+    _C.PROFILE = {}
+    log_prob()
+    torch.cuda.synchronize()
+    launches = [a.elapsed_time(b) * 1e-3 for a, b, _ in _C.PROFILE.get("zk_cnf_step", [])]
+    _C.PROFILE = None
+    flop = flop_per_row_step(F, Q, hidden) * x.shape[0]
+    out["flop_per_row_step"] = flop_per_row_step(F, Q, hidden)
+    out["zk_cnf_step_launch_ms"] = [round(1e3 * t, 4) for t in launches]
+    if launches:
+        out["zk_cnf_step_tflops"] = flop / min(launches) / 1e12
+        out["zk_cnf_step_share_of_f32_matrix_peak"] = flop / min(launches) / PEAK_F32_MATRIX
+    out["bound"] = "compute (363 kFLOP against under 400 B per row and step)"
+    out["version"] = zuko_amd.__version__
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

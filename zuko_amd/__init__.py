@@ -33,6 +33,7 @@ def invalidate(module) -> None:
             m.__dict__.pop(k, None)
         for k in ("_mnn_image_cache", "_mnn_feat_cache"):  # weight image of the monotone networks of a NAF (mnn_plan.py)
             m.__dict__.pop(k, None)
+        m.__dict__.pop("_cnf_image_cache", None)  # weight image of the field of a CNF (cnf_plan.py)
         from . import train as _train
         from .flows import coupling as _cp
 

@@ -1,0 +1,393 @@
+// zuko_amd — continuous normalizing flow (CNF): one attempted Dormand-Prince 5(4) step of the free-form Jacobian ODE for all rows.
+//
+// Replaces one pass of the inner loop of AdaptiveCheckpointAdjoint.forward (zuko/utils.py:515-554): dopri45(f_aug, (x, ladj), t, dt, error=True)
+// with f_aug of FreeFormJacobianTransform.call_and_ladj (zuko/transforms.py:1147-1179) and f of FFJTransform (zuko/flows/continuous.py:88-97),
+// and the per-row share of max(error / tolerance).  The reference runs seven MLP evaluations, each with a batched autograd Jacobian (`features`
+// backward passes under vmap) for the trace: several hundred launches per attempt.  Here it is one.
+//
+// Execution model (gfx950):
+//   * a wavefront owns 16 rows for the whole step.  As in csrc/mnn.hip every layer is computed transposed, H^T = W X^T, on
+//     v_mfma_f32_16x16x4_f32 (exact fp32): the 16 columns of a tile are the wave's 16 rows, lane (j, q) = (lane & 15, lane >> 4) of a D fragment
+//     holds out units 16 t + 4 q + r (r = 0..3) of row j, which is the next layer's B operand with the weight image laid out in that k order.
+//   * the state lives in registers in the SAME distribution: lane (j, q) holds features 4 s + q (slots s = 0..3) of row j — the B operand of the
+//     first layer's x product as it stands — and the last layer's rows are permuted in the image so that its D fragment comes out in that
+//     distribution too.  The seven k vectors are 4 registers each per lane; the log-determinant's k and the row's l are kept in all four lanes.
+//   * the exact trace is carried in forward mode: the value pass keeps act'(pre) of every hidden layer (D_l); tangent i enters as D_1 o W0x[:, i],
+//     goes through the hidden layers on the same A fragments (two tangents at a time for networks up to 64 wide: four independent accumulator
+//     chains per fragment read), and meets row i of the last layer in a per-lane dot product and two cross-lane adds: only the diagonal of the
+//     last product is formed.  The trace adds the tangents' terms in the order i = 0, 1, ...
+//   * the stage loop is a run-time loop over one body (seven unrolled bodies would not fit the instruction cache): the Butcher rows come from a
+//     table, zero entries included — adding 0 * k changes nothing, so the sums are the reference's left to right.
+//   * the weight image (zuko_amd/cnf_plan.py: layout) sits in LDS, shared by the block's 4 wavefronts; a block covers 64 rows.
+//   * the error ratio is reduced per row over the four lanes, per wave over the rows, and one lane per wave joins an integer atomic maximum on
+//     the bits of |ratio| (NaN > inf > finite in that order): the one float the host reads back per attempt.
+//
+// A row's outputs depend on its own x, l and pre row only: not on N, the launch geometry or its neighbours.
+#include "zk_mnn_common.h"
+#include <math.h>
+
+namespace zk {
+
+#define CNF_ROWS 64  // rows per block: one 16-row tile per wavefront
+
+// Offsets (floats) of the image; the same arithmetic as zuko_amd/cnf_plan.py: layout.
+struct CnfLayout {
+  int nh, F, Q, kt, kx;  // hidden layers, features, frequencies, k-steps of the time product = ceil(2 Q / 4) and of the x product = ceil(F / 4)
+  int T[3];              // 16-unit tiles per hidden layer
+  int o_fr, o_w0t, o_w0x, o_w0c, o_w[3], o_b[3], o_wo, o_bo, o_wl, total;
+};
+
+static inline bool cnf_layout(int F, int Q, int nh, const int* widths, CnfLayout* L) {
+  if (F < 1 || F > 16 || Q < 1 || Q > 8 || nh < 1 || nh > 3) return false;
+  for (int l = 0; l < 3; ++l) {
+    const int h = widths[l];
+    if (l < nh ? (h < 16 || h > 128 || h % 16 != 0) : h != 0) return false;
+    L->T[l] = h / 16;
+  }
+  L->nh = nh; L->F = F; L->Q = Q; L->kt = (2 * Q + 3) / 4; L->kx = (F + 3) / 4;
+  int o = 0;
+  L->o_fr = o; o += 8;
+  L->o_w0t = o; o += L->T[0] * L->kt * 64;
+  L->o_w0x = o; o += L->T[0] * L->kx * 64;
+  L->o_w0c = o; o += F * L->T[0] * 16;
+  L->o_w[0] = L->o_b[0] = 0;
+  for (int l = 1; l < 3; ++l) {
+    L->o_w[l] = o; if (l < nh) o += L->T[l] * L->T[l - 1] * 256;
+    L->o_b[l] = o; if (l < nh) o += L->T[l] * 16;
+  }
+  L->o_wo = o; o += L->T[nh - 1] * 256;
+  L->o_bo = o; o += 16;
+  L->o_wl = o; o += F * L->T[nh - 1] * 16;
+  L->total = o;
+  return o * 4 <= MNN_LDS_MAX;
+}
+
+struct CnfArgs {
+  const float* x;
+  const float* l;
+  const float* pre;
+  const float* image;
+  float* y;
+  float* l_next;
+  unsigned* err;
+  float* err_rows;
+  long long N, ldx, ldy, ld_pre;
+  float t, dt, atol, rtol, tscale;
+  CnfLayout L;
+};
+
+// Dormand-Prince: stage s (0..6) is evaluated at t + CNF_C[s] dt on x + sum_m CNF_A[s][m] k_m; row 6 is the fifth-order result, whose field value is k_7
+// of the embedded fourth-order one.  The quotients are rounded from double once, as a Python float times a float32 tensor is.  CNF_E holds the
+// DIFFERENCE of the two results' weights: next - star = sum_m CNF_E[m] k_m is formed from the k directly.  The reference subtracts the two sums, which
+// in float32 leaves the rounding of a dozen additions at the state's magnitude in a quantity a hundred thousand times smaller (its ratio moves by
+// +-0.02 between two correct float32 evaluations); the direct sum is the same quantity without that cancellation.
+__constant__ float CNF_C[7] = {0.f, (float)(1.0 / 5), (float)(3.0 / 10), (float)(4.0 / 5), (float)(8.0 / 9), 1.f, 1.f};
+__constant__ float CNF_A[7][6] = {
+    {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {(float)(1.0 / 5), 0.f, 0.f, 0.f, 0.f, 0.f},
+    {(float)(3.0 / 40), (float)(9.0 / 40), 0.f, 0.f, 0.f, 0.f},
+    {(float)(44.0 / 45), -(float)(56.0 / 15), (float)(32.0 / 9), 0.f, 0.f, 0.f},
+    {(float)(19372.0 / 6561), -(float)(25360.0 / 2187), (float)(64448.0 / 6561), -(float)(212.0 / 729), 0.f, 0.f},
+    {(float)(9017.0 / 3168), -(float)(355.0 / 33), (float)(46732.0 / 5247), (float)(49.0 / 176), -(float)(5103.0 / 18656), 0.f},
+    {(float)(35.0 / 384), 0.f, (float)(500.0 / 1113), (float)(125.0 / 192), -(float)(2187.0 / 6784), (float)(11.0 / 84)},
+};
+__constant__ float CNF_E[7] = {(float)(35.0 / 384 - 5179.0 / 57600), 0.f, (float)(500.0 / 1113 - 7571.0 / 16695), (float)(125.0 / 192 - 393.0 / 640),
+                               (float)(92097.0 / 339200 - 2187.0 / 6784), (float)(11.0 / 84 - 187.0 / 2100), -(float)(1.0 / 40)};
+
+// ELU(alpha = 1) and its derivative
+__device__ __forceinline__ void cnf_act(float p, float& v, float& d) {
+  v = p > 0.f ? p : expm1f(p);
+  d = p > 0.f ? 1.f : expf(p);
+}
+__device__ __forceinline__ float cnf_act(float p) { return p > 0.f ? p : expm1f(p); }
+
+// max that keeps a NaN from either side (torch.max does; fmaxf drops it)
+__device__ __forceinline__ float cnf_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+// out_g = W in_g (+ b) for G column tiles at once: the A fragment of a (out tile, in tile) pair is read once and feeds 4 G products; out tiles go
+// in pairs, so 2 G accumulator chains are independent.  tin / tout tiles; the tiles of one out tile are consecutive in the image.
+template <int TM, int G, bool BIAS>
+__device__ __forceinline__ void cnf_matvec(const float* W, const float* B, int tin, int tout, int lane, int q, const mnn_f4 (&in)[G][TM], mnn_f4 (&out)[G][TM]) {
+  const int rowstride = tin * 256;
+  mnn_for<TM / 2>([&](auto P) MNN_INLINE {
+    constexpr int o0 = 2 * P, o1 = o0 + 1;
+    if (o0 < tout) {
+      const bool two = o1 < tout;
+      const float* const p0 = W + o0 * rowstride + lane * 4;
+      const float* const p1 = p0 + rowstride;
+      mnn_for<G>([&](auto g) MNN_INLINE {
+        out[g][o0] = mnn_f4{0.f, 0.f, 0.f, 0.f};
+        out[g][o1] = mnn_f4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (BIAS) {
+          out[g][o0] = *reinterpret_cast<const mnn_f4*>(B + o0 * 16 + q * 4);
+          if (two) out[g][o1] = *reinterpret_cast<const mnn_f4*>(B + o1 * 16 + q * 4);
+        }
+      });
+      mnn_for<TM>([&](auto it) MNN_INLINE {
+        if (it < tin) {
+          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(p0 + it * 256);
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            mnn_for<G>([&](auto g) MNN_INLINE { out[g][o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], in[g][it][(int)r], out[g][o0], 0, 0, 0); });
+          });
+          if (two) {
+            const mnn_f4 a1 = *reinterpret_cast<const mnn_f4*>(p1 + it * 256);
+            mnn_for<4>([&](auto r) MNN_INLINE {
+              mnn_for<G>([&](auto g) MNN_INLINE { out[g][o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], in[g][it][(int)r], out[g][o1], 0, 0, 0); });
+            });
+          }
+        }
+      });
+    }
+  });
+}
+
+// G tangents i0 .. i0 + G - 1 through the network behind the first layer's pre-activation: returns W_last[i, :] T[:, i] summed over them in order
+template <int TM, int G>
+__device__ __forceinline__ float cnf_tangents(const CnfLayout& L, const float* lds, int lane, int q, int i0, const mnn_f4 (&D)[3][TM]) {
+  mnn_f4 a[G][TM], b[G][TM];
+  const int H0 = L.T[0] * 16;
+  mnn_for<G>([&](auto g) MNN_INLINE {
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < L.T[0]) {
+        const mnn_f4 w = *reinterpret_cast<const mnn_f4*>(lds + L.o_w0c + (i0 + g) * H0 + o * 16 + q * 4);
+        mnn_for<4>([&](auto r) MNN_INLINE { a[g][o][(int)r] = D[0][o][(int)r] * w[(int)r]; });
+      }
+    });
+  });
+  if (L.nh > 1) {
+    cnf_matvec<TM, G, false>(lds + L.o_w[1], nullptr, L.T[0], L.T[1], lane, q, a, b);
+    mnn_for<G>([&](auto g) MNN_INLINE {
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        if (o < L.T[1]) mnn_for<4>([&](auto r) MNN_INLINE { a[g][o][(int)r] = D[1][o][(int)r] * b[g][o][(int)r]; });
+      });
+    });
+  }
+  if (L.nh > 2) {
+    cnf_matvec<TM, G, false>(lds + L.o_w[2], nullptr, L.T[1], L.T[2], lane, q, a, b);
+    mnn_for<G>([&](auto g) MNN_INLINE {
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        if (o < L.T[2]) mnn_for<4>([&](auto r) MNN_INLINE { a[g][o][(int)r] = D[2][o][(int)r] * b[g][o][(int)r]; });
+      });
+    });
+  }
+  const int tl = L.T[L.nh - 1];
+  float tr = 0.f;
+  mnn_for<G>([&](auto g) MNN_INLINE {
+    float p = 0.f;
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < tl) {
+        const mnn_f4 w = *reinterpret_cast<const mnn_f4*>(lds + L.o_wl + (i0 + g) * tl * 16 + o * 16 + q * 4);
+        mnn_for<4>([&](auto r) MNN_INLINE { p = fmaf(w[(int)r], a[g][o][(int)r], p); });
+      }
+    });
+    tr += mnn_sum_q(p);
+  });
+  return tr;
+}
+
+// f(ts, xin) of the wave's 16 rows: fo[r] = component 4 r + q of the field, tr = the trace of its Jacobian (TAN)
+template <int TM, bool TAN>
+__device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, const float* __restrict__ prow, int lane, int q, float ts, const float (&xin)[4], float (&fo)[4], float& tr) {
+  mnn_f4 v[1][TM], w[1][TM], D[3][TM];
+  float emb[4];
+  mnn_for<4>([&](auto s) MNN_INLINE {
+    const int e = 4 * s + q;
+    emb[s] = 0.f;
+    if (s < L.kt) {
+      const float arg = lds[L.o_fr + (e < L.Q ? e : (e < 2 * L.Q ? e - L.Q : 0))] * ts;
+      emb[s] = e < L.Q ? cosf(arg) : (e < 2 * L.Q ? sinf(arg) : 0.f);
+    }
+  });
+  // first layer: pre + W0t emb + W0x x
+  const float* const pt = lds + L.o_w0t + lane;
+  const float* const px = lds + L.o_w0x + lane;
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < L.T[0]) {
+      mnn_f4 c = *reinterpret_cast<const mnn_f4*>(prow + o * 16 + q * 4);
+      mnn_for<4>([&](auto s) MNN_INLINE {
+        if (s < L.kt) c = __builtin_amdgcn_mfma_f32_16x16x4f32(pt[(o * L.kt + s) * 64], emb[s], c, 0, 0, 0);
+      });
+      mnn_for<4>([&](auto s) MNN_INLINE {
+        if (s < L.kx) c = __builtin_amdgcn_mfma_f32_16x16x4f32(px[(o * L.kx + s) * 64], xin[s], c, 0, 0, 0);
+      });
+      mnn_for<4>([&](auto r) MNN_INLINE {
+        if constexpr (TAN) {
+          float av, ad;
+          cnf_act(c[(int)r], av, ad);
+          v[0][o][(int)r] = av;
+          D[0][o][(int)r] = ad;
+        } else {
+          v[0][o][(int)r] = cnf_act(c[(int)r]);
+        }
+      });
+    }
+  });
+  if (L.nh > 1) {
+    cnf_matvec<TM, 1, true>(lds + L.o_w[1], lds + L.o_b[1], L.T[0], L.T[1], lane, q, v, w);
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < L.T[1]) mnn_for<4>([&](auto r) MNN_INLINE {
+        if constexpr (TAN) {
+          float av, ad;
+          cnf_act(w[0][o][(int)r], av, ad);
+          v[0][o][(int)r] = av;
+          D[1][o][(int)r] = ad;
+        } else {
+          v[0][o][(int)r] = cnf_act(w[0][o][(int)r]);
+        }
+      });
+    });
+  }
+  if (L.nh > 2) {
+    cnf_matvec<TM, 1, true>(lds + L.o_w[2], lds + L.o_b[2], L.T[1], L.T[2], lane, q, v, w);
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < L.T[2]) mnn_for<4>([&](auto r) MNN_INLINE {
+        if constexpr (TAN) {
+          float av, ad;
+          cnf_act(w[0][o][(int)r], av, ad);
+          v[0][o][(int)r] = av;
+          D[2][o][(int)r] = ad;
+        } else {
+          v[0][o][(int)r] = cnf_act(w[0][o][(int)r]);
+        }
+      });
+    });
+  }
+  // last layer: its rows are stored so that register r of lane (j, q) is feature 4 r + q
+  const int tl = L.T[L.nh - 1];
+  mnn_f4 c = *reinterpret_cast<const mnn_f4*>(lds + L.o_bo + q * 4);
+  mnn_for<TM>([&](auto it) MNN_INLINE {
+    if (it < tl) {
+      const mnn_f4 a = *reinterpret_cast<const mnn_f4*>(lds + L.o_wo + it * 256 + lane * 4);
+      mnn_for<4>([&](auto r) MNN_INLINE { c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[(int)r], v[0][it][(int)r], c, 0, 0, 0); });
+    }
+  });
+  mnn_for<4>([&](auto r) MNN_INLINE { fo[r] = c[(int)r]; });
+  if constexpr (TAN) {
+    tr = 0.f;
+    int i = 0;
+    if constexpr (TM <= 4) {
+      for (; i + 2 <= L.F; i += 2) tr += cnf_tangents<TM, 2>(L, lds, lane, q, i, D);
+    }
+    for (; i < L.F; ++i) tr += cnf_tangents<TM, 1>(L, lds, lane, q, i, D);
+  }
+}
+
+extern __shared__ __attribute__((aligned(16))) float cnf_lds[];
+
+template <int TM, bool TAN> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 2 : 1) void cnf_step_kernel(CnfArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
+  const CnfLayout& L = a.L;
+  for (int i = tid * 4; i < L.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(cnf_lds + i) = *reinterpret_cast<const mnn_f4*>(a.image + i);
+  __syncthreads();
+  const long long row0 = (long long)blockIdx.x * CNF_ROWS + wave * 16;
+  if (row0 >= a.N) return;  // (the whole wavefront; no barrier follows)
+  const long long row = row0 + j;
+  const long long rc = row < a.N ? row : a.N - 1;  // rows behind the end compute on the last row and store nothing
+  const float* const prow = a.pre + rc * a.ld_pre;
+  float x[4], xs[4], xn[4], k[7][4], kl[7];
+  mnn_for<4>([&](auto s) MNN_INLINE { x[s] = 4 * s + q < L.F ? a.x[rc * a.ldx + 4 * s + q] : 0.f; });
+  float l0 = 0.f, ln = 0.f;
+  if constexpr (TAN) l0 = a.l[rc];
+  mnn_for<7>([&](auto m) MNN_INLINE {
+    kl[m] = 0.f;
+    mnn_for<4>([&](auto s) MNN_INLINE { k[m][s] = 0.f; });
+  });
+#pragma unroll 1
+  for (int s = 0; s < 7; ++s) {
+    // x + A[s][0] k1 + A[s][1] k2 + ..., left to right (a zero entry adds nothing)
+    mnn_for<4>([&](auto c) MNN_INLINE {
+      float acc = x[c];
+      mnn_for<6>([&](auto m) MNN_INLINE { acc = acc + CNF_A[s][m] * k[m][c]; });
+      xs[c] = acc;
+    });
+    if (s == 6) {
+      mnn_for<4>([&](auto c) MNN_INLINE { xn[c] = xs[c]; });
+      if constexpr (TAN) {
+        float acc = l0;
+        mnn_for<6>([&](auto m) MNN_INLINE { acc = acc + CNF_A[6][m] * kl[m]; });
+        ln = acc;
+      }
+    }
+    const float ts = a.t + CNF_C[s] * a.dt;
+    float fo[4], tr = 0.f;
+    cnf_field<TM, TAN>(L, cnf_lds, prow, lane, q, ts, xs, fo, tr);
+    mnn_for<7>([&](auto m) MNN_INLINE {
+      if (s == m) {
+        mnn_for<4>([&](auto c) MNN_INLINE { k[m][c] = a.dt * fo[c]; });
+        if constexpr (TAN) kl[m] = a.dt * (tr * a.tscale);
+      }
+    });
+  }
+  // next - star of the embedded pair and the ratio |next - star| / (atol + rtol max(|state|, |next|))
+  float ratio = 0.f;
+  mnn_for<4>([&](auto c) MNN_INLINE {
+    float diff = CNF_E[0] * k[0][c];
+    mnn_for<7>([&](auto m) MNN_INLINE {
+      if (m > 1) diff = diff + CNF_E[m] * k[m][c];
+    });
+    const float tol = a.atol + a.rtol * cnf_max(fabsf(x[c]), fabsf(xn[c]));
+    const float rt = fabsf(diff) / tol;
+    if (4 * c + q < L.F) ratio = cnf_max(ratio, rt);
+  });
+  if constexpr (TAN) {
+    float diff = CNF_E[0] * kl[0];
+    mnn_for<7>([&](auto m) MNN_INLINE {
+      if (m > 1) diff = diff + CNF_E[m] * kl[m];
+    });
+    const float tol = a.atol + a.rtol * cnf_max(fabsf(l0), fabsf(ln));
+    ratio = cnf_max(ratio, fabsf(diff) / tol);
+  }
+  ratio = cnf_max(ratio, __shfl_xor(ratio, 16, 64));
+  ratio = cnf_max(ratio, __shfl_xor(ratio, 32, 64));
+  if (row < a.N) {
+    mnn_for<4>([&](auto c) MNN_INLINE {
+      if (4 * c + q < L.F) a.y[row * a.ldy + 4 * c + q] = xn[c];
+    });
+    if (q == 0) {
+      if constexpr (TAN) a.l_next[row] = ln;
+      if (a.err_rows) a.err_rows[row] = ratio;
+    }
+  }
+  unsigned bits = row < a.N ? (__float_as_uint(ratio) & 0x7fffffffu) : 0u;
+  for (int off = 1; off < 16; off <<= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)bits, off, 64);
+    bits = o > bits ? o : bits;
+  }
+  if (lane == 0) atomicMax(a.err, bits);
+}
+
+static int cnf_step(const zk_cnf_args_v1* p, void* stream) {
+  if (!p || p->struct_size != sizeof(zk_cnf_args_v1) || p->version != 1) return ZK_EINVAL;
+  CnfArgs a;
+  const int widths[3] = {p->width0, p->width1, p->width2};
+  if (!cnf_layout(p->features, p->freqs, p->n_hidden, widths, &a.L)) return ZK_EINVAL;
+  if (p->image_floats != a.L.total || (p->n_tangents != 0 && p->n_tangents != p->features) || p->N < 0) return ZK_EINVAL;
+  if (p->ldx < p->features || p->ldy < p->features) return ZK_EINVAL;
+  if (p->ld_pre != 0 && (p->ld_pre < p->width0 || p->ld_pre % 4 != 0)) return ZK_EINVAL;
+  if (!std::isfinite(p->t) || !std::isfinite(p->dt) || !(p->atol >= 0) || !(p->rtol >= 0) || !std::isfinite(p->atol) || !std::isfinite(p->rtol)) return ZK_EINVAL;
+  if (p->n_tangents != 0 && !(p->trace_scale > 0 && std::isfinite(p->trace_scale))) return ZK_EINVAL;
+  if (p->N == 0) return 0;
+  if (!p->x || !p->pre || !p->image || !p->y || !p->err) return ZK_EINVAL;
+  if (p->n_tangents != 0 && (!p->l || !p->l_next)) return ZK_EINVAL;
+  if (((uintptr_t)p->pre | (uintptr_t)p->image) % 16 != 0) return ZK_EINVAL;
+  const long long gx = (p->N + CNF_ROWS - 1) / CNF_ROWS;
+  if (gx > 0x7fffffffLL) return ZK_EINVAL;
+  a.x = (const float*)p->x; a.l = (const float*)p->l; a.pre = (const float*)p->pre; a.image = (const float*)p->image;
+  a.y = (float*)p->y; a.l_next = (float*)p->l_next; a.err = (unsigned*)p->err; a.err_rows = (float*)p->err_rows;
+  a.N = p->N; a.ldx = p->ldx; a.ldy = p->ldy; a.ld_pre = p->ld_pre;
+  a.t = (float)p->t; a.dt = (float)p->dt; a.atol = (float)p->atol; a.rtol = (float)p->rtol; a.tscale = (float)p->trace_scale;
+  const bool small = a.L.T[0] <= 4 && a.L.T[1] <= 4 && a.L.T[2] <= 4;
+  const bool tan = p->n_tangents != 0;
+  const void* fn = small ? (tan ? (const void*)cnf_step_kernel<4, true> : (const void*)cnf_step_kernel<4, false>)
+                         : (tan ? (const void*)cnf_step_kernel<8, true> : (const void*)cnf_step_kernel<8, false>);
+  return mnn_launch_dyn_lds(fn, dim3((unsigned)gx), a.L.total * 4, &a, (hipStream_t)stream);
+}
+
+}  // namespace zk
+
+extern "C" int zk_cnf_step(const zk_cnf_args_v1* args, void* stream) { return zk::cnf_step(args, stream); }
+extern "C" int zk_cnf_image_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2) {
+  zk::CnfLayout L;
+  const int widths[3] = {width0, width1, width2};
+  return zk::cnf_layout(features, freqs, n_hidden, widths, &L) ? L.total : -1;
+}

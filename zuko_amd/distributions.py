@@ -118,6 +118,8 @@ class NormalizingFlow(Distribution):
         else:
             z, ladj = self.transform.call_and_ladj(x)
         ladj = _sum_rightmost(ladj, self.reinterpreted)
+        if fused is not None and z.dtype != torch.float32 and torch.is_grad_enabled() and (z.requires_grad or (torch.is_tensor(ladj) and ladj.requires_grad)):
+            fused = None  # the base's adjoint kernel is float32: a float64 call that needs gradients (a continuous flow trained in float64) takes torch's Normal
         if fused is not None and z.is_cuda and torch.is_tensor(ladj) and ladj.shape == z.shape[:-1]:
             return ops.diag_normal_log_prob(z, fused[0], fused[1], ladj)
         return self.base.log_prob(z) + ladj

@@ -1,8 +1,9 @@
 r"""Flow factories of the hot path: MAF / NSF (autoregressive), NICE / RealNVP (coupling),
-SOSPF / BPF (polynomial), NAF / UNAF (monotone networks); GMM is an alias of zuko_amd.mixtures.GMM, as in the reference.  Same constructor signatures and module trees as zuko.flows."""
+SOSPF / BPF (polynomial), NAF / UNAF (monotone networks), CNF (continuous); GMM is an alias of zuko_amd.mixtures.GMM, as in the reference.  Same constructor signatures and module trees as zuko.flows."""
 
 from ..mixtures import GMM
 from .autoregressive import MAF, MaskedAutoregressiveTransform
+from .continuous import CNF, FFJTransform
 from .coupling import NICE, GeneralCouplingTransform, RealNVP
 from .elementwise import ElementWiseTransform
 from .neural import MNN, NAF, UMNN, UNAF
@@ -11,6 +12,7 @@ from .spline import NCSF, NSF
 
 __all__ = [
     "BPF",
+    "CNF",
     "GMM",
     "MAF",
     "MNN",
@@ -22,6 +24,7 @@ __all__ = [
     "UMNN",
     "UNAF",
     "ElementWiseTransform",
+    "FFJTransform",
     "GeneralCouplingTransform",
     "MaskedAutoregressiveTransform",
     "RealNVP",

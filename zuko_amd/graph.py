@@ -19,6 +19,16 @@ from torch import Tensor
 __all__ = ["capture", "capture_step"]
 
 
+def _refuse_continuous(flow, what: str) -> None:
+    """A continuous flow integrates with adaptive steps: after every attempt the host reads the error estimate back and decides the next step, so
+    the sequence of launches depends on the data and cannot be recorded once and replayed."""
+    from .flows.continuous import FFJTransform
+
+    if any(isinstance(m, FFJTransform) for m in flow.modules()):
+        raise NotImplementedError(f"zuko_amd.{what}: a continuous flow (CNF / FFJTransform) cannot be captured: its adaptive step loop reads the error "
+                                  "estimate back after every attempted step, and the number of steps depends on the data")
+
+
 class CapturedCall:
     """`captured(x[, c])` -> the output of the captured call for these inputs (a view of the graph's static output buffer: valid until the next
     call; `.clone()` it to keep it).  Shapes, dtypes and devices are fixed at capture time, and so are the WEIGHTS: the fused kernels read weight
@@ -45,6 +55,7 @@ def capture(flow, x: Tensor, c: Tensor | None = None, call: str = "log_prob", wa
     build plans, weight streams and any static-shape kernel before the capture, on a side stream as torch.cuda.graph requires."""
     if not x.is_cuda:
         raise ValueError("zuko_amd.capture: inputs must live on the GPU")
+    _refuse_continuous(flow, "capture")
     xs = x.detach().clone()
     cs = None if c is None else c.detach().clone()
 
@@ -92,6 +103,7 @@ def capture_step(flow, optimizer, x: Tensor, c: Tensor | None = None, loss_fn=No
     the optimizer state allocated) ARE optimisation steps: the parameters move during them."""
     if not x.is_cuda:
         raise ValueError("zuko_amd.capture_step: inputs must live on the GPU")
+    _refuse_continuous(flow, "capture_step")
     for group in optimizer.param_groups:
         if group.get("capturable") is False:
             raise ValueError("zuko_amd.capture_step: the optimizer must be built with capturable=True (its step counter has to live on the device)")

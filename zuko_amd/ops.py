@@ -5,7 +5,9 @@ All functions require tensors on a HIP device (`tensor.is_cuda`) in float32 or f
 otherwise — there is no CPU or eager-PyTorch fallback.  One documented exception: the monotone networks of a neural autoregressive
 flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shapes their kernel does not serve, for float64 and for
 calls that need gradients (no adjoint kernel yet).  Likewise the Gaussian mixture density (gmm_log_prob) runs the reference's expressions as torch ops
-ON THE DEVICE outside its kernels' envelope (features or components above 64, sample dimensions broadcast over a batch of mixtures).
+ON THE DEVICE outside its kernels' envelope (features or components above 64, sample dimensions broadcast over a batch of mixtures).  And the
+continuous flow (cnf_integrate) hands every call its step kernel does not serve — gradients, float64, Hutchinson's estimator, other activations or
+shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.
 """
 
 from __future__ import annotations
@@ -1016,3 +1018,129 @@ def gmm_log_prob(x: Tensor, phi: Tensor, components: int, covariance_type: str =
     if AG.needs_grad(x, phi):
         return AG.GmmLogProbFn.apply(x, phi, components, covariance_type, tied, epsilon)
     return gmm_forward_kernel(x, phi, components, covariance_type, tied, epsilon)
+
+
+# ------------------------------------------------------------------------------------------------
+# continuous normalizing flow: zk_cnf_step driven by the adaptive controller; torch ops (zuko_amd.utils.odeint) when the kernel does not serve the call
+# ------------------------------------------------------------------------------------------------
+
+CNF_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_cnf.py measures the kernel against it)
+CNF_STATS: dict = {}  # the last integration: path ("kernel" | "torch"); on the kernel path also attempts, accepted and t_end (the time reached)
+
+
+def cnf_supported(features: int, context: int = 0, hidden_features=(64, 64), freqs: int = 3, activation=None) -> bool:
+    """True when zk_cnf_step serves the field MLP(2 freqs + features + context, features, hidden_features, activation): 1 <= features <= 16, one to
+    three hidden layers whose widths are multiples of 16 up to 128, 1 <= freqs <= 8, ELU(alpha = 1) (None: the default of FFJTransform, which is
+    ELU); any context width — the context enters the kernel through the first layer's product, computed once per integration."""
+    from . import cnf_plan
+
+    act = torch.nn.ELU if activation is None else activation
+    if not isinstance(act, torch.nn.Module):
+        try:
+            act = act()
+        except Exception:
+            return False
+    if type(act) is not torch.nn.ELU or act.alpha != 1.0 or int(context) < 0:
+        return False
+    return cnf_plan.layout(int(features), int(freqs), tuple(hidden_features)) is not None
+
+
+def _cnf_kernel_serves(module, c, x: Tensor):
+    """The field's weight image when the step kernel serves this call (fp32 on the device, a supported field, nothing asks for gradients), else None."""
+    from . import cnf_plan
+
+    if not CNF_KERNEL or not x.is_cuda:
+        return None
+    ts = [x, *module.ode.parameters(), module.freqs] + ([] if c is None else [c])
+    if any(t.dtype != torch.float32 for t in ts):
+        return None
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        return None
+    sh = cnf_plan.shape_of(module)
+    if sh is None or x.dim() < 1 or x.shape[-1] != sh[0] or (sh[1] > 0) != (c is not None) or (c is not None and c.shape[-1] != sh[1]) or x.numel() == 0:
+        return None
+    return cnf_plan.image_of(module, x.device)
+
+
+def cnf_step(img, x: Tensor, l, pre: Tensor, t: float, dt: float, atol: float, rtol: float, trace_scale: float, y: Tensor, l_next, err: Tensor, err_rows=None) -> None:
+    """One attempted Dormand-Prince step on zk_cnf_step: x [N, F] (unit column stride), l [N] | None (None: the value alone, no trace), pre
+    [N, H1] or [H1] (one row for every x row) -> y, l_next, and the largest error ratio in `err` (one float, zeroed by the caller)."""
+    lay = img.layout
+    w = list(lay.widths) + [0, 0]
+    N, F = x.shape
+    a = _C.args("zk_cnf_args_v1", features=F, freqs=lay.Q, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], image_floats=lay.total,
+                n_tangents=0 if l is None else F, N=N, ldx=x.stride(0) if N > 1 else F, ldy=y.stride(0) if N > 1 else F,
+                ld_pre=0 if pre.dim() == 1 else (pre.stride(0) if N > 1 else lay.widths[0]), t=t, dt=dt, atol=atol, rtol=rtol, trace_scale=trace_scale,
+                x=x.data_ptr(), l=None if l is None else l.data_ptr(), pre=pre.data_ptr(), image=img.data.data_ptr(), y=y.data_ptr(),
+                l_next=None if l_next is None else l_next.data_ptr(), err=err.data_ptr(), err_rows=None if err_rows is None else err_rows.data_ptr())
+    _C.check(_C.lib().zk_cnf_step(a, _stream()), "zk_cnf_step")
+
+
+def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool):
+    """(x(t1), l(t1) | None) of the free-form Jacobian ODE of `module` (a zuko_amd.flows.FFJTransform) from x(t0) = x, l(t0) = 0, on the step kernel —
+    or None when the kernel does not serve the call (the caller then integrates in torch ops).  l is the log-determinant times `trace_scale`.
+
+    The loop is the reference's (zuko/utils.py:532-552) with t and dt carried in float32: per attempt `err` is zeroed, zk_cnf_step writes the step
+    into the spare buffers, the largest ratio is read back (the one synchronisation per attempt the reference has too), dt is multiplied by
+    min(10, max(0.1, 0.9 / ratio^(1/5))), and the buffers swap when ratio < 1.  The last step is clamped to the rest of the interval and ends at t1
+    exactly.  A non-finite ratio raises RuntimeError (utils.odeint does likewise)."""
+    from .utils import step_factor
+
+    img = _cnf_kernel_serves(module, c, x)
+    if img is None:
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("zuko_amd: a continuous flow cannot be captured into a HIP graph: its step loop reads the error estimate back after every "
+                           "attempt and the number of attempts depends on the data")
+    F = x.shape[-1]
+    lin0 = module.ode[0]
+    Q2 = 2 * img.Q
+    if c is None:
+        shape, pre = x.shape, lin0.bias.detach()
+    else:
+        shape = torch.broadcast_shapes(x.shape[:-1], c.shape[:-1]) + (F,)
+        c2 = c.reshape(-1, c.shape[-1])
+        pre = torch.addmm(lin0.bias.detach(), c2, lin0.weight.detach()[:, Q2 + F :].t())  # once per integration: it does not depend on t or x
+        if c2.shape[0] == 1:
+            pre = pre[0]
+        elif c.shape[:-1] != shape[:-1]:
+            pre = pre.reshape(c.shape[:-1] + (-1,)).expand(shape[:-1] + (-1,)).reshape(-1, pre.shape[-1])
+    pre = pre.contiguous()
+    if pre.data_ptr() % 16:
+        pre = pre.clone()  # (a parameter that is a view into a larger buffer: the kernel reads 16-byte pieces)
+    cur = x.expand(shape).reshape(-1, F).contiguous().clone()
+    N = cur.shape[0]
+    spare = torch.empty_like(cur)
+    l_cur = torch.zeros(N, dtype=torch.float32, device=x.device) if with_ladj else None
+    l_spare = torch.empty_like(l_cur) if with_ladj else None
+    err = torch.zeros(1, dtype=torch.float32, device=x.device)
+    data = img.refresh(module)
+    f32 = np.float32
+    floor = float(f32(1e-9))
+    t, end = f32(t0), f32(t1)
+    dt = f32(end - t)
+    sign = f32(np.sign(dt))
+    attempts = accepted = 0
+    while sign * (end - t) > 0:
+        rest = f32(end - t)
+        dt = f32(sign * min(abs(dt), abs(rest)))
+        while True:
+            err.zero_()
+            cnf_step(img, cur, l_cur, pre, float(t), float(dt), atol, rtol, trace_scale, spare, l_spare, err)
+            ratio = float(err.item())
+            attempts += 1
+            if not math.isfinite(ratio):
+                raise RuntimeError(f"zuko_amd: continuous flow: non-finite error estimate ({ratio}) at t = {float(t):g}, dt = {float(dt):g}")
+            ratio = max(ratio, floor)
+            ok = ratio < 1.0
+            if ok:
+                cur, spare, l_cur, l_spare = spare, cur, l_spare, l_cur
+                t = end if dt == rest else f32(t + dt)
+                accepted += 1
+            dt = f32(dt * f32(step_factor(ratio)))
+            if ok:
+                break
+    del data
+    CNF_STATS.clear()
+    CNF_STATS.update(path="kernel", attempts=attempts, accepted=accepted, t_end=float(t))
+    return cur.reshape(shape), (l_cur.reshape(shape[:-1]) if with_ladj else None)

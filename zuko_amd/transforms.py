@@ -34,6 +34,7 @@ __all__ = [
     "ComposedTransform",
     "CouplingTransform",
     "DependentTransform",
+    "FreeFormJacobianTransform",
     "MonotonicAffineTransform",
     "MonotonicNetworkTransform",
     "MonotonicRQSTransform",
@@ -531,3 +532,93 @@ class CouplingTransform(Transform):
         a, b = self.split(x)
         yb, ladj = self.meta(a).call_and_ladj(b)
         return self.merge(a, yb, x.shape), ladj
+
+
+class FreeFormJacobianTransform(Transform):
+    r"""y = x(t1) for dx/dt = f(t, x), x(t0) = x, and log|det dy/dx| = the integral of the trace of df/dx along the path (FFJORD, Grathwohl et al.,
+    2018).  Mirrors zuko/transforms.py:1076-1179: arguments, `inv` (t0 and t1 swapped), `trace_scale` = 1e-2 on the log-determinant component of
+    the ODE state, `exact` = the exact trace or Hutchinson's estimator.
+
+    `kernel` = (module, c), given by `zuko_amd.flows.FFJTransform`: the field's module and the context.  A call without gradients in float32 on
+    the device, `exact=True`, on a field csrc/cnf.hip serves (ops.cnf_supported) is integrated by ops.cnf_integrate — one launch per attempted
+    step.  Every other call integrates `f` in torch ops (zuko_amd.utils.odeint), with the reference's adjoint for the gradients."""
+
+    domain = constraints.real_vector
+    codomain = constraints.real_vector
+    bijective = True
+
+    def __init__(self, f: Callable[[Tensor, Tensor], Tensor], t0=0.0, t1=1.0, phi=(), atol: float = 1e-6, rtol: float = 1e-5, exact: bool = True,
+                 kernel=None, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.f = f
+        self.t0 = t0
+        self.t1 = t1
+        self.phi = tuple(p for p in phi if p.requires_grad)
+        self.atol = atol
+        self.rtol = rtol
+        self.exact = exact
+        self.kernel = kernel
+        self.trace_scale = 1e-2  # (the log-determinant enters the error estimate at a hundredth of its size)
+
+    def _integrate(self, x: Tensor, t0, t1, with_ladj: bool):
+        """The kernel path's result, or None when the call belongs to the torch-op path."""
+        ops._require_device(x)
+        if self.kernel is None or (with_ladj and not self.exact):
+            return None
+        module, c = self.kernel
+        return ops.cnf_integrate(module, c, x, float(t0), float(t1), self.atol, self.rtol, self.trace_scale, with_ladj)
+
+    def _call(self, x: Tensor) -> Tensor:
+        out = self._integrate(x, self.t0, self.t1, False)
+        if out is not None:
+            return out[0]
+        from .utils import odeint
+
+        ops.CNF_STATS.clear()
+        ops.CNF_STATS.update(path="torch")
+        return odeint(self.f, x, self.t0, self.t1, self.phi, self.atol, self.rtol)
+
+    @property
+    def inv(self) -> Transform:
+        return FreeFormJacobianTransform(self.f, self.t1, self.t0, self.phi, self.atol, self.rtol, self.exact, kernel=self.kernel)
+
+    def _inverse(self, y: Tensor) -> Tensor:
+        return self.inv._call(y)
+
+    def log_abs_det_jacobian(self, x: Tensor, y: Tensor) -> Tensor:
+        return self.call_and_ladj(x)[1]
+
+    def augmented(self, x: Tensor, eps: Tensor | None = None):
+        """The system call_and_ladj integrates in torch ops for inputs like `x`: (t, x, ladj) -> (f(t, x), trace(df/dx) * trace_scale), the trace
+        exact (one batched vector-Jacobian product per feature) or Hutchinson's eps^T (df/dx) eps."""
+        graph = torch.is_grad_enabled() and (x.requires_grad or bool(self.phi))
+        if self.exact:
+            seeds = torch.eye(x.shape[-1], dtype=x.dtype, device=x.device).expand(*x.shape, -1).movedim(-1, 0)
+        elif eps is None:
+            eps = torch.randn_like(x)
+
+        def system(t: Tensor, x: Tensor, ladj: Tensor):
+            with torch.enable_grad():
+                x = x.clone().requires_grad_()
+                dx = self.f(t, x)
+            if self.exact:
+                jac = torch.autograd.grad(dx, x, seeds, create_graph=graph, is_grads_batched=True)[0]
+                trace = torch.einsum("i...i", jac)
+            else:
+                trace = (torch.autograd.grad(dx, x, eps, create_graph=graph)[0] * eps).sum(dim=-1)
+            return dx, trace * self.trace_scale
+
+        return system
+
+    def call_and_ladj(self, x: Tensor, eps: Tensor | None = None):
+        """(y, log|det dy/dx|).  `eps` fixes the probe of Hutchinson's estimator (exact=False; default: a standard-normal draw)."""
+        out = self._integrate(x, self.t0, self.t1, True)
+        if out is not None:
+            return out[0], out[1] * (1 / self.trace_scale)
+        from .utils import odeint
+
+        ops.CNF_STATS.clear()
+        ops.CNF_STATS.update(path="torch")
+        augmented = self.augmented(x, eps)
+        y, ladj = odeint(augmented, (x, torch.zeros_like(x[..., 0])), self.t0, self.t1, self.phi, self.atol, self.rtol)
+        return y, ladj * (1 / self.trace_scale)
