@@ -107,6 +107,19 @@ int zk_bernstein_forward(int dtype, int64_t N, int64_t D, int M, int bounded, do
 int zk_bernstein_inverse(int dtype, int64_t N, int64_t D, int M, int bounded, double bound, double eps, int n_bisect, const void* y,
                          const void* theta, int64_t t_sN, int64_t t_sD, void* x, void* stream);
 
+/* ---- GaussianizationTransform (zuko/transforms.py:834-875, :570-637) ----------------------------- *
+ * y = sqrt(2) erfinv(c mean_k erf(u_k / sqrt(2))), u_k = x exp(scale_k) + shift_k, c = 1 - 1e-6; shift / scale [N, D, K] with
+ * element strides (sN, sD), 0 = broadcast, as above; 1 <= K <= 64, fp32 / fp64; any other K or dtype returns
+ * hipErrorInvalidValue before anything is launched.  Evaluated in a cancellation-free form (the smaller tail of the mixture
+ * from erfc, the complementary inverse, ladj as a max-subtracted log-sum-exp): nearer float64 than the float32 expression
+ * tree in the tails; ladj is finite or -inf, never NaN or +inf, for finite inputs.  A packed [shift(K) | scale(K)] buffer is
+ * staged through LDS while 64 * 2K elements fit 16 KiB per wave (K <= 32 in fp32, 16 in fp64); otherwise the parameters are
+ * read from global memory.  The inverse is the reference's bisection on [-bound, bound] with n_bisect steps. */
+int zk_gauss_forward(int dtype, int64_t N, int64_t D, int K, const void* x, const void* shift, int64_t b_sN, int64_t b_sD,
+                     const void* scale, int64_t a_sN, int64_t a_sD, void* y, void* ladj, int ladj_reduced, void* stream);
+int zk_gauss_inverse(int dtype, int64_t N, int64_t D, int K, double bound, int n_bisect, const void* y, const void* shift,
+                     int64_t b_sN, int64_t b_sD, const void* scale, int64_t a_sN, int64_t a_sD, void* x, void* stream);
+
 /* ---- conditioner layer: F.linear(x, mask * weight, bias) + activation (zuko/nn.py:217-218, 13-15) - *
  * x [N, in] with row stride ldx, weight [out, in] contiguous, mask (uint8/bool [out, in]) and bias
  * optional, y [N, out] with row stride ldy.  fp32 runs on v_mfma_f32_32x32x2_f32. */
@@ -473,6 +486,11 @@ int zk_sos_backward(int64_t N, int64_t D, int P, int L1, double slope, const dou
                     void* gparams, void* stream);
 int zk_bernstein_backward(int64_t N, int64_t D, int M, int bounded, double bound, double eps, const void* x, const void* theta, const void* gy,
                           const void* gl, int gl_reduced, void* gx, void* gtheta, void* stream);
+/* Adjoint of zk_gauss_forward (fp32): phi [N, D, 2K] = [shift(K) | scale(K)] packed, 1 <= K <= 32 (the wave's LDS image holds
+ * 64 elements x 2K floats; another K returns hipErrorInvalidValue); phi / gphi with the same 16-byte alignment; gy [N, D] /
+ * gl ([N] if gl_reduced else [N, D]) may be NULL; outputs gx [N, D], gphi [N, D, 2K].  No atomics. */
+int zk_gauss_backward(int64_t N, int64_t D, int K, const void* x, const void* phi, const void* gy, const void* gl, int gl_reduced,
+                      void* gx, void* gphi, void* stream);
 /* Adjoint seeds of an INVERSE univariate map x = f^{-1}(y) (gradients through rsample; inverse function theorem):
  * gy[e] = gx[e] * exp(-ladj[e]) with ladj = log f'(x), seed[e] = -gy[e] (zk_univariate_backward(x, phi, gy = seed) then
  * yields dL/dphi). */

@@ -113,6 +113,9 @@ SIGNATURES = {
     "zk_sos_inverse": [I, L, L, I, I, F, POINTER(c_double), POINTER(c_double), I, P, P, L, L, P, L, L, P, P],
     "zk_bernstein_forward": [I, L, L, I, I, F, F, P, P, L, L, P, P, I, P],
     "zk_bernstein_inverse": [I, L, L, I, I, F, F, I, P, P, L, L, P, P],
+    "zk_gauss_forward": [I, L, L, I, P, P, L, L, P, L, L, P, P, I, P],
+    "zk_gauss_inverse": [I, L, L, I, F, I, P, P, L, L, P, L, L, P, P],
+    "zk_gauss_backward": [L, L, I, P, P, P, P, I, P, P, P],
     "zk_linear": [I, L, I, I, P, L, P, P, P, I, P, L, P],
     "zk_linear_bf16": [L, I, I, P, L, P, P, P, I, P, L, P],
     "zk_linear_bf16_rqs": [L, I, I, P, L, P, P, P, I, I, F, F, P, L, P, L, P, P, P],

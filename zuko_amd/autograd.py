@@ -66,7 +66,8 @@ def _packed(parts: list[Tensor], batch) -> Tensor:
 
 # ---- univariate maps: one description object, three autograd Functions ------------------------------------------------
 # meta = (kind, bound, slope, sizes, extra): kind 0 affine [shift | scale], 1 RQS [w(K) | h(K) | d(K-1)], 2 SOS
-# [a(P*L1) | constant?] with extra = (P, L1, has_const), 3 Bernstein [theta(M)] with extra = (bounded,).
+# [a(P*L1) | constant?] with extra = (P, L1, has_const), 3 Bernstein [theta(M)] with extra = (bounded,), 4 Gaussianization [shift(K) | scale(K)]
+# with extra = (eps,) on the inverse.
 
 
 def _split(meta, phi):
@@ -93,6 +94,8 @@ def _fwd_any(meta, xe, phi, reduce):
             return ops.rqs_forward(xe, pc[0], pc[1], pc[2], bound, slope, reduce)
         if kind == 2:
             return ops.sos_forward(xe, pc[0], pc[1] if extra[2] else None, slope, reduce)
+        if kind == 4:
+            return ops.gauss_forward(xe, pc[0], pc[1], reduce)
         return ops.bernstein_forward(xe, pc[0], extra[0], bound, reduce, eps=extra[1] if len(extra) > 1 else ops.BERN_EPS)
 
 
@@ -108,6 +111,8 @@ def _inv_any(meta, ye, phi):
             return ops.rqs_inverse(ye, pc[0], pc[1], pc[2], bound, slope)
         if kind == 2:
             return ops.sos_inverse(ye, pc[0], pc[1] if extra[2] else None, slope)
+        if kind == 4:
+            return ops.gauss_inverse(ye, pc[0], pc[1], bound, extra[0])
         return ops.bernstein_inverse(ye, pc[0], extra[0], bound, eps=extra[1] if len(extra) > 1 else ops.BERN_EPS)
 
 
@@ -131,6 +136,11 @@ def _adj_any(meta, xe, phi, gy, gl, reduce):
         if err == 1:
             raise NotImplementedError("zuko_amd: the SOS adjoint kernel is built for 15 coefficients per element (SOSPF default: 3 polynomials of degree 4)")
         _C.check(err, "zk_sos_backward")
+    elif kind == 4:
+        err = lib.zk_gauss_backward(N, D, sizes[0], _ptr(xe), _ptr(phi), _ptr(gy), _ptr(gl), int(reduce), _ptr(gx), _ptr(gphi), _stream())
+        if err == 1:
+            raise NotImplementedError("zuko_amd: the Gaussianization adjoint kernel is built for 1 to 32 components")
+        _C.check(err, "zk_gauss_backward")
     else:
         M = sizes[0]
         from .ops import BERN_EPS

@@ -33,50 +33,60 @@ struct BwdArgs {
 
 extern __shared__ __attribute__((aligned(16))) float bw_lds[];
 
-// KIND 0: affine (total 2), 1: RQS with K bins.  Requires 16-byte aligned phi / gphi and D*total*... any D.
-template <int KIND, int K> __global__ __launch_bounds__(256) void uni_backward_kernel(BwdArgs a) {
-  constexpr int TOTAL = KIND == 0 ? 2 : 3 * K - 1;
-  constexpr int PER_WAVE = 64 * TOTAL + 8;
+// The frame of the packed adjoints: a wave owns 64 consecutive elements; their parameters come in through the wave-private LDS image, `elem(slot, x,
+// gy, gl)` replaces an element's `total` parameters in the image by their gradients (in place: a lane's own words) and returns gx, and the image goes
+// out as g_phi.  `total` is a count (zk_univariate.h): Fixed for the kinds whose element lives in registers, Dyn for a run-time size.  Requires phi and
+// gphi of the same alignment modulo 16 bytes; any N, D.
+template <class C, typename Elem> __device__ __forceinline__ void uni_backward_frame(const BwdArgs& a, C total_count, Elem elem) {
+  const int total = total_count;
+  const int per_wave = 64 * total + 8;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* wsh = bw_lds + wave * PER_WAVE;
+  float* wsh = bw_lds + wave * per_wave;
   const int64_t total_elems = a.N * a.D;
   const int64_t wt0 = ((int64_t)blockIdx.x * 4 + wave) * a.iters;
   for (int64_t it = 0; it < a.iters; ++it) {
     const int64_t e0 = (wt0 + it) * 64;
     if (e0 >= total_elems) break;  // wave-uniform
     const int64_t cnt = (total_elems - e0) < 64 ? (total_elems - e0) : 64;
-    const float* src = a.phi + e0 * TOTAL;
+    const float* src = a.phi + e0 * total;
     const int shift = (int)(((uintptr_t)src / 4) % 4);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    stage_contiguous<float>(src, wsh, cnt * TOTAL, lane);  // (alignment-preserving image, as the forward kernel)
+    stage_contiguous<float>(src, wsh, cnt * total, lane);  // (alignment-preserving image, as the forward kernel)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    const bool valid = lane < cnt;
-    float g[TOTAL];
-    float gxv = 0.f;
-    if (valid) {
+    if (lane < cnt) {
       const int64_t e = e0 + lane;
-      float p[TOTAL];
-#pragma unroll
-      for (int i = 0; i < TOTAL; ++i) p[i] = wsh[shift + lane * TOTAL + i];
       const float glv = a.gl ? (a.gl_reduced ? a.gl[e / a.D] : a.gl[e]) : 0.f;
       const float gyv = a.gy ? a.gy[e] : 0.f;
-      if (KIND == 0) affine_backward_element(p, a.x[e], gyv, glv, a.ls, gxv, g);
-      else rqs_backward_element<K>(p, a.x[e], gyv, glv, a.bound, a.ls, gxv, g);
-      a.gx[e] = gxv;
+      a.gx[e] = elem(wsh + shift + lane * total, a.x[e], gyv, glv);
     }
     // g_phi out through the same LDS image (same shift: gphi has the alignment of phi by contract)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    if (valid) {
-#pragma unroll
-      for (int i = 0; i < TOTAL; ++i) wsh[shift + lane * TOTAL + i] = g[i];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    unstage_contiguous<float>(wsh, shift, a.gphi + e0 * TOTAL, cnt * TOTAL, lane);
+    unstage_contiguous<float>(wsh, shift, a.gphi + e0 * total, cnt * total, lane);
   }
+}
+
+// KIND 0: affine (total 2), 1: RQS with K bins.
+template <int KIND, int K> __global__ __launch_bounds__(256) void uni_backward_kernel(BwdArgs a) {
+  constexpr int TOTAL = KIND == 0 ? 2 : 3 * K - 1;
+  uni_backward_frame(a, Fixed<TOTAL>{}, [&](float* slot, float x, float gyv, float glv) {
+    float p[TOTAL], g[TOTAL];
+    float gxv = 0.f;
+#pragma unroll
+    for (int i = 0; i < TOTAL; ++i) p[i] = slot[i];
+    if (KIND == 0) affine_backward_element(p, x, gyv, glv, a.ls, gxv, g);
+    else rqs_backward_element<K>(p, x, gyv, glv, a.bound, a.ls, gxv, g);
+#pragma unroll
+    for (int i = 0; i < TOTAL; ++i) slot[i] = g[i];
+    return gxv;
+  });
+}
+
+// Gaussianization with a run-time component count K <= ZK_GAUSS_KMAX_BWD: phi = [b(K) | a(K)] per element
+__global__ __launch_bounds__(256) void gauss_backward_kernel(BwdArgs a, int K) {
+  uni_backward_frame(a, Dyn<2 * ZK_GAUSS_KMAX_BWD>{2 * K}, [&](float* slot, float x, float gyv, float glv) { return gauss_backward_element(K, slot, x, gyv, glv); });
 }
 
 // Any bin count up to 64 (zuko/transforms.py:469-477 accepts any `bins`): one lane per element, knots and softmax probabilities
@@ -200,6 +210,30 @@ int zk_univariate_backward(int kind, int64_t N, int64_t D, int K, double bound, 
     const int64_t nb = (N * D + 255) / 256;
     hipLaunchKernelGGL(rqs_backward_generic_kernel, dim3((unsigned)(nb > 8192 ? 8192 : nb)), dim3(256), 0, st, a, K);
   } else return ZK_EINVAL;
+  return ZK_LAUNCH_CHECK();
+}
+
+// Gaussianization (phi [N, D, 2K] = [shift(K) | log-scale(K)], 1 <= K <= 32): fp32, packed phi/gphi of the same alignment modulo 16 bytes.
+int zk_gauss_backward(int64_t N, int64_t D, int K, const void* x, const void* phi, const void* gy, const void* gl, int gl_reduced, void* gx, void* gphi, void* stream) {
+  if (K < 1 || K > ZK_GAUSS_KMAX_BWD) return ZK_EINVAL;
+  if ((((uintptr_t)phi ^ (uintptr_t)gphi) % 16) != 0) return ZK_EINVAL;
+  if (N <= 0 || D <= 0) return 0;
+  BwdArgs a{};
+  a.N = N; a.D = D; a.x = (const float*)x; a.phi = (const float*)phi; a.gy = (const float*)gy; a.gl = (const float*)gl; a.gl_reduced = gl_reduced;
+  a.gx = (float*)gx; a.gphi = (float*)gphi;
+  const int64_t tiles = (N * D + 63) / 64;
+  const int64_t blocks = (tiles + 3) / 4;
+  const size_t lds = 4 * (size_t)(64 * 2 * K + 8) * sizeof(float);
+  if (lds > 64 * 1024) {  // K = 32: 128 bytes of alignment slack above 64 KiB
+    const hipError_t e = hipFuncSetAttribute((const void*)gauss_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  int64_t per_cu = (160 * 1024) / (int64_t)lds;
+  per_cu = per_cu > 8 ? 8 : per_cu;
+  const int64_t cap = 256 * per_cu;
+  const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
+  a.iters = (tiles + (int64_t)grid * 4 - 1) / ((int64_t)grid * 4);
+  hipLaunchKernelGGL(gauss_backward_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, K);
   return ZK_LAUNCH_CHECK();
 }
 

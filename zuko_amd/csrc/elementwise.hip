@@ -182,6 +182,18 @@ template <typename T, bool INV> struct BernDynOp {
   }
 };
 
+// Gaussianization with a.K components (run-time, <= ZK_GAUSS_KMAX): seg0 = shift b(K), seg1 = log-scale a(K), read per component from the wave's LDS
+// image (packed [b | a]) or from global memory (separate tensors, parameters shared by all rows, 2K floats beyond the image)
+template <typename T, bool INV> struct GaussOp {
+  static constexpr int NSEG = 2;
+  static __device__ __forceinline__ int off(int s, int K) { return s * K; }
+  template <typename A> static __device__ __forceinline__ void run(const A& a, const Ld<T> (&ld)[3], T in, T& out, T& ladj, int& k, int64_t e) {
+    k = 0;
+    if (INV) { out = gauss_inv<T>(a.K, ld[0], ld[1], in, T(a.bound), a.n_bisect); ladj = T(0); }
+    else gauss_fwd<T>(a.K, ld[0], ld[1], in, out, ladj);
+  }
+};
+
 // ---- the streaming driver ------------------------------------------------------------------------
 
 template <typename T, bool PACKED, typename Op, typename RunFn>
@@ -340,6 +352,10 @@ template <typename T, typename OpP, typename OpS> static int launch_uni(UniArgs 
   a.total = total;
   const bool packed = is_packed(a, lens, nseg, sizeof(T));
   Plan p = plan<T>(a, packed);
+  if (p.lds > 64 * 1024) {  // a 64 KiB image carries 128 bytes of alignment slack on top
+    const hipError_t e = hipFuncSetAttribute((const void*)uni_kernel<T, true, OpP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    if (e != hipSuccess) return (int)e;
+  }
   if (packed) hipLaunchKernelGGL((uni_kernel<T, true, OpP>), p.grid, dim3(256), p.lds, st, a);
   else hipLaunchKernelGGL((uni_kernel<T, false, OpS>), p.grid, dim3(256), 0, st, a);
   return ZK_LAUNCH_CHECK();
@@ -814,6 +830,30 @@ int zk_bernstein_inverse(int dtype, int64_t N, int64_t D, int M, int bounded, do
   a.bound = bound; a.bounded = bounded; a.n_bisect = n_bisect; a.eps = eps;
   hipStream_t st = (hipStream_t)stream;
   return ZK_DISPATCH(dtype, (launch_bern<float, true>(a, M, st)), (launch_bern<double, true>(a, M, st)));
+}
+
+int zk_gauss_forward(int dtype, int64_t N, int64_t D, int K, const void* x, const void* shift, int64_t b_sN, int64_t b_sD, const void* scale, int64_t a_sN,
+                     int64_t a_sD, void* y, void* ladj, int ladj_reduced, void* stream) {
+  if (K < 1 || K > ZK_GAUSS_KMAX || (dtype != ZK_DTYPE_F32 && dtype != ZK_DTYPE_F64)) return ZK_EINVAL;
+  UniArgs a = base_args(N, D, x, y, ladj, ladj_reduced, nullptr);
+  a.seg[0] = {shift, b_sN, b_sD}; a.seg[1] = {scale, a_sN, a_sD}; a.seg[2] = a.seg[1];
+  a.K = K;
+  const int lens[2] = {K, K};
+  hipStream_t st = (hipStream_t)stream;
+  return ZK_DISPATCH(dtype, (launch_uni<float, GaussOp<float, false>, GaussOp<float, false>>(a, lens, 2, st)),
+                     (launch_uni<double, GaussOp<double, false>, GaussOp<double, false>>(a, lens, 2, st)));
+}
+
+int zk_gauss_inverse(int dtype, int64_t N, int64_t D, int K, double bound, int n_bisect, const void* y, const void* shift, int64_t b_sN, int64_t b_sD,
+                     const void* scale, int64_t a_sN, int64_t a_sD, void* x, void* stream) {
+  if (K < 1 || K > ZK_GAUSS_KMAX || (dtype != ZK_DTYPE_F32 && dtype != ZK_DTYPE_F64) || n_bisect < 0 || !(bound > 0.0)) return ZK_EINVAL;
+  UniArgs a = base_args(N, D, y, x, nullptr, 0, nullptr);
+  a.seg[0] = {shift, b_sN, b_sD}; a.seg[1] = {scale, a_sN, a_sD}; a.seg[2] = a.seg[1];
+  a.K = K; a.bound = bound; a.n_bisect = n_bisect;
+  const int lens[2] = {K, K};
+  hipStream_t st = (hipStream_t)stream;
+  return ZK_DISPATCH(dtype, (launch_uni<float, GaussOp<float, true>, GaussOp<float, true>>(a, lens, 2, st)),
+                     (launch_uni<double, GaussOp<double, true>, GaussOp<double, true>>(a, lens, 2, st)));
 }
 
 int zk_diag_normal_log_prob(int dtype, int64_t N, int64_t D, const void* z, const void* loc, const void* scale, const void* ladj, void* out, void* stream) {

@@ -595,4 +595,79 @@ template <typename T, class C> __device__ __forceinline__ T bern_inv(C NC, const
   return x;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gaussianization (zuko/transforms.py:834-875): y = sqrt(2) erfinv(c mean_k erf(u_k / sqrt(2))), u_k = x exp(a_k) + b_k, c = 1 - 1e-6.
+// The shift b(K) and the unconstrained log-scale a(K) are read through `ldb(k)` / `lda(k)`; K is a run-time count and no array is sized by it.
+//
+// Cancellation-free form.  erf saturates and erfinv near +-1 amplifies a rounding error by sqrt(pi/2) exp(y^2/2) (2e4 at |y| = 4.4), so the
+// expression tree above loses the tails in float32.  Here BOTH tails of the mixture are accumulated from one erfc per component,
+//   lo = sum_k Phi(u_k),  hi = sum_k Phi(-u_k),   Phi(-|u|) = erfc(|u| / sqrt(2)) / 2  (no cancellation), the other side 1 - that,
+// the smaller one is kept (when it is small every term of it is a directly evaluated erfc), the shrink by c is applied to that tail,
+//   q' = q + 0.5e-6 (1 - 2 q)    (from c (2 q - 1) = 2 q' - 1),
+// and inverted by the complementary inverse: y = -+ |Phi^-1(q')|.  x far out gives q = 0, q' = 0.5e-6, |y| = 4.89: bounded as the reference's.
+// log dy/dx = log c - log K + y^2/2 + log sum_k exp(a_k - u_k^2/2): the sum as a streaming max-subtracted log-sum-exp (m, S), so a derivative
+// that underflows in the reference (-inf) stays finite here; it is never NaN or +inf for finite inputs.
+// ---------------------------------------------------------------------------------------------
+#define ZK_GAUSS_KMAX 64      /* components of the forward / inverse kernels; ops.GAUSS_K_MAX mirrors it */
+#define ZK_GAUSS_KMAX_BWD 32  /* components of the adjoint kernel (its LDS image: 64 elements x 2K floats per wave) */
+
+__device__ __forceinline__ float t_erfc(float v) { return erfcf(v); }
+__device__ __forceinline__ double t_erfc(double v) { return erfc(v); }
+__device__ __forceinline__ float t_ncdfinv(float v) { return normcdfinvf(v); }
+__device__ __forceinline__ double t_ncdfinv(double v) { return normcdfinv(v); }
+
+// One sweep over the components: returns y.  MODE 0: the value only (bisection).  MODE 1: also (m, S) with sum_k exp(a_k - u_k^2/2) = exp(m) S.
+// MODE 2 (adjoint): also R = sum_k exp(a_k - u_k^2/2 - m) u_k exp(a_k).
+template <typename T, int MODE, typename LdB, typename LdA> __device__ __forceinline__ T gauss_sweep(int K, LdB ldb, LdA lda, T x, T& m, T& S, T& R) {
+  const T rsqrt2 = T(0.70710678118654752440), ninf = T(-INFINITY);
+  T lo = T(0), hi = T(0);
+  m = ninf; S = T(0); R = T(0);
+  for (int k = 0; k < K; ++k) {
+    const T a = lda(k);
+    const T s = t_exp(a);
+    const T u = x * s + ldb(k);
+    const T e = T(0.5) * t_erfc(t_abs(u) * rsqrt2);
+    const bool neg = u < T(0);
+    lo += neg ? e : T(1) - e;
+    hi += neg ? T(1) - e : e;
+    if (MODE >= 1) {
+      const T t = a - T(0.5) * (u * u);
+      const bool up = t > m;                                      // (false for NaN: the value is NaN then, and so is ladj through y)
+      const T r = (t > ninf) ? t_exp(up ? m - t : t - m) : T(0);  // exp(-inf) = 0 on the first component; t = -inf adds nothing
+      S = up ? S * r + T(1) : S + r;
+      if (MODE == 2) R = up ? R * r + u * s : R + r * (u * s);
+      m = up ? t : m;
+    }
+  }
+  const bool lower = lo <= hi;
+  T q = (lower ? lo : hi) / T(K);
+  q = q + T(0.5e-6) * (T(1) - T(2) * q);
+  const T yt = t_ncdfinv(q);  // <= 0
+  return lower ? yt : -yt;
+}
+
+template <typename T> __device__ __forceinline__ T gauss_ladj(int K, T y, T m, T S) {
+  const T lcK = T(-1.0000005000003333e-6) - t_log(T(K));  // log(1 - 1e-6) - log K
+  return (lcK + T(0.5) * (y * y)) + (m + t_log(S));
+}
+
+template <typename T, typename LdB, typename LdA> __device__ __forceinline__ void gauss_fwd(int K, LdB ldb, LdA lda, T x, T& y, T& ladj) {
+  T m, S, R;
+  y = gauss_sweep<T, 1>(K, ldb, lda, x, m, S, R);
+  ladj = gauss_ladj<T>(K, y, m, S);
+}
+
+// fixed-count bisection on [-B, B] (utils.py:170-180; n = ceil(log2(2B/eps)), transforms.py:615)
+template <typename T, typename LdB, typename LdA> __device__ __forceinline__ T gauss_inv(int K, LdB ldb, LdA lda, T y, T bound, int n) {
+  T a = -bound, b = bound;
+  for (int it = 0; it < n; ++it) {
+    const T mid = (a + b) / T(2);
+    T m, S, R;
+    const bool below = gauss_sweep<T, 0>(K, ldb, lda, mid, m, S, R) < y;
+    a = below ? mid : a;
+    b = below ? b : mid;
+  }
+  return (a + b) / T(2);
+}
+
 }  // namespace zk

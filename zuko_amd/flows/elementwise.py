@@ -18,7 +18,7 @@ from torch.distributions import Transform
 
 from ..lazy import LazyTransform
 from ..nn import MLP
-from ..transforms import DependentTransform, MonotonicAffineTransform
+from ..transforms import DependentTransform, GaussianizationTransform, MonotonicAffineTransform, MonotonicRQSTransform
 from ..utils import unpack
 
 
@@ -47,7 +47,9 @@ class ElementWiseTransform(LazyTransform):
 
     def forward(self, c: Tensor | None = None) -> Transform:
         if self.hyper is None:
-            phi = tuple(self.phi)
-        else:
-            phi = unpack(self.hyper(c).unflatten(-1, (-1, self.total)), self.shapes)
-        return DependentTransform(self.univariate(*phi), 1)
+            return DependentTransform(self.univariate(*self.phi), 1)
+        phi = self.hyper(c).unflatten(-1, (-1, self.total))
+        u = self.univariate(*unpack(phi, self.shapes))
+        if type(u) in (MonotonicAffineTransform, MonotonicRQSTransform, GaussianizationTransform):
+            u._packed = phi  # the views above were cut from this tensor: autograd can differentiate it directly (no split, no concatenation)
+        return DependentTransform(u, 1)

@@ -29,6 +29,17 @@ def _refuse_continuous(flow, what: str) -> None:
                                   "estimate back after every attempted step, and the number of steps depends on the data")
 
 
+def _refuse_rotation(flow, what: str) -> None:
+    """A Gaussianization flow rebuilds its rotations R = exp(A - A^T) on every call with torch.linalg.matrix_exp, which may choose the order of its
+    approximation from the matrix norm on the host: a synchronisation that a stream capture does not allow."""
+    from .lazy import UnconditionalTransform
+    from .transforms import RotationTransform
+
+    if any(isinstance(m, UnconditionalTransform) and m.f is RotationTransform for m in flow.modules()):
+        raise NotImplementedError(f"zuko_amd.{what}: a Gaussianization flow (GF / RotationTransform) cannot be captured: torch.linalg.matrix_exp, which builds "
+                                  "its rotations on every call, may synchronise with the host")
+
+
 class CapturedCall:
     """`captured(x[, c])` -> the output of the captured call for these inputs (a view of the graph's static output buffer: valid until the next
     call; `.clone()` it to keep it).  Shapes, dtypes and devices are fixed at capture time, and so are the WEIGHTS: the fused kernels read weight
@@ -56,6 +67,7 @@ def capture(flow, x: Tensor, c: Tensor | None = None, call: str = "log_prob", wa
     if not x.is_cuda:
         raise ValueError("zuko_amd.capture: inputs must live on the GPU")
     _refuse_continuous(flow, "capture")
+    _refuse_rotation(flow, "capture")
     xs = x.detach().clone()
     cs = None if c is None else c.detach().clone()
 
@@ -104,6 +116,7 @@ def capture_step(flow, optimizer, x: Tensor, c: Tensor | None = None, loss_fn=No
     if not x.is_cuda:
         raise ValueError("zuko_amd.capture_step: inputs must live on the GPU")
     _refuse_continuous(flow, "capture_step")
+    _refuse_rotation(flow, "capture_step")
     for group in optimizer.param_groups:
         if group.get("capturable") is False:
             raise ValueError("zuko_amd.capture_step: the optimizer must be built with capturable=True (its step counter has to live on the device)")

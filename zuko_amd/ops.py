@@ -7,7 +7,9 @@ flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shap
 calls that need gradients (no adjoint kernel yet).  Likewise the Gaussian mixture density (gmm_log_prob) runs the reference's expressions as torch ops
 ON THE DEVICE outside its kernels' envelope (features or components above 64, sample dimensions broadcast over a batch of mixtures).  And the
 continuous flow (cnf_integrate) hands every call its step kernel does not serve — gradients, float64, Hutchinson's estimator, other activations or
-shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.
+shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.  The Gaussianization map (gauss_forward / gauss_inverse) runs the
+reference's expressions as torch ops ON THE DEVICE for more than 64 components (32 with gradients), for float64 calls that need gradients and under
+GAUSS_KERNEL = False.
 """
 
 from __future__ import annotations
@@ -700,6 +702,93 @@ def mnn_inverse(y: Tensor, signal: Tensor, network, feat=None, bound: float = MN
     _C.check(_C.lib().zk_mnn_inverse(a, _stream()), "zk_mnn_inverse")
     del data
     return x.reshape(shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# Gaussianization (GF): zk_gauss_forward / zk_gauss_inverse / zk_gauss_backward, torch ops when the kernels do not serve the call
+# ------------------------------------------------------------------------------------------------
+
+GAUSS_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_gf.py measures the kernels against it)
+GAUSS_K_MAX = 64  # ZK_GAUSS_KMAX of csrc/zk_univariate.h
+GAUSS_K_MAX_BWD = 32  # ZK_GAUSS_KMAX_BWD: the adjoint's LDS image
+GAUSS_BOUND = 10.0
+GAUSS_EPS = 1e-6
+
+
+def gauss_supported(K: int, dtype=torch.float32, needs_grad: bool = False) -> bool:
+    """Do the kernels serve K components in `dtype`?  Forward and inverse: float32 / float64, 1 <= K <= 64; with gradients: float32 (bfloat16
+    trains on float32 copies), 1 <= K <= 32."""
+    if needs_grad:
+        return dtype in (torch.float32, torch.bfloat16) and 1 <= K <= GAUSS_K_MAX_BWD
+    return dtype in (torch.float32, torch.float64) and 1 <= K <= GAUSS_K_MAX
+
+
+def _gauss_torch_f(x: Tensor, shift: Tensor, scale: Tensor) -> Tensor:
+    """The reference's expression tree (zuko/transforms.py:869-875)."""
+    u = x[..., None] * torch.exp(scale) + shift
+    return torch.erfinv(torch.erf(u / math.sqrt(2)).mean(dim=-1) * (1 - 1e-6)) * math.sqrt(2)
+
+
+def _gauss_check(x: Tensor, shift: Tensor, scale: Tensor) -> int:
+    _require_device(x, shift, scale)
+    if shift.dim() < 1 or shift.shape[-1] != scale.shape[-1] or shift.shape[-1] < 1:
+        raise ValueError(f"zuko_amd: gaussianization: shift [..., K] and scale [..., K] expected, got {tuple(shift.shape)} and {tuple(scale.shape)}")
+    return shift.shape[-1]
+
+
+@_bf16_trains_in_f32
+def gauss_forward(x: Tensor, shift: Tensor, scale: Tensor, reduce: bool = False, packed: Tensor | None = None):
+    """(y, ladj) of the Gaussianization map — see include/zuko_amd.h: zk_gauss_forward.  `packed`: the phi[..., D, 2K] = [shift | scale] tensor the
+    two views were cut from, when the caller has it.  Outside the kernels' envelope (gauss_supported) and under GAUSS_KERNEL = False: the
+    reference's torch ops on the device, the derivative by torch.autograd.grad (zuko/transforms.py:623-637)."""
+    from . import autograd as AG
+
+    K = _gauss_check(x, shift, scale)
+    grad = AG.needs_grad(x, shift, scale)
+    if not (GAUSS_KERNEL and gauss_supported(K, x.dtype, grad)):
+        with torch.enable_grad():
+            xg = x.expand(torch.broadcast_shapes(x.shape, shift.shape[:-1], scale.shape[:-1])).clone().requires_grad_()
+            y = _gauss_torch_f(xg, shift, scale)
+        jac = torch.autograd.grad(y, xg, torch.ones_like(y), create_graph=grad)[0]
+        if not grad:
+            y = y.detach()
+        ladj = jac.log()
+        return y, (ladj.sum(dim=-1) if reduce else ladj)
+    if grad:
+        if _packed_ok(x, packed, 2 * K):
+            return AG.UnivariatePackedFn.apply((4, GAUSS_BOUND, 0.0, (K, K), ()), reduce, x, packed)
+        return AG.UnivariateFn.apply(4, GAUSS_BOUND, 0.0, reduce, x, shift, scale)
+    pr = _Prepared(x, [(shift, 1), (scale, 1)])
+    if reduce and len(pr.shape) == 0:
+        raise ValueError("zuko_amd: cannot reduce ladj of a 0-d input")
+    y, ladj = pr.out(), pr.out_ladj(reduce)
+    (b, bn, bd), (a, an, ad) = pr.params
+    err = _C.lib().zk_gauss_forward(pr.code, pr.N, pr.D, K, _ptr(pr.x), _ptr(b), bn, bd, _ptr(a), an, ad, _ptr(y), _ptr(ladj), int(reduce), _stream())
+    _C.check(err, "zk_gauss_forward")
+    return y, ladj
+
+
+@_bf16_trains_in_f32
+def gauss_inverse(y: Tensor, shift: Tensor, scale: Tensor, bound: float = GAUSS_BOUND, eps: float = GAUSS_EPS) -> Tensor:
+    """x with f(x) = y by n = ceil(log2(2 bound / eps)) bisection steps on [-bound, bound] (zuko/transforms.py:609-617): zk_gauss_inverse, its
+    gradients by the inverse function theorem on the forward map's adjoint kernel; the same loop in torch ops where gauss_forward runs torch ops."""
+    from . import autograd as AG
+
+    K = _gauss_check(y, shift, scale)
+    grad = AG.needs_grad(y, shift, scale)
+    n = math.ceil(math.log2(2 * bound / eps))
+    if not (GAUSS_KERNEL and gauss_supported(K, y.dtype, grad)):
+        phi = [p for p in (shift, scale) if p.requires_grad] if torch.is_grad_enabled() else []
+        ye = y.expand(torch.broadcast_shapes(y.shape, shift.shape[:-1], scale.shape[:-1]))
+        return _MnnBisection.apply(lambda v: _gauss_torch_f(v, shift, scale), ye, float(bound), n, *phi)
+    if grad:
+        return AG.UnivariateInverseFn.apply(4, float(bound), 0.0, (float(eps),), y, shift, scale)
+    pr = _Prepared(y, [(shift, 1), (scale, 1)])
+    x = pr.out()
+    (b, bn, bd), (a, an, ad) = pr.params
+    err = _C.lib().zk_gauss_inverse(pr.code, pr.N, pr.D, K, float(bound), n, _ptr(pr.x), _ptr(b), bn, bd, _ptr(a), an, ad, _ptr(x), _stream())
+    _C.check(err, "zk_gauss_inverse")
+    return x
 
 
 # ------------------------------------------------------------------------------------------------

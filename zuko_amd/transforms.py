@@ -35,9 +35,11 @@ __all__ = [
     "CouplingTransform",
     "DependentTransform",
     "FreeFormJacobianTransform",
+    "GaussianizationTransform",
     "MonotonicAffineTransform",
     "MonotonicNetworkTransform",
     "MonotonicRQSTransform",
+    "RotationTransform",
     "SOSPolynomialTransform",
     "ShiftedSOSPolynomialTransform",
     "SoftclipTransform",
@@ -182,6 +184,49 @@ class BoundedBernsteinTransform(BernsteinTransform):
     r"""Bernstein polynomial pinned to the identity at +-B.  Mirrors zuko/transforms.py:780-831."""
 
     bounded = True
+
+
+class GaussianizationTransform(_Univariate):
+    r"""y = \Phi^{-1}(c mean_k \Phi(exp(a_k) x + b_k)), c = 1 - 1e-6, with shift b[*, K] and unconstrained scale a[*, K]: the univariate map of the
+    Gaussianization flow.  Mirrors zuko/transforms.py:834-875 + MonotonicTransform (:570-637): value and log-derivative in one launch
+    (zk_gauss_forward; the derivative in closed form instead of torch.autograd.grad), the inverse by the reference's bisection on [-bound, bound]
+    to `eps` (zk_gauss_inverse), gradients by zk_gauss_backward.  More than 64 components (32 with gradients) and float64 calls that need
+    gradients run the reference's expressions as torch ops on the device (zuko_amd/ops.py: gauss_forward)."""
+
+    def __init__(self, shift: Tensor, scale: Tensor, bound: float = 10.0, eps: float = 1e-6, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.shift = shift
+        self.unconstrained_scale = scale
+        self.bound = bound
+        self.eps = eps
+
+    def _forward(self, x, reduce):
+        return ops.gauss_forward(x, self.shift, self.unconstrained_scale, reduce, packed=getattr(self, "_packed", None))
+
+    def _inverse(self, y: Tensor) -> Tensor:
+        return ops.gauss_inverse(y, self.shift, self.unconstrained_scale, self.bound, self.eps)
+
+
+class RotationTransform(Transform):
+    r"""y = R x with R = exp(A - A^T), orthogonal because A - A^T is skew-symmetric; log|det J| = 0.  Mirrors zuko/transforms.py:1217-1244, on torch
+    ops (matrix_exp and the library's matrix products): gradients reach A through autograd."""
+
+    domain = constraints.real_vector
+    codomain = constraints.real_vector
+    bijective = True
+
+    def __init__(self, A: Tensor, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.R = torch.linalg.matrix_exp(A - A.mT)
+
+    def _call(self, x: Tensor) -> Tensor:
+        return torch.einsum("...ij,...j->...i", self.R, x)
+
+    def _inverse(self, y: Tensor) -> Tensor:
+        return torch.einsum("...ij,...i->...j", self.R, y)
+
+    def log_abs_det_jacobian(self, x: Tensor, y: Tensor) -> Tensor:
+        return torch.zeros_like(x[..., 0])
 
 
 class MonotonicNetworkTransform(_Univariate):
