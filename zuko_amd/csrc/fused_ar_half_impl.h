@@ -22,8 +22,9 @@
 // weights whose magnitudes spread over more than the f16 range WITHIN a layer keep the three-part kernel (zuko_amd/fused.py: eligibility).
 // A hidden value that overflows f32 becomes NaN for its sample, as in fused_ar_split_impl.h (inf - inf in the low part).
 //
-// Stream layout, ring, raw reads and counted waits are those of fused_ar_split_impl.h with TWO 1 KiB images (h, l) per block; the frame around the
-// matrix part (LDS carve-up, input stage, epilogue) is zk_ar_common.h's.
+// Stream layout, raw reads and counted waits are those of fused_ar_split_impl.h with TWO 1 KiB images (h, l) per block; the frame around the
+// matrix part (LDS carve-up, input stage, epilogue) is zk_ar_common.h's.  The ring is this header's: four slots with a chunk visible one chunk
+// before it is read (ArhRing4) where they fit the LDS, else the three-slot ring of fused_ar_static_impl.h with a wait that knows the x loads (ArhRing).
 #pragma once
 #include "fused_ar_split_impl.h"
 
@@ -151,6 +152,89 @@ template <int WAVES, int CH, int NR> struct ArhRing : ArRingS<WAVES, CH, NR> {
   }
 };
 
+// The FOUR-slot ring (Shape::NR == 4; zuko_amd/static_ar.py chooses it where four slots fit the LDS, and half_schedule there is this
+// protocol as a list of events, checked by tests/test_half_ring_schedule.py).  Chunk g of the stream (counted on through the tiles) lives in
+// slot g mod 4.  Its barrier B_g stands INSIDE the chunk, behind the request of the block at images BPOS, BPOS + 1:
+//     wait, by vmcnt, for the wavefront's own pieces of chunk g + 2 (issued at B_(g-1): the only weight DMAs in flight)
+//     barrier                                          -> chunk g + 2 is visible to every wavefront, a whole chunk before its first read
+//     issue the pieces of chunk g + 3 into slot (g - 1) mod 4: every wavefront has SETTLED its last read of chunk g - 1 in front of B_g
+//                                                         (BPOS >= 2 (ARH_LOOK + 1): the reads outstanding at B_g belong to chunk g)
+// so no read waits at a barrier, a look-ahead request may cross the chunk boundary, and nothing drains the LDS queue.  Moving on to the next
+// slot is one scalar add / compare / select and one vector add; the stream address is a scalar byte offset advanced by a constant and
+// wrapped by one compare, the lane's 16-byte column a constant 32-bit vector offset.  Where the stream ends before image BPOS + 1 of its last
+// chunk, B stands behind the chunk's last image and drains the LDS queue too (once per tile).  XV: as ArhRing's — vector-memory loads
+// younger than the pieces waited for (the next tile's rows: arh_body's XPOS); every other B waits for vmcnt(0), a whole chunk after the
+// request (the running log-derivative's load and a tile's stores, if still in flight, are sat out at the tile's first B).
+template <int WAVES, int CH, int IMAGES, int BPOS> struct ArhRing4 {
+  static constexpr int NR = 4, PER = CH / WAVES, PIVOT = PER > 4 ? 4 : 0, CHB = CH * AR_TF * 4, NCH = (IMAGES + CH - 1) / CH;
+  static_assert(PER * WAVES == CH && PER <= 6 && BPOS % 2 == 0 && BPOS >= 2 * (ARH_LOOK + 1) && BPOS + 1 < CH && CH % 2 == 0 && IMAGES % 2 == 0, "ring geometry");
+  static constexpr int trigger(int c) {  // the image of chunk c behind whose request B stands (static_ar.half_trigger)
+    const int last = (IMAGES < (c + 1) * CH ? IMAGES : (c + 1) * CH) - 1;
+    return c * CH + BPOS + 1 < last ? c * CH + BPOS + 1 : last;
+  }
+  static constexpr int first_trigger_from(int pos) {  // the first B behind a load issued in front of the request of image pos
+    for (int c = 0; c < NCH; ++c)
+      if (trigger(c) >= pos) return trigger(c);
+    return -1;
+  }
+  const char* gsrc;    // the stream + this wavefront's pieces of a chunk (scalar)
+  char* ldst;          // the ring + the same
+  unsigned goff, gend; // byte offset of the chunk requested next; bytes of the stream
+  unsigned fill_off;   // byte offset of the slot it goes to
+  unsigned read_off;   // byte offset of the slot being read
+  unsigned lane_off;   // LDS byte address of the ring + lane * 16
+  unsigned lane16;     // lane * 16
+  unsigned cur_off;    // lane_off + read_off
+  __device__ __forceinline__ void start(float* lds, const float* stream, int n_chunks, int wave, int lane) {
+    const int b0 = wave * PER + PIVOT;
+    gsrc = reinterpret_cast<const char*>(stream + b0 * AR_TF);
+    ldst = reinterpret_cast<char*>(lds + b0 * AR_TF);
+    goff = 0; gend = (unsigned)n_chunks * CHB; fill_off = 0;
+    lane16 = (unsigned)lane * 16;
+    lane_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)lds) + lane16;
+#pragma unroll
+    for (int i = 0; i < NR - 1; ++i) issue();
+    read_off = (NR - 1) * CHB;  // (the first read, position 0, moves on to slot 0)
+    cur_off = lane_off;
+  }
+  template <int I> __device__ __forceinline__ void dma(const char* g, char* l) {
+    if constexpr (I < PER) {
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, (I - PIVOT) * AR_TF * 4, 0);
+      dma<I + 1>(g, l);
+    }
+  }
+  __device__ __forceinline__ void issue() {
+    asm volatile("" : "+v"(lane16));  // (kept apart from the scalar address: scalar base + 32-bit vector offset, no 64-bit vector add per chunk)
+    if (ARX_ABL != 1) dma<0>(gsrc + goff + (size_t)lane16, ldst + fill_off);
+    goff = (goff + CHB == gend) ? 0 : goff + CHB;
+    fill_off = (fill_off + CHB == NR * CHB) ? 0 : fill_off + CHB;
+  }
+  template <int XV, bool DRAIN> __device__ __forceinline__ void boundary() {
+    if constexpr (DRAIN) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(XV) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XV) : "memory");
+    if (ARX_ABL != 4) __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    issue();
+    asm volatile("" ::: "memory");
+  }
+  template <int S, int XV = 0> __device__ __forceinline__ f32x4 read() {
+    static_assert(S >= 0 && S < IMAGES, "stream position");
+    if constexpr (S % CH == 0) {
+      read_off = (read_off + CHB == NR * CHB) ? 0 : read_off + CHB;
+      cur_off = lane_off + read_off;
+    }
+    f32x4 v;
+    if (ARX_ABL == 5) {
+      asm volatile("v_mov_b32 %0, %1" : "=v"(v[0]) : "v"(cur_off));
+      v[1] = v[2] = v[3] = v[0];
+    } else {
+      asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(cur_off), "n"((S % CH) * AR_TF * 4));
+    }
+    if constexpr (S == trigger(S / CH)) boundary<XV, (S % CH != BPOS + 1)>();
+    return v;
+  }
+};
+
 // one hidden layer: out = fma(W' in', d, bias) over the blocks of the generated pattern (W', in': the scaled operands; d = 2^-(ew + ea))
 template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d) {
   typedef ArxPat<S> P;
@@ -252,25 +336,31 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
 // arx_kernel's.  TERM: the terminal launch of a log_prob (arht_kernel): the base's tables staged behind the feature map, no y rows written, the
 // log-density in the ladj buffer (zk_ar_common.h: ArArgs::base_loc).
 template <class S, typename Uni, bool DIAG, bool TERM> __device__ __forceinline__ void arh_body(const ArArgs& a) {
-  typedef ArhRing<S::WAVES, S::CH, S::NR> Ring;
-  static_assert(S::WAVES == 8 && S::NR == 3 && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::OCC == 2, "two-part split kernels: widths <= 256, two wavefronts per SIMD");
+  constexpr bool RING4 = S::NR == 4;
+  typedef std::conditional_t<RING4, ArhRing4<S::WAVES, S::CH, S::IMAGES, S::BPOS>, ArhRing<S::WAVES, S::CH, S::NR>> Ring;
+  static_assert(S::WAVES == 8 && (S::NR == 3 || S::NR == 4) && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::OCC == 2, "two-part split kernels: widths <= 256, two wavefronts per SIMD");
   constexpr int NT = Uni::NT, FPL = Uni::FPL, TOTAL = Uni::TOTAL, WAVES = S::WAVES;
   constexpr int NG = S::NG;
   constexpr int NSTEP = S::GOFF[NG];  // (group, in pair) steps of the last layer, NT blocks each
+  static_assert(S::IMAGES == S::LAST_BASE + 2 * NSTEP * NT && (S::IMAGES + S::CH - 1) / S::CH == S::NCHUNK, "stream length");
   constexpr bool XLDS = S::XLDS;
   const ArLane ln;
   const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
 
   Ring ring;
-  // (ArRingS::start written out: called as the member, this kernel's first two requests come out with scalar base addresses and the loop's vector
-  //  base is built a second time — one vector instruction more, profiles/ar_frame/census.md)
-  ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
-  ring.load_chunk = 0; ring.load_slot = 0;
+  if constexpr (RING4) {
+    ring.start(ars_lds, a.stream, a.n_chunks, wave, lane);
+  } else {
+    // (ArRingS::start written out: called as the member, this kernel's first two requests come out with scalar base addresses and the loop's vector
+    //  base is built a second time — one vector instruction more, profiles/ar_frame/census.md)
+    ring.lds = ars_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
+    ring.load_chunk = 0; ring.load_slot = 0;
 #pragma unroll
-  for (int i = 0; i < S::NR - 1; ++i) ring.issue();
-  ring.slot = S::NR - 1;
-  ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
-  ring.cur_off = ring.lds_off;
+    for (int i = 0; i < S::NR - 1; ++i) ring.issue();
+    ring.slot = S::NR - 1;
+    ring.lds_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)ars_lds);
+    ring.cur_off = ring.lds_off;
+  }
 
   // x rows of a tile, 4 values of S::NIT 16-column groups per lane.  Every lane loads (a column group that ends beyond DIN is read at the
   // row's last four columns and zeroed afterwards): the number of load instructions in flight is the same for every wavefront (ArhRing)
@@ -349,7 +439,12 @@ template <class S, typename Uni, bool DIAG, bool TERM> __device__ __forceinline_
     f32x4 w[LOOKL + 1][2];
     // the next tile of this workgroup: its rows travel during the last layer.  The LAST tile requests its own rows again, so that the
     // count of loads in flight does not depend on the tile; XPOS is the one advance of the ring that finds them younger than its chunk
-    constexpr int XPOS = ARH_PREFETCH ? (S::LAST_BASE + S::CH - 1) / S::CH * S::CH : -1;
+    // (four-slot ring: the first barrier behind the last layer's first request)
+    constexpr int XPOS = []() constexpr {
+      if constexpr (!ARH_PREFETCH) return -1;
+      else if constexpr (RING4) return Ring::first_trigger_from(S::LAST_BASE);
+      else return (S::LAST_BASE + S::CH - 1) / S::CH * S::CH;
+    }();
     if (ARH_PREFETCH) {
       asm volatile("" ::: "memory");
       x_request(tile + gridDim.x < a.n_tiles ? tile + gridDim.x : tile, xnext);

@@ -384,10 +384,80 @@ def half_tables(plan, uni_kind: int, act: int = 1):
     last = gathers[NH][: n_last * 512]
     g = [np.asarray(x) for x in gathers[:NH]] + [np.concatenate([last, -np.ones(pad_blocks * 512, dtype=np.int32)]).astype(np.int32)]
     out = {k: v for k, v in t.items() if k not in ("split", "TRAIN_OK")}
+    # Ring depth: FOUR slots (a chunk becomes visible one chunk before it is read: half_schedule) where they fit the 160 KiB next to the bias
+    # image, the tables and the row tiles the three-slot geometry has chosen (XLDS stays what it was); else the three-slot protocol
+    bias_floats = plan.bias_off[-1] + len(plan.bias_gather[-1])
+    rows = t["WAVES"] * 16 * (((t["D"] + 3) // 4) * 4 + 4) if t["XLDS"] else 0
+    nr = 4 if (4 * ch * 256 + bias_floats + 1024 + 256 + rows) * 4 <= 160 * 1024 else 3
     out.update({"half": 1, "BASE": [2 * sum(t["NB"][:l]) for l in range(NH)], "LAST_BASE": 2 * sum(t["NB"]), "NCHUNK": n_chunks, "STREAM_IMAGES": max(n_chunks * ch, cursor + 2 * pad_blocks),
-                "NR": 3, "TRAIN_OK": 0})
+                "NR": nr, "IMAGES": cursor, "BPOS": HALF_BPOS, "TRAIN_OK": 0})
     plan._half_cache = ((uni_kind, act), (out, g))
     return out, g
+
+
+HALF_LOOK = 1  # == ARH_LOOK of csrc/fused_ar_half_impl.h: blocks of weight images requested ahead of the matrix instructions that consume them
+HALF_BPOS = 8  # four-slot ring: the chunk's barrier stands behind the request of the block at images BPOS, BPOS + 1 (even, >= 2 (HALF_LOOK + 1))
+
+
+def half_trigger(t: dict, c: int) -> int:
+    """Four-slot ring: the stream position (image) of chunk c behind whose read the chunk's barrier stands — BPOS + 1, or the chunk's last real
+    image when the stream ends before it (the last chunk; the wait there also drains the wavefront's LDS reads)."""
+    ch = t["CH"]
+    last = min(t["IMAGES"], (c + 1) * ch) - 1
+    return min(c * ch + t["BPOS"] + 1, last)
+
+
+def half_schedule(t: dict) -> tuple:
+    """The static schedule of the two-part kernel's weight ring (csrc/fused_ar_half_impl.h: ArhRing / ArhRing4, arh_hidden, arh_body), the same for
+    every wavefront: (prologue, one tile pass), each a list of events in program order
+
+        ("issue",)            the wavefront's PER DMA pieces of the next stream chunk into the next slot (both counted round-robin from 0)
+        ("x", n)              n vector-memory loads of the next tile's rows
+        ("wait", n, drain)    s_waitcnt vmcnt(n); drain: also lgkmcnt(0)
+        ("barrier",)
+        ("read", pos)         LDS read of stream image pos of this pass
+        ("settle", n)         s_waitcnt lgkmcnt(n): all but the youngest n image reads have returned
+
+    (the bias reads that share the LDS queue stand in front of the request a settle leaves outstanding: they do not change which images return)."""
+    ch, nr, per, look = t["CH"], t["NR"], t["CH"] // t["WAVES"], HALF_LOOK
+    nit, last_base, images = t["NIT"], t["LAST_BASE"], t["IMAGES"]
+    pro = [("issue",)] * (nr - 1) + [("x", nit), ("wait", 0, True), ("barrier",)]  # (ArLds::stage ends in __syncthreads())
+    if nr == 4:
+        trig = {half_trigger(t, c): c for c in range(t["NCHUNK"])}
+        xpos = min((p for p in trig if p >= last_base), default=-1)  # (none: the rows are consumed, at the next tile's start, in front of the next barrier)
+    else:
+        xpos = -(-last_base // ch) * ch
+    ev = []
+
+    def read(pos):
+        if nr != 4 and pos % ch == 0:
+            ev.extend([("wait", (nr - 2) * per + (nit if pos == xpos else 0), True), ("barrier",), ("issue",)])
+        ev.append(("read", pos))
+        if nr == 4 and pos in trig:
+            ev.extend([("wait", nit if pos == xpos else 0, pos % ch != t["BPOS"] + 1), ("barrier",), ("issue",)])
+
+    def layer(base, nb, last_of):
+        lk = min(look, nb)
+        for b in range(lk):
+            read(base + 2 * b), read(base + 2 * b + 1)
+        for s in range(nb):
+            if s + lk < nb:
+                read(base + 2 * (s + lk)), read(base + 2 * (s + lk) + 1)
+            ahead = lk if s + lk < nb else nb - 1 - s
+            ev.append(("settle", (2 if s + lk < nb else 0) if last_of(s) else 2 * ahead))
+
+    off = 0
+    for l in range(t["NH"]):
+        nb = t["NB"][l]
+        ots = t["B_OT"][off : off + nb]
+        layer(t["BASE"][l], nb, lambda s: s + 1 == nb or ots[s + 1] != ots[s])
+        off += nb
+    ev.append(("x", nit))
+    nbl = (images - last_base) // 2
+    nt = nbl // max(t["GOFF"][-1], 1)
+    ends = {g1 * nt - 1 for g1 in t["GOFF"][1:]}
+    layer(last_base, nbl, lambda s: s in ends)
+    return pro, ev
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -461,7 +531,7 @@ ARX = Family(
 # the two-part twin of that, two f16 parts per operand, inference only (csrc/fused_ar_half_impl.h: arh_kernel); stamped by its own header too
 ARH = dataclasses.replace(
     ARX, prefix="arh", header="fused_ar_half_impl.h", stamp=_half_digest, launcher="zk::arh_launch<Shape, {uni}>",
-    shape=ARX.shape[:2] + (("bool", ("XLDS",)),) + ARX.shape[3:],
+    shape=ARX.shape[:2] + (("int", ("IMAGES", "BPOS")), ("bool", ("XLDS",))) + ARX.shape[3:],
     sig=lambda t, alt: {"half": t},
     index=lambda t: "h" + _digest(t),
     meta=lambda t: dict(_pick(t, "uni", "ACT", "D", "DIN", "HT", "WAVES", "CH", "TRAIN_OK", "XLDS", "NCHUNK"), half=1, split=2),
