@@ -670,6 +670,69 @@ int zk_mnn_image_floats(int S, int n_hidden, int width0, int width1, int width2)
  * tests can name the shapes that reach every geometry.  N >= 1, 1 <= Dsel <= 2^20, both pointers non-NULL; otherwise hipErrorInvalidValue. */
 int zk_mnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block);
 
+/* ---- adjoint of the monotone neural network (NAF training; fp32) ------------------------------------------------------------------------
+ * zk_mnn_backward: the gradients of zk_mnn_forward's (y, ladj) with respect to x, the signal and every weight and bias, for upstream gy and gl.
+ * The forward is recomputed inside the kernel (the forward launch saves nothing); products run on v_mfma_f32_16x16x4_f32.  No atomics: every
+ * block writes one partial per (row chunk, column) into `work`, and a second launch adds the partials in chunk order, applies sign(W) (0 at
+ * W = 0, as the derivative of |W| in PyTorch) and writes the flat parameter order.  The same inputs give the same bits; gx and gsignal of an
+ * element depend on that element only (not on N, Dsel or the geometry).
+ *
+ *   x, signal, feat   as for zk_mnn_forward; every feature may appear in feat at most once (the caller checks it)
+ *   image             n_features BACKWARD images of image_floats floats: the forward image followed by the weights in transposed tile order
+ *                     (zuko_amd/mnn_plan.py: layout_backward, index_table_backward)
+ *   gy                [N, Dsel] contiguous, or NULL (= 0)
+ *   gl                [N, Dsel] contiguous, or [N] with gl_reduced != 0, or NULL (= 0)
+ *   gx                [N, Dsel], row stride ld_gx, or NULL (not wanted)
+ *   gsignal           the signal's layout with row stride ld_gsignal >= Dsel * S, or NULL; nothing is written behind the S values of an element
+ *   gparams           flat [flat_total] in the order of zuko_amd/mnn_plan.py: flat_parameters (weights, then biases), or NULL; parameters of
+ *                     features that feat does not select receive zeros.  Needs `params` (the SIGNED flat parameters, for sign(W); the first
+ *                     flat_weights floats are weights), `grad_table` (DEVICE int32 [n_features, grad_floats]: where every float of a feature's
+ *                     partial goes in the flat order, -1 = nowhere; zuko_amd/mnn_plan.py: grad_table) and `work`
+ *                     (zk_mnn_backward_workspace_floats floats).
+ *   limits            the shapes of zk_mnn_forward whose widths are all <= 64 (zk_mnn_backward_floats says which)
+ * N = 0 launches nothing and still zeroes gparams.  Bad blocks return hipErrorInvalidValue before anything touches the device. */
+typedef struct zk_mnn_bwd_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_mnn_bwd_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t S;
+  int32_t n_hidden;
+  int32_t width0;
+  int32_t width1;
+  int32_t width2;
+  int32_t n_features;
+  int32_t image_floats;    /* floats per backward image (zk_mnn_backward_floats) */
+  int32_t grad_floats;     /* floats per partial (zk_mnn_backward_floats) */
+  int32_t gl_reduced;      /* != 0: gl is [N] */
+  int32_t reserved;        /* 0 */
+  int64_t N;
+  int64_t Dsel;
+  int64_t ldx;
+  int64_t ld_signal;
+  int64_t ld_gx;
+  int64_t ld_gsignal;
+  int64_t flat_total;
+  int64_t flat_weights;
+  const void* x;
+  const void* signal;
+  const void* image;
+  const int32_t* feat;       /* or NULL */
+  const void* gy;            /* or NULL */
+  const void* gl;            /* or NULL */
+  const void* params;        /* with gparams */
+  const int32_t* grad_table; /* with gparams */
+  void* gx;                  /* or NULL */
+  void* gsignal;             /* or NULL */
+  void* gparams;             /* or NULL */
+  void* work;                /* with gparams */
+} zk_mnn_bwd_args_v1;
+int zk_mnn_backward(const zk_mnn_bwd_args_v1* args, void* stream);
+/* Host only.  zk_mnn_backward_floats: the sizes of a backward image and of a partial, or hipErrorInvalidValue for a shape the adjoint does not
+ * serve.  zk_mnn_backward_geometry: a block covers one column and rows_per_chunk rows (a multiple of 64); n_chunks = ceil(N / rows_per_chunk),
+ * a pure function of (N, Dsel) that keeps the grid near 512 blocks.  zk_mnn_backward_workspace_floats: n_chunks * Dsel * grad_floats (0 at N = 0). */
+int zk_mnn_backward_floats(int S, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats);
+int zk_mnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks);
+int zk_mnn_backward_workspace_floats(int64_t N, int64_t Dsel, int S, int n_hidden, int width0, int width1, int width2, int64_t* floats);
+
 /* ---- unconstrained monotone neural network of the unconstrained neural autoregressive flow (UNAF; fp32) ---------------------------------
  * Every feature f owns an integrand network h_f: (1 + S) -> width0 [-> width1 [-> width2]] -> 1 with SIGNED weights and ELU(alpha = 1); its
  * input is cat(u, signal).  With sq(v) = v / (1 + |v / 7|), g(u) = exp(sq(h(u, signal))) and (t_i, w_i) the n_quad-point Gauss-Legendre rule on

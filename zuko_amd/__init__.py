@@ -31,7 +31,7 @@ def invalidate(module) -> None:
         m.__dict__.pop("_split_cache", None)
         for k in ("_sweep_cache", "_unit_cache", "_unit_rows_cache"):  # wavefront form of the layer-wise inverse (flows/autoregressive.py)
             m.__dict__.pop(k, None)
-        for k in ("_mnn_image_cache", "_mnn_feat_cache"):  # weight image of the monotone networks of a NAF (mnn_plan.py)
+        for k in ("_mnn_image_cache", "_mnn_bwd_image_cache", "_mnn_feat_cache"):  # weight image of the monotone networks of a NAF (mnn_plan.py)
             m.__dict__.pop(k, None)
         m.__dict__.pop("_cnf_image_cache", None)  # weight image of the field of a CNF (cnf_plan.py)
         from . import train as _train

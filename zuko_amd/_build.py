@@ -42,6 +42,7 @@ SOURCES = {
     "backward_bern.hip": ["-ffp-contract=off"],
     "backward_bern_u.hip": ["-ffp-contract=off"],
     "mnn.hip": ["-ffp-contract=off"],
+    "mnn_backward.hip": ["-ffp-contract=off"],
     "umnn.hip": ["-ffp-contract=off"],
     "gmm.hip": ["-ffp-contract=off"],
     "cnf.hip": ["-ffp-contract=off"],

@@ -1,0 +1,544 @@
+// zuko_amd — adjoint of the monotone neural network of the neural autoregressive flow (NAF): the gradients of (y, ladj = log dy/dx) of
+// csrc/mnn.hip with respect to x, the signal and every weight and bias of the per-feature networks.
+//
+// Per element (n, column j of feature f), with A_l = |W_l[f]|, u = (x, s_1..s_S), a0x = A_0[:, 0], the forward is
+//     p_0 = A_0 u + b_0      pd_0 = a0x
+//     p_l = A_l v_{l-1} + b_l    pd_l = A_l t_{l-1}        v_l = act(p_l)    t_l = act'(p_l) * pd_l
+//     y = a_L . v_last + b_L     dy = a_L . t_last         ladj = log dy
+// and the reverse sweep for upstream (gy, gl), k = gl / dy:
+//     vb_last = gy a_L    tb_last = k a_L    g a_L += gy v_last + k t_last    g b_L += gy
+//     pb_l = vb_l act'(p_l) + tb_l act''(p_l) pd_l      pdb_l = tb_l act'(p_l)      g b_l += pb_l
+//     l >= 1:  g A_l += pb_l v_{l-1}^T + pdb_l t_{l-1}^T     vb_{l-1} = A_l^T pb_l     tb_{l-1} = A_l^T pdb_l
+//     l = 0:   g A_0 += pb_0 u^T,  g A_0[:, 0] += pdb_0      gx = a0x . pb_0           gsignal = A_0[:, 1:]^T pb_0
+//     g W_l = sign(W_l) g A_l
+//
+// Execution model (gfx950), the forward kernel's:
+//   * a wavefront owns 16 elements of ONE feature; the forward is recomputed, p_l and pd_l stay in registers (nothing was saved by the forward
+//     launch); lane (j, q) = (lane & 15, lane >> 4) holds units 16 o + 4 q + r of element j (the D fragment of v_mfma_f32_16x16x4_f32).
+//   * one feature's BACKWARD image sits in LDS: the forward image followed by the same weights in transposed tile order (zuko_amd/mnn_plan.py:
+//     layout_backward), so that A_l^T pb is the forward's product with the roles of `in` and `out` exchanged: one conflict-free 16-byte read per
+//     lane and tile, pb in the D layout is the B operand as it stands.
+//   * the weight gradients contract over the wave's 16 ELEMENTS: both operands are transposes of what the lanes hold.  A 16 x 16 fragment goes
+//     through 256 floats of per-wave LDS as M[element][unit] (one 16-byte write per lane, rows of 16 floats), and k-step s of either operand is
+//     M[64 s + lane]: consecutive addresses, no bank conflict.  Only the wave itself touches its scratch: s_waitcnt + wave_barrier, no
+//     workgroup barrier inside the row loop.
+//   * a block covers one column and one row chunk (zk_mnn_backward_geometry) and walks its row tiles with the gradient of every weight in
+//     accumulator registers; bias-like gradients are per-lane sums, added over the 16 element lanes once, at the end.  The block's four waves
+//     are then added in LDS in the order 0, 1, 2, 3 and ONE partial per (row chunk, column) is written.  No atomics.
+//   * mnn_bwd_reduce_kernel adds the partials in chunk order, applies sign(W) and scatters through the gradient table (the inverse of the
+//     partial's layout) into the flat parameter order; columns name distinct features, so every parameter has one writer.
+#include "zk_mnn_common.h"
+
+namespace zk {
+
+#define MNN_BWD_TM 4          // tiles per layer: widths <= 64
+#define MNN_BWD_SCRATCH 512   // floats of transpose scratch per wavefront
+#define MNN_BWD_BLOCKS 512    // the grid aims at this many blocks: two per CU
+#define MNN_WAVE_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
+
+// Offsets (floats) behind the forward image, and of one (row chunk, column) partial; the arithmetic of zuko_amd/mnn_plan.py: layout_backward.
+struct MnnBwdLayout {
+  int ts;       // 16-wide tiles of the signal = ceil(S / 16)
+  int o_wT[3];  // l = 1, 2: [T_{l-1}][T_l][256], lane (j, q), r of tile (i, o): |W_l[16 o + 4 q + r][16 i + j]|
+  int o_w0sT;   // [ts][T_0][256], tile (i, o): |W_0[16 o + 4 q + r][1 + 16 i + j]| (zero behind S)
+  int total;    // the backward image
+  int g_w0s, g_w0x, g_b0, g_w[3], g_b[3], g_wl, g_bl, g_total;
+};
+
+static inline bool mnn_bwd_layout(const MnnLayout& L, MnnBwdLayout* B) {
+  for (int l = 0; l < L.nh; ++l)
+    if (L.T[l] > MNN_BWD_TM) return false;
+  B->ts = (L.S + 15) / 16;
+  int o = L.total;
+  B->o_wT[0] = 0;
+  for (int l = 1; l < 3; ++l) {
+    B->o_wT[l] = o;
+    if (l < L.nh) o += L.T[l] * L.T[l - 1] * 256;
+  }
+  B->o_w0sT = o; o += B->ts * L.T[0] * 256;
+  B->total = o;
+  int g = 0;
+  B->g_w0s = g; g += L.T[0] * B->ts * 256;
+  B->g_w0x = g; g += L.T[0] * 16;
+  B->g_b0 = g; g += L.T[0] * 16;
+  B->g_w[0] = B->g_b[0] = 0;
+  for (int l = 1; l < 3; ++l) {
+    B->g_w[l] = g; if (l < L.nh) g += L.T[l] * L.T[l - 1] * 256;
+    B->g_b[l] = g; if (l < L.nh) g += L.T[l] * 16;
+  }
+  B->g_wl = g; g += L.T[L.nh - 1] * 16;
+  B->g_bl = g; g += 4;
+  B->g_total = g;
+  return true;
+}
+
+static inline int mnn_bwd_lds_floats(const MnnBwdLayout& B) { return (B.total > B.g_total ? B.total : B.g_total) + (MNN_THREADS / 64) * MNN_BWD_SCRATCH; }
+
+// rows per chunk (a multiple of 64) and the number of chunks: a pure function of the two sizes
+static inline int mnn_bwd_geometry(long long N, long long Dsel, int* rows_per_chunk, int* n_chunks) {
+  if (N < 1 || Dsel < 1 || Dsel > 65535 || N > (1LL << 40) || !rows_per_chunk || !n_chunks) return ZK_EINVAL;
+  long long want = MNN_BWD_BLOCKS / Dsel;
+  if (want < 1) want = 1;
+  const long long t64 = (N + 63) / 64;
+  if (want > t64) want = t64;
+  const long long rows = ((t64 + want - 1) / want) * 64;
+  if (rows > 0x7fffffc0LL) return ZK_EINVAL;
+  *rows_per_chunk = (int)rows;
+  *n_chunks = (int)((N + rows - 1) / rows);
+  return 0;
+}
+
+struct MnnBwdArgs {
+  const float* x;
+  const float* signal;
+  const float* image;
+  const int* feat;
+  const float* gy;
+  const float* gl;
+  float* gx;
+  float* gsignal;
+  float* work;
+  long long N, ldx, lds, ldgx, ldgs;
+  int Dsel, n_features, rows_per_chunk, gl_reduced, lds_main;
+  MnnLayout L;
+  MnnBwdLayout B;
+};
+
+typedef mnn_f4 (&bwd_tiles)[MNN_BWD_TM];
+typedef const mnn_f4 (&bwd_ctiles)[MNN_BWD_TM];
+
+__device__ __forceinline__ mnn_f4 bwd_zero() { return mnn_f4{0.f, 0.f, 0.f, 0.f}; }
+
+// v = act(p), t = act'(p) * pd for the T tiles of a layer (the two-way ELU of csrc/mnn.hip)
+__device__ __forceinline__ void bwd_act(bwd_ctiles p, bwd_ctiles pd, int T, int q, bwd_tiles v, bwd_tiles t) {
+  const int half = (T * 16 + 1) / 2;
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    if (o < T) {
+      mnn_for<4>([&](auto r) MNN_INLINE {
+        const bool first = o * 16 + q * 4 + r < half;
+        const float pr = p[o][(int)r];
+        const float s = first ? pr : -pr;
+        const float a = s > 0.f ? s : expm1f(s);
+        const float d = s > 0.f ? 1.f : expf(s);
+        v[o][(int)r] = first ? a : -a;
+        t[o][(int)r] = d * pd[o][(int)r];
+      });
+    }
+  });
+}
+
+// p = |W| v + b, pd = |W| t of one hidden-to-hidden layer (forward tile order)
+__device__ __forceinline__ void bwd_pre(const float* W, const float* Bias, int tin, int tout, int lane, int q, bwd_ctiles v, bwd_ctiles t, bwd_tiles p, bwd_tiles pd) {
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    if (o < tout) {
+      p[o] = *reinterpret_cast<const mnn_f4*>(Bias + o * 16 + q * 4);
+      pd[o] = bwd_zero();
+      mnn_for<MNN_BWD_TM>([&](auto it) MNN_INLINE {
+        if (it < tin) {
+          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(W + (o * tin + it) * 256 + lane * 4);
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            p[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], v[it][(int)r], p[o], 0, 0, 0);
+            pd[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], t[it][(int)r], pd[o], 0, 0, 0);
+          });
+        }
+      });
+    }
+  });
+}
+
+// pb = vb act'(p) + tb act''(p) pd, pdb = tb act'(p)
+__device__ __forceinline__ void bwd_local(bwd_ctiles p, bwd_ctiles pd, int T, int q, bwd_ctiles vb, bwd_ctiles tb, bwd_tiles pb, bwd_tiles pdb) {
+  const int half = (T * 16 + 1) / 2;
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    pb[o] = bwd_zero();
+    pdb[o] = bwd_zero();
+    if (o < T) {
+      mnn_for<4>([&](auto r) MNN_INLINE {
+        const bool first = o * 16 + q * 4 + r < half;
+        const float pr = p[o][(int)r];
+        const float s = first ? pr : -pr;
+        const float e = expf(s);
+        const float d1 = s > 0.f ? 1.f : e;
+        const float d2 = s > 0.f ? 0.f : (first ? e : -e);
+        pb[o][(int)r] = vb[o][(int)r] * d1 + tb[o][(int)r] * d2 * pd[o][(int)r];
+        pdb[o][(int)r] = tb[o][(int)r] * d1;
+      });
+    }
+  });
+}
+
+// A 16 x 16 fragment held as (element = j, units 4 q + r) becomes the four k-steps of a matrix operand that contracts over the elements:
+// out[s] = fragment[unit = lane & 15][element = 4 s + (lane >> 4)].
+__device__ __forceinline__ void bwd_transpose(float* scr, const mnn_f4& a, int lane, int j, int q, float (&out)[4]) {
+  MNN_WAVE_SYNC();  // the reads of the fragment before this one are done
+  *reinterpret_cast<mnn_f4*>(scr + j * 16 + q * 4) = a;
+  MNN_WAVE_SYNC();
+  mnn_for<4>([&](auto s) MNN_INLINE { out[s] = scr[s * 64 + lane]; });
+}
+
+// acc[o][i] += pb[o] v[i]^T + pdb[o] t[i]^T, contracted over the wave's 16 elements
+__device__ __forceinline__ void bwd_outer(float* scr, int lane, int j, int q, int tout, int tin, bwd_ctiles pb, bwd_ctiles pdb, bwd_ctiles v, bwd_ctiles t,
+                                          mnn_f4 (&acc)[MNN_BWD_TM][MNN_BWD_TM]) {
+  float PA[MNN_BWD_TM][4], PT[MNN_BWD_TM][4];
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    if (o < tout) {
+      bwd_transpose(scr, pb[o], lane, j, q, PA[o]);
+      bwd_transpose(scr + 256, pdb[o], lane, j, q, PT[o]);
+    }
+  });
+  mnn_for<MNN_BWD_TM>([&](auto i) MNN_INLINE {
+    if (i < tin) {
+      float VB[4], TB[4];
+      bwd_transpose(scr, v[i], lane, j, q, VB);
+      bwd_transpose(scr + 256, t[i], lane, j, q, TB);
+      mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+        if (o < tout) {
+          mnn_for<4>([&](auto s) MNN_INLINE {
+            acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(PA[o][s], VB[s], acc[o][i], 0, 0, 0);
+            acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(PT[o][s], TB[s], acc[o][i], 0, 0, 0);
+          });
+        }
+      });
+    }
+  });
+}
+
+// vb = A^T pb, tb = A^T pdb through the transposed tiles WT [tin][tout][256] (tin: the tiles of the layer below, the product's rows)
+__device__ __forceinline__ void bwd_down(const float* WT, int tin, int tout, int lane, bwd_ctiles pb, bwd_ctiles pdb, bwd_tiles vb, bwd_tiles tb) {
+  mnn_for<MNN_BWD_TM>([&](auto i) MNN_INLINE {
+    vb[i] = bwd_zero();
+    tb[i] = bwd_zero();
+    if (i < tin) {
+      mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+        if (o < tout) {
+          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(WT + (i * tout + o) * 256 + lane * 4);
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            vb[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], pb[o][(int)r], vb[i], 0, 0, 0);
+            tb[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], pdb[o][(int)r], tb[i], 0, 0, 0);
+          });
+        }
+      });
+    }
+  });
+}
+
+__device__ __forceinline__ void bwd_add(bwd_tiles acc, bwd_ctiles v, int T) {
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    if (o < T) acc[o] += v[o];
+  });
+}
+
+// sum over the 16 lanes that share q: the same value in all of them, the same order everywhere
+__device__ __forceinline__ float bwd_sum_j(float p) {
+  p += __shfl_xor(p, 1, 64);
+  p += __shfl_xor(p, 2, 64);
+  p += __shfl_xor(p, 4, 64);
+  p += __shfl_xor(p, 8, 64);
+  return p;
+}
+
+// the wave's share of a bias-like gradient (per-lane sums over the rows of element lane j) into the block's partial
+__device__ __forceinline__ void bwd_put_units(float* G, bwd_ctiles acc, int T, int j, int q, bool set) {
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    if (o < T) {
+      mnn_f4 s;
+      mnn_for<4>([&](auto r) MNN_INLINE { s[(int)r] = bwd_sum_j(acc[o][(int)r]); });
+      if (j == 0) {
+        mnn_f4* dst = reinterpret_cast<mnn_f4*>(G + o * 16 + q * 4);
+        *dst = set ? s : *dst + s;
+      }
+    }
+  });
+}
+
+template <int TI> __device__ __forceinline__ void bwd_put_tiles(float* G, const mnn_f4 (&acc)[MNN_BWD_TM][TI], int tout, int tin, int lane, bool set) {
+  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
+    mnn_for<TI>([&](auto i) MNN_INLINE {
+      if (o < tout && i < tin) {
+        mnn_f4* dst = reinterpret_cast<mnn_f4*>(G + (o * tin + i) * 256 + lane * 4);
+        *dst = set ? acc[o][i] : *dst + acc[o][i];
+      }
+    });
+  });
+}
+
+extern __shared__ __attribute__((aligned(16))) float mnn_bwd_lds[];
+
+template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_bwd_kernel(MnnBwdArgs a) {
+  constexpr int TM = MNN_BWD_TM;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
+  const MnnLayout& L = a.L;
+  const MnnBwdLayout& B = a.B;
+  const int col = blockIdx.y;
+  int f = a.feat ? a.feat[col] : col;
+  f = f < 0 ? 0 : (f >= a.n_features ? a.n_features - 1 : f);  // (a memory guard only: the caller checks the range)
+  const float* img = a.image + (size_t)f * B.total;
+  float* const lds = mnn_bwd_lds;
+  float* const scr = mnn_bwd_lds + a.lds_main + wave * MNN_BWD_SCRATCH;
+  for (int i = tid * 4; i < B.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(lds + i) = *reinterpret_cast<const mnn_f4*>(img + i);
+  __syncthreads();
+
+  const int T0 = L.T[0], T1 = L.T[1], T2 = L.T[2], TL = L.T[NH - 1];
+  mnn_f4 aW0[TM][TS], aW1[TM][TM], aW2[TM][TM], aX[TM], aB0[TM], aB1[TM], aB2[TM], aWl[TM];
+  float aBl = 0.f;
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    mnn_for<TS>([&](auto i) MNN_INLINE { aW0[o][i] = bwd_zero(); });
+    mnn_for<TM>([&](auto i) MNN_INLINE { aW1[o][i] = bwd_zero(); aW2[o][i] = bwd_zero(); });
+    aX[o] = aB0[o] = aB1[o] = aB2[o] = aWl[o] = bwd_zero();
+  });
+
+  const long long r0 = (long long)blockIdx.x * a.rows_per_chunk;
+  const long long r1 = r0 + a.rows_per_chunk < a.N ? r0 + a.rows_per_chunk : a.N;
+  for (long long t0 = r0 + wave * 16; t0 < r1; t0 += (MNN_THREADS / 64) * 16) {
+    const long long row = t0 + j;
+    const bool valid = row < r1;
+    const long long rc = valid ? row : a.N - 1;  // rows behind the end compute on the last row with zero upstream gradients and store nothing
+    const float xin = a.x[rc * a.ldx + col];
+    const float gyv = (valid && a.gy) ? a.gy[row * a.Dsel + col] : 0.f;
+    const float glv = (valid && a.gl) ? (a.gl_reduced ? a.gl[row] : a.gl[row * a.Dsel + col]) : 0.f;
+
+    // ---- the forward, keeping the pre-activations p_l and their tangents pd_l
+    mnn_f4 p0[TM], p1[TM], p2[TM], pd1[TM], pd2[TM], w0x[TM], v[TM], t[TM];
+    mnn_signal<TM>(L, lds, a.signal + rc * a.lds + (size_t)col * L.S, lane, q, p0);
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      p1[o] = p2[o] = pd1[o] = pd2[o] = bwd_zero();
+      if (o < T0) {
+        w0x[o] = *reinterpret_cast<const mnn_f4*>(lds + L.o_w0x + o * 16 + q * 4);
+        mnn_for<4>([&](auto r) MNN_INLINE { p0[o][(int)r] = fmaf(w0x[o][(int)r], xin, p0[o][(int)r]); });
+      } else {
+        p0[o] = w0x[o] = bwd_zero();
+      }
+    });
+    bwd_act(p0, w0x, T0, q, v, t);
+    if constexpr (NH > 1) {
+      bwd_pre(lds + L.o_w[1], lds + L.o_b[1], T0, T1, lane, q, v, t, p1, pd1);
+      bwd_act(p1, pd1, T1, q, v, t);
+    }
+    if constexpr (NH > 2) {
+      bwd_pre(lds + L.o_w[2], lds + L.o_b[2], T1, T2, lane, q, v, t, p2, pd2);
+      bwd_act(p2, pd2, T2, q, v, t);
+    }
+
+    // ---- the last layer
+    mnn_f4 vb[TM], tb[TM], pb[TM], pdb[TM];
+    {
+      mnn_f4 wl[TM];
+      float pdy = 0.f;
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        wl[o] = bwd_zero();
+        if (o < TL) {
+          wl[o] = *reinterpret_cast<const mnn_f4*>(lds + L.o_wl + o * 16 + q * 4);
+          mnn_for<4>([&](auto r) MNN_INLINE { pdy = fmaf(wl[o][(int)r], t[o][(int)r], pdy); });
+        }
+      });
+      const float dy = mnn_sum_q(pdy);
+      const float k = glv / dy;
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        vb[o] = tb[o] = bwd_zero();
+        if (o < TL) {
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            vb[o][(int)r] = gyv * wl[o][(int)r];
+            tb[o][(int)r] = k * wl[o][(int)r];
+            aWl[o][(int)r] += gyv * v[o][(int)r] + k * t[o][(int)r];
+          });
+        }
+      });
+      if (q == 0) aBl += gyv;
+    }
+
+    // ---- the reverse sweep
+    if constexpr (NH > 2) {
+      bwd_local(p2, pd2, T2, q, vb, tb, pb, pdb);
+      bwd_add(aB2, pb, T2);
+      bwd_act(p1, pd1, T1, q, v, t);
+      bwd_outer(scr, lane, j, q, T2, T1, pb, pdb, v, t, aW2);
+      bwd_down(lds + B.o_wT[2], T1, T2, lane, pb, pdb, vb, tb);
+    }
+    if constexpr (NH > 1) {
+      bwd_local(p1, pd1, T1, q, vb, tb, pb, pdb);
+      bwd_add(aB1, pb, T1);
+      bwd_act(p0, w0x, T0, q, v, t);
+      bwd_outer(scr, lane, j, q, T1, T0, pb, pdb, v, t, aW1);
+      bwd_down(lds + B.o_wT[1], T0, T1, lane, pb, pdb, vb, tb);
+    }
+    bwd_local(p0, w0x, T0, q, vb, tb, pb, pdb);
+    bwd_add(aB0, pb, T0);
+    {
+      float sx = 0.f;
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        if (o < T0) {
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            aX[o][(int)r] += pb[o][(int)r] * xin + pdb[o][(int)r];
+            sx = fmaf(w0x[o][(int)r], pb[o][(int)r], sx);
+          });
+        }
+      });
+      sx = mnn_sum_q(sx);
+      if (a.gx && q == 0 && valid) a.gx[row * a.ldgx + col] = sx;
+    }
+    if (a.work) {  // g A_0[:, 1:] += pb_0 signal^T: the signal of element 4 s + q, feature 16 i + j, read in the operand's own layout
+      float PA[TM][4];
+      mnn_for<TM>([&](auto o) MNN_INLINE {
+        if (o < T0) bwd_transpose(scr, pb[o], lane, j, q, PA[o]);
+      });
+      mnn_for<TS>([&](auto i) MNN_INLINE {
+        if (i < B.ts) {
+          const int sidx = i * 16 + j;
+          mnn_for<4>([&](auto s) MNN_INLINE {
+            const long long er = t0 + s * 4 + q;
+            const long long ec = er < a.N ? er : a.N - 1;
+            const float b = sidx < L.S ? a.signal[ec * a.lds + (size_t)col * L.S + sidx] : 0.f;
+            mnn_for<TM>([&](auto o) MNN_INLINE {
+              if (o < T0) aW0[o][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(PA[o][s], b, aW0[o][i], 0, 0, 0);
+            });
+          });
+        }
+      });
+    }
+    if (a.gsignal) {
+      mnn_for<TS>([&](auto i) MNN_INLINE {
+        if (i < B.ts) {
+          mnn_f4 gs = bwd_zero();
+          mnn_for<TM>([&](auto o) MNN_INLINE {
+            if (o < T0) {
+              const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(lds + B.o_w0sT + (i * T0 + o) * 256 + lane * 4);
+              mnn_for<4>([&](auto r) MNN_INLINE { gs = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], pb[o][(int)r], gs, 0, 0, 0); });
+            }
+          });
+          if (valid) {
+            float* dst = a.gsignal + row * a.ldgs + (size_t)col * L.S;
+            mnn_for<4>([&](auto r) MNN_INLINE {
+              const int sidx = i * 16 + q * 4 + r;
+              if (sidx < L.S) dst[sidx] = gs[(int)r];
+            });
+          }
+        }
+      });
+    }
+  }
+  if (!a.work) return;  // (uniform over the grid: nobody asked for parameter gradients)
+
+  // ---- the block's four waves, added in the order 0, 1, 2, 3 over the LDS the image occupied
+  float* const G = lds;
+  for (int w = 0; w < MNN_THREADS / 64; ++w) {
+    __syncthreads();
+    if (wave == w) {
+      const bool set = w == 0;
+      bwd_put_tiles<TS>(G + B.g_w0s, aW0, T0, B.ts, lane, set);
+      bwd_put_units(G + B.g_w0x, aX, T0, j, q, set);
+      bwd_put_units(G + B.g_b0, aB0, T0, j, q, set);
+      if constexpr (NH > 1) {
+        bwd_put_tiles<TM>(G + B.g_w[1], aW1, T1, T0, lane, set);
+        bwd_put_units(G + B.g_b[1], aB1, T1, j, q, set);
+      }
+      if constexpr (NH > 2) {
+        bwd_put_tiles<TM>(G + B.g_w[2], aW2, T2, T1, lane, set);
+        bwd_put_units(G + B.g_b[2], aB2, T2, j, q, set);
+      }
+      bwd_put_units(G + B.g_wl, aWl, TL, j, q, set);
+      const float sb = bwd_sum_j(aBl);
+      if (lane == 0) {
+        if (set) {
+          G[B.g_bl] = sb; G[B.g_bl + 1] = 0.f; G[B.g_bl + 2] = 0.f; G[B.g_bl + 3] = 0.f;
+        } else {
+          G[B.g_bl] += sb;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  float* out = a.work + ((size_t)blockIdx.x * a.Dsel + col) * B.g_total;
+  for (int i = tid * 4; i < B.g_total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(out + i) = *reinterpret_cast<const mnn_f4*>(G + i);
+}
+
+// gparams[table[f][pos]] = sign(W) * the partials of (column, pos) added in chunk order
+__global__ __launch_bounds__(256) void mnn_bwd_reduce_kernel(const float* __restrict__ work, const int* __restrict__ table, const int* __restrict__ feat,
+                                                             const float* __restrict__ params, float* __restrict__ gparams, int chunks, int Dsel, int g_total,
+                                                             int n_features, long long flat_weights, long long flat_total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)Dsel * g_total) return;
+  const int col = (int)(idx / g_total), pos = (int)(idx % g_total);
+  int f = feat ? feat[col] : col;
+  if (f < 0 || f >= n_features) return;
+  const long long dst = table[(size_t)f * g_total + pos];
+  if (dst < 0 || dst >= flat_total) return;
+  float s = 0.f;
+  for (int c = 0; c < chunks; ++c) s += work[((size_t)c * Dsel + col) * g_total + pos];
+  if (dst < flat_weights) {
+    const float w = params[dst];
+    s = w > 0.f ? s : (w < 0.f ? -s : 0.f);
+  }
+  gparams[dst] = s;
+}
+
+static bool mnn_bwd_shape(int S, int nh, int w0, int w1, int w2, MnnLayout* L, MnnBwdLayout* B) {
+  const int widths[3] = {w0, w1, w2};
+  if (!mnn_layout(S, nh, widths, L)) return false;
+  if (!mnn_bwd_layout(*L, B)) return false;
+  return mnn_bwd_lds_floats(*B) * 4 <= MNN_LDS_MAX;
+}
+
+template <int NH> static const void* mnn_bwd_fn(int ts) {
+  if (ts <= 1) return (const void*)mnn_bwd_kernel<NH, 1>;
+  if (ts <= 2) return (const void*)mnn_bwd_kernel<NH, 2>;
+  return (const void*)mnn_bwd_kernel<NH, 4>;
+}
+
+static int mnn_backward(const zk_mnn_bwd_args_v1* p, void* stream) {
+  if (!p || p->struct_size != sizeof(zk_mnn_bwd_args_v1) || p->version != 1) return ZK_EINVAL;
+  MnnBwdArgs a;
+  if (!mnn_bwd_shape(p->S, p->n_hidden, p->width0, p->width1, p->width2, &a.L, &a.B)) return ZK_EINVAL;
+  if (p->image_floats != a.B.total || p->grad_floats != a.B.g_total || p->n_features < 1 || p->N < 0 || p->Dsel < 1 || p->Dsel > 65535) return ZK_EINVAL;
+  if (p->ldx < 1 || p->ld_signal < p->Dsel * (int64_t)p->S) return ZK_EINVAL;
+  if (p->gx && p->ld_gx < p->Dsel) return ZK_EINVAL;
+  if (p->gsignal && p->ld_gsignal < p->Dsel * (int64_t)p->S) return ZK_EINVAL;
+  if (p->gparams && (p->flat_total < 1 || p->flat_weights < 0 || p->flat_weights > p->flat_total)) return ZK_EINVAL;
+  if (p->gparams && p->N > 0 && (!p->params || !p->grad_table || !p->work)) return ZK_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (p->N == 0) {
+    if (p->gparams && hipMemsetAsync(p->gparams, 0, (size_t)p->flat_total * 4, st) != hipSuccess) return ZK_LAUNCH_CHECK();
+    return 0;
+  }
+  if (!p->x || !p->signal || !p->image) return ZK_EINVAL;
+  int chunks = 0;
+  if (mnn_bwd_geometry(p->N, p->Dsel, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
+  a.x = (const float*)p->x; a.signal = (const float*)p->signal; a.image = (const float*)p->image; a.feat = (const int*)p->feat;
+  a.gy = (const float*)p->gy; a.gl = (const float*)p->gl; a.gx = (float*)p->gx; a.gsignal = (float*)p->gsignal;
+  a.work = p->gparams ? (float*)p->work : nullptr;
+  a.N = p->N; a.ldx = p->ldx; a.lds = p->ld_signal; a.ldgx = p->ld_gx; a.ldgs = p->ld_gsignal;
+  a.Dsel = (int)p->Dsel; a.n_features = p->n_features; a.gl_reduced = p->gl_reduced;
+  a.lds_main = a.B.total > a.B.g_total ? a.B.total : a.B.g_total;
+  if (p->gparams && hipMemsetAsync(p->gparams, 0, (size_t)p->flat_total * 4, st) != hipSuccess) return ZK_LAUNCH_CHECK();
+  if (!a.gx && !a.gsignal && !a.work) return 0;
+  const void* fn = a.L.nh == 1 ? mnn_bwd_fn<1>(a.B.ts) : (a.L.nh == 2 ? mnn_bwd_fn<2>(a.B.ts) : mnn_bwd_fn<3>(a.B.ts));
+  const int rc = mnn_launch_dyn_lds(fn, dim3((unsigned)chunks, (unsigned)a.Dsel), mnn_bwd_lds_floats(a.B) * 4, &a, st);
+  if (rc != 0 || !a.work) return rc;
+  const long long n = (long long)a.Dsel * a.B.g_total;
+  hipLaunchKernelGGL(mnn_bwd_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)a.work, (const int*)p->grad_table, a.feat,
+                     (const float*)p->params, (float*)p->gparams, chunks, a.Dsel, a.B.g_total, a.n_features, (long long)p->flat_weights, (long long)p->flat_total);
+  return ZK_LAUNCH_CHECK();
+}
+
+}  // namespace zk
+
+extern "C" int zk_mnn_backward(const zk_mnn_bwd_args_v1* args, void* stream) { return zk::mnn_backward(args, stream); }
+extern "C" int zk_mnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks) { return zk::mnn_bwd_geometry(N, Dsel, rows_per_chunk, n_chunks); }
+extern "C" int zk_mnn_backward_floats(int S, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats) {
+  zk::MnnLayout L;
+  zk::MnnBwdLayout B;
+  if (!image_floats || !grad_floats || !zk::mnn_bwd_shape(S, n_hidden, width0, width1, width2, &L, &B)) return ZK_EINVAL;
+  *image_floats = B.total;
+  *grad_floats = B.g_total;
+  return 0;
+}
+extern "C" int zk_mnn_backward_workspace_floats(int64_t N, int64_t Dsel, int S, int n_hidden, int width0, int width1, int width2, int64_t* floats) {
+  zk::MnnLayout L;
+  zk::MnnBwdLayout B;
+  if (!floats || !zk::mnn_bwd_shape(S, n_hidden, width0, width1, width2, &L, &B)) return ZK_EINVAL;
+  *floats = 0;
+  if (N == 0 && Dsel >= 1 && Dsel <= 65535) return 0;
+  int rows = 0, chunks = 0;
+  if (zk::mnn_bwd_geometry(N, Dsel, &rows, &chunks) != 0) return ZK_EINVAL;
+  *floats = (int64_t)chunks * Dsel * B.g_total;
+  return 0;
+}

@@ -3,8 +3,8 @@ shape bookkeeping only; every arithmetic result comes out of a HIP kernel in lib
 
 All functions require tensors on a HIP device (`tensor.is_cuda`) in float32 or float64 and raise
 otherwise — there is no CPU or eager-PyTorch fallback.  One documented exception: the monotone networks of a neural autoregressive
-flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shapes their kernel does not serve, for float64 and for
-calls that need gradients (no adjoint kernel yet).  Likewise the Gaussian mixture density (gmm_log_prob) runs the reference's expressions as torch ops
+flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shapes their kernels do not serve, for float64, for the gradient of the
+bisection inverse and, under autograd, for layers wider than 64 (the adjoint kernel's envelope: mnn_backward_supported).  Likewise the Gaussian mixture density (gmm_log_prob) runs the reference's expressions as torch ops
 ON THE DEVICE outside its kernels' envelope (features or components above 64, sample dimensions broadcast over a batch of mixtures).  And the
 continuous flow (cnf_integrate) hands every call its step kernel does not serve — gradients, float64, Hutchinson's estimator, other activations or
 shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.  The Gaussianization map (gauss_forward / gauss_inverse) runs the
@@ -520,6 +520,7 @@ def sum_f64(v: Tensor, scale: float = 1.0) -> Tensor:
 MNN_BOUND = 10.0
 MNN_EPS = 1e-6
 MNN_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_naf.py measures the kernels against it)
+MNN_ADJOINT = True  # False: calls that need gradients take the torch-op path (double backward through ATen), as before zk_mnn_backward existed
 
 
 def mnn_supported(S: int, widths) -> bool:
@@ -528,6 +529,14 @@ def mnn_supported(S: int, widths) -> bool:
     from . import mnn_plan
 
     return mnn_plan.supported(int(S), tuple(widths))
+
+
+def mnn_backward_supported(S: int, widths) -> bool:
+    """True when zk_mnn_backward serves per-feature networks (1 + S) -> widths -> 1: the shapes of mnn_supported whose widths are all <= 64
+    (zuko_amd/mnn_plan.py: layout_backward).  Wider layers keep the torch-op path under autograd."""
+    from . import mnn_plan
+
+    return mnn_plan.layout_backward(int(S), tuple(widths)) is not None
 
 
 def _mnn_feat(network, feat, device):
@@ -557,9 +566,17 @@ def _mnn_feat(network, feat, device):
         host = feat.detach().cpu()
         if host.numel() and not (0 <= int(host.min()) and int(host.max()) < stack):
             raise IndexError(f"zuko_amd: monotone network: feature indices outside a stack of {stack} networks")
-        entry = (feat, feat._version, host.to(device=device, dtype=torch.int32).contiguous())
+        entry = (feat, feat._version, host.to(device=device, dtype=torch.int32).contiguous(), int(host.unique().numel()) == host.numel())
         cache[key] = entry
     return entry[2]
+
+
+def _mnn_feat_distinct(network, feat, device) -> bool:
+    """Does every feature appear at most once in `feat`?  (The adjoint kernel gives every parameter one writer.)  Answered from _mnn_feat's cache."""
+    if feat is None or isinstance(feat, tuple):
+        return True
+    _mnn_feat(network, feat, device)
+    return network.__dict__["_mnn_feat_cache"][(str(device), id(feat))][3]
 
 
 def _mnn_torch_f(network, x: Tensor, signal: Tensor, feat, signed: bool = False) -> Tensor:
@@ -629,12 +646,127 @@ def _mnn_check(network, x: Tensor, signal: Tensor, feat) -> None:
         raise ValueError(f"zuko_amd: monotone network: {n_sel} columns do not match the feature selection of a stack of {stack} networks")
 
 
+def _mnn_launch_forward(img, network, x2: Tensor, s2: Tensor, feat, reduce: bool):
+    N, D = x2.shape
+    data = img.refresh(network)
+    y = torch.empty((N, D), dtype=torch.float32, device=x2.device)
+    ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x2.device)
+    work = torch.empty((N, D), dtype=torch.float32, device=x2.device) if reduce else None
+    a = _mnn_args(img, x2, s2, _mnn_feat(network, feat, x2.device), y, ladj=ladj.data_ptr(), work=None if work is None else work.data_ptr(), ladj_reduced=int(reduce))
+    _C.check(_C.lib().zk_mnn_forward(a, _stream()), "zk_mnn_forward")
+    del data
+    return y, ladj
+
+
+def mnn_backward_launch(bimg, network, x2: Tensor, s2: Tensor, feat, gy, gl, flat, need_x: bool = True, need_signal: bool = True, need_params: bool = True):
+    """zk_mnn_backward on prepared operands: x2 [N, D] and s2 [N, D S] (unit inner stride), gy [N, D] or None, gl [N, D] / [N] or None, `flat` the
+    signed flat parameters (mnn_plan.flat_parameters order).  Returns (gx, gsignal, gparams), None where not asked for.  Launches on the current
+    stream; nothing synchronises."""
+    N, D = x2.shape
+    lay, B = bimg.layout, bimg.backward
+    dev = x2.device
+    data = bimg.refresh(network)
+    gx = torch.empty((N, D), dtype=torch.float32, device=dev) if need_x else None
+    gs = torch.empty((N, D * lay.S), dtype=torch.float32, device=dev) if need_signal else None
+    gp = torch.empty(bimg.flat_total, dtype=torch.float32, device=dev) if need_params else None
+    work = None
+    if need_params and N > 0:
+        import ctypes
+
+        rows, chunks = ctypes.c_int(0), ctypes.c_int(0)
+        _C.check(_C.lib().zk_mnn_backward_geometry(N, D, ctypes.byref(rows), ctypes.byref(chunks)), "zk_mnn_backward_geometry")
+        work = torch.empty(chunks.value * D * B.g_total, dtype=torch.float32, device=dev)
+    w = list(lay.widths) + [0, 0]
+    ft = _mnn_feat(network, feat, dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = _C.args("zk_mnn_bwd_args_v1", S=lay.S, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], n_features=bimg.features, image_floats=B.total,
+                grad_floats=B.g_total, gl_reduced=int(gl is not None and gl.dim() == 1), N=N, Dsel=D, ldx=x2.stride(0) if N > 1 else D,
+                ld_signal=s2.stride(0) if N > 1 else D * lay.S, ld_gx=D, ld_gsignal=D * lay.S, flat_total=bimg.flat_total, flat_weights=bimg.flat_weights,
+                x=x2.data_ptr(), signal=s2.data_ptr(), image=data.data_ptr(), feat=ptr(ft), gy=ptr(gy), gl=ptr(gl), params=ptr(flat) if need_params else None,
+                grad_table=bimg.table.data_ptr() if need_params else None, gx=ptr(gx), gsignal=ptr(gs), gparams=ptr(gp), work=ptr(work))
+    _C.check(_C.lib().zk_mnn_backward(a, _stream()), "zk_mnn_backward")
+    del data
+    return gx, gs, gp
+
+
+class MnnForwardFn(torch.autograd.Function):
+    """(y, ladj) of the monotone networks under autograd: zk_mnn_forward forward, ONE zk_mnn_backward call backward (the adjoint kernel and the
+    chunk reduction), which recomputes the forward from x and the signal: nothing else is saved."""
+
+    @staticmethod
+    def forward(ctx, network, feat, reduce, n_lin, x2, s2, *params):
+        from . import mnn_plan
+
+        ctx.network, ctx.feat, ctx.n_lin = network, feat, n_lin
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x2, s2, *params)
+        return _mnn_launch_forward(mnn_plan.image_of(network, x2.device), network, x2.detach(), s2.detach(), feat, reduce)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # raw-pointer HIP kernels on detached data: double backward (create_graph=True) must raise
+    def backward(ctx, gy, gl):
+        from . import mnn_plan
+
+        x2, s2, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_p = any(need[6:])
+        none = (None, None, None, None)
+        if gy is None and gl is None:
+            return none + (None,) * (2 + len(params))
+        bimg = mnn_plan.backward_image_of(ctx.network, x2.device)
+        flat = torch.cat([p.detach().reshape(-1) for p in params]) if need_p else None
+        gx, gs, gp = mnn_backward_launch(bimg, ctx.network, x2, s2, ctx.feat, None if gy is None else gy.contiguous(), None if gl is None else gl.contiguous(), flat,
+                                         need_x=need[4], need_signal=need[5], need_params=need_p)
+        gparams = [None] * len(params)
+        if need_p:
+            o = 0
+            for i, p in enumerate(params):
+                gparams[i] = gp[o : o + p.numel()].view(p.shape) if need[6 + i] else None
+                o += p.numel()
+        return none + (gx, gs, *gparams)
+
+
+def _mnn_adjoint_serves(network, x: Tensor, signal: Tensor, feat):
+    """The dtype the adjoint path runs this call from (float32, or bfloat16 trained on float32 copies as _bf16_trains_in_f32 arranges it), or
+    None: switches off, another dtype, a shape outside mnn_backward_supported, or a feature named twice."""
+    from . import mnn_plan
+
+    if not (MNN_KERNEL and MNN_ADJOINT):
+        return None
+    params = list(network.parameters())
+    dt = x.dtype
+    if dt not in (torch.float32, torch.bfloat16) or signal.dtype != dt or any(p.dtype != dt for p in params):
+        return None
+    if mnn_plan.backward_image_of(network, x.device) is None or not _mnn_feat_distinct(network, feat, x.device):
+        return None
+    return dt
+
+
+def _mnn_forward_adjoint(x: Tensor, signal: Tensor, network, feat, reduce: bool, dt):
+    from . import mnn_plan
+
+    lins = mnn_plan._linears(network)
+    params = [l.weight for l in lins] + [l.bias for l in lins]  # (the order of mnn_plan.flat_parameters)
+    if dt == torch.bfloat16:
+        x, signal, params = x.float(), signal.float(), [p.float() for p in params]
+    shape, x2, s2 = _mnn_prepare(x, signal)  # (differentiable views: broadcast gradients are summed by autograd)
+    y, ladj = MnnForwardFn.apply(network, feat, reduce, len(lins), x2, s2, *params)
+    lshape = shape[:-1] if reduce else shape
+    y = y if y.shape == shape else y.reshape(shape)  # (two-dimensional calls hand out the node's own outputs)
+    return (y.to(dt) if dt != torch.float32 else y), (ladj if ladj.shape == lshape else ladj.reshape(lshape))
+
+
 def mnn_forward(x: Tensor, signal: Tensor, network, feat=None, reduce: bool = False):
     """(y, ladj) of the per-feature monotone networks `network` (a stacked zuko_amd.nn.MonotonicMLP(1 + S, 1, ...)): x [..., D], signal
     [..., D, S]; column j uses the network of feature feat[j] (`feat`: None, a (lo, hi) run or an index tensor).  zk_mnn_forward when it
-    serves the call; otherwise (unsupported shape, float64, gradients) the reference's torch ops with torch.autograd.grad for the
-    derivative (zuko/transforms.py:623-637)."""
+    serves the call, under autograd with zk_mnn_backward as its adjoint (MnnForwardFn: float32 and bfloat16, shapes of
+    mnn_backward_supported); otherwise (unsupported shape, float64, MNN_ADJOINT = False) the reference's torch ops with torch.autograd.grad
+    for the derivative (zuko/transforms.py:623-637), which can be differentiated twice."""
     _mnn_check(network, x, signal, feat)
+    if torch.is_grad_enabled() and (x.requires_grad or signal.requires_grad or any(p.requires_grad for p in network.parameters())):
+        dt = _mnn_adjoint_serves(network, x, signal, feat)
+        if dt is not None:
+            return _mnn_forward_adjoint(x, signal, network, feat, reduce, dt)
     img = _mnn_kernel_serves(network, x, signal)
     if img is None:
         create_graph = torch.is_grad_enabled() and (x.requires_grad or signal.requires_grad or any(p.requires_grad for p in network.parameters()))
@@ -647,14 +779,7 @@ def mnn_forward(x: Tensor, signal: Tensor, network, feat=None, reduce: bool = Fa
         ladj = jac.log()
         return y, (ladj.sum(dim=-1) if reduce else ladj)
     shape, x2, s2 = _mnn_prepare(x, signal)
-    N, D = x2.shape
-    data = img.refresh(network)
-    y = torch.empty((N, D), dtype=torch.float32, device=x.device)
-    ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x.device)
-    work = torch.empty((N, D), dtype=torch.float32, device=x.device) if reduce else None
-    a = _mnn_args(img, x2, s2, _mnn_feat(network, feat, x.device), y, ladj=ladj.data_ptr(), work=None if work is None else work.data_ptr(), ladj_reduced=int(reduce))
-    _C.check(_C.lib().zk_mnn_forward(a, _stream()), "zk_mnn_forward")
-    del data
+    y, ladj = _mnn_launch_forward(img, network, x2, s2, feat, reduce)
     return y.reshape(shape), ladj.reshape(shape[:-1] if reduce else shape)
 
 

@@ -235,8 +235,9 @@ class MonotonicNetworkTransform(_Univariate):
     zuko/transforms.py:570-637): value and log-derivative in one launch (zk_mnn_forward; the derivative in forward mode instead of
     torch.autograd.grad), the inverse by the reference's bisection on [-bound, bound] to `eps` (zk_mnn_inverse).  `features`: the
     networks the columns of x belong to — None (all, in order), a (lo, hi) run or an index tensor; the ordered inverse of an
-    autoregressive layer evaluates one sweep's features at a time.  Unsupported network shapes, float64 and calls that need
-    gradients run the same expressions as torch ops (zuko_amd/ops.py: mnn_forward)."""
+    autoregressive layer evaluates one sweep's features at a time.  Under autograd the forward launch sits in an autograd node whose backward is
+    zk_mnn_backward (widths <= 64).  Unsupported network shapes, float64 and the gradient of the inverse run the same expressions as torch ops
+    (zuko_amd/ops.py: mnn_forward, mnn_inverse)."""
 
     def __init__(self, signal: Tensor, network, features=None, bound: float = 10.0, eps: float = 1e-6, **kwargs) -> None:
         super().__init__(**kwargs)
