@@ -786,6 +786,61 @@ int zk_umnn_inverse(const zk_umnn_args_v1* args, void* stream);
 /* The launch geometry of zk_umnn_forward / zk_umnn_inverse: the rule, arguments and return values of zk_mnn_launch_geometry (one function behind both). */
 int zk_umnn_launch_geometry(int64_t N, int64_t Dsel, int* rows_per_block, int* feats_per_block);
 
+/* ---- adjoint of the unconstrained monotone neural network (UNAF training; fp32) ------------------------------------------------------------
+ * zk_umnn_backward: the gradients of zk_umnn_forward's (y, ladj) with respect to x, the signal and every weight and bias of the integrand
+ * networks, for upstream gy and gl (the constant's gradient is gy itself: the caller's).  With hb the upstream gradient of h at a point,
+ *     node i: hb = gy x w_i g(t_i x) sq'(h_i)      the point x: hb = gl sq'(h(x))      sq'(h) = 1 / (1 + |h| / 7)^2
+ * every point is one reverse sweep of the network, and gx = gy g(x) + W0[:, 0] . pb_0(x): the integrand at the upper limit, as GaussLegendre.backward
+ * (zuko/utils.py:282-326) has it; the nodes t_i x carry no gradient to x.  The sums over the points run in the order i = 0, 1, ..., then x.  The
+ * execution model, `image` (here of the SIGNED weights), `gy`, `gl`, `gx`, `gsignal`, `gparams`, `grad_table`, `work`, the limits, the geometry and
+ * the determinism are those of zk_mnn_backward; the chunk reduction applies no sign(W), and `params` is not read.
+ *
+ *   signal    read in place as by zk_umnn_forward: element (n, j) at signal + n * ld_signal + j * ld_col, ld_col >= S
+ *   gsignal   [N, Dsel * S] with row stride ld_gsignal (packed columns, whatever ld_col is)
+ *   quad      DEVICE float [2 * n_quad]: the nodes, then the weights; 1 <= n_quad <= 64 */
+typedef struct zk_umnn_bwd_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_umnn_bwd_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t S;
+  int32_t n_hidden;
+  int32_t width0;
+  int32_t width1;
+  int32_t width2;
+  int32_t n_features;
+  int32_t image_floats;    /* floats per backward image (zk_umnn_backward_floats) */
+  int32_t grad_floats;     /* floats per partial (zk_umnn_backward_floats) */
+  int32_t gl_reduced;      /* != 0: gl is [N] */
+  int32_t n_quad;          /* quadrature points */
+  int64_t N;
+  int64_t Dsel;
+  int64_t ldx;
+  int64_t ld_signal;
+  int64_t ld_col;
+  int64_t ld_gx;
+  int64_t ld_gsignal;
+  int64_t flat_total;
+  int64_t flat_weights;
+  const void* x;
+  const void* signal;
+  const void* image;
+  const void* quad;
+  const int32_t* feat;       /* or NULL */
+  const void* gy;            /* or NULL */
+  const void* gl;            /* or NULL */
+  const void* params;        /* not read (the weights are signed); kept for the layout of zk_mnn_bwd_args_v1 */
+  const int32_t* grad_table; /* with gparams */
+  void* gx;                  /* or NULL */
+  void* gsignal;             /* or NULL */
+  void* gparams;             /* or NULL */
+  void* work;                /* with gparams */
+} zk_umnn_bwd_args_v1;
+int zk_umnn_backward(const zk_umnn_bwd_args_v1* args, void* stream);
+/* Host only: the rules, arguments and return values of zk_mnn_backward_floats / _geometry / _workspace_floats (one geometry function behind both
+ * families; the sizes are those of the same layout, served when the quadrature table also fits behind it). */
+int zk_umnn_backward_floats(int S, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats);
+int zk_umnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks);
+int zk_umnn_backward_workspace_floats(int64_t N, int64_t Dsel, int S, int n_hidden, int width0, int width1, int width2, int64_t* floats);
+
 /* ---- Gaussian mixture model (GMM; zuko/mixtures.py, zuko/distributions.py: Mixture; float32 and float64) ------------------------------------
  * One row of phi, as the model's MLP (or the concatenated parameter list) lays it out, with Lc = 1 if tied else K, Dd = 1 for spherical
  * covariance and D otherwise:

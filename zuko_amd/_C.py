@@ -50,7 +50,7 @@ def _parse_structs(path: str) -> dict:
 
 
 STRUCTS = _parse_structs(_HEADER)
-_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1}
+_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_umnn_bwd_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1}
 
 
 def args(struct: str, **fields):
@@ -99,6 +99,7 @@ _AR, _CP, _INC = POINTER(STRUCTS["zk_ar_args_v1"]), POINTER(STRUCTS["zk_coupling
 _MNN = POINTER(STRUCTS["zk_mnn_args_v1"])
 _MNN_BWD = POINTER(STRUCTS["zk_mnn_bwd_args_v1"])
 _UMNN = POINTER(STRUCTS["zk_umnn_args_v1"])
+_UMNN_BWD = POINTER(STRUCTS["zk_umnn_bwd_args_v1"])
 _GMM = POINTER(STRUCTS["zk_gmm_args_v1"])
 _CNF = POINTER(STRUCTS["zk_cnf_args_v1"])
 
@@ -171,6 +172,10 @@ SIGNATURES = {
     "zk_umnn_forward": [_UMNN, P],
     "zk_umnn_inverse": [_UMNN, P],
     "zk_umnn_launch_geometry": [L, L, POINTER(c_int), POINTER(c_int)],
+    "zk_umnn_backward": [_UMNN_BWD, P],
+    "zk_umnn_backward_floats": [I, I, I, I, I, POINTER(c_int), POINTER(c_int)],
+    "zk_umnn_backward_geometry": [L, L, POINTER(c_int), POINTER(c_int)],
+    "zk_umnn_backward_workspace_floats": [L, L, I, I, I, I, I, POINTER(c_int64)],
     "zk_gmm_log_prob": [_GMM, P],
     "zk_gmm_backward": [_GMM, P],
     "zk_gmm_total": [I, I, I, I],

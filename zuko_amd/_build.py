@@ -44,6 +44,7 @@ SOURCES = {
     "mnn.hip": ["-ffp-contract=off"],
     "mnn_backward.hip": ["-ffp-contract=off"],
     "umnn.hip": ["-ffp-contract=off"],
+    "umnn_backward.hip": ["-ffp-contract=off"],
     "gmm.hip": ["-ffp-contract=off"],
     "cnf.hip": ["-ffp-contract=off"],
 }

@@ -27,66 +27,11 @@
 //     are then added in LDS in the order 0, 1, 2, 3 and ONE partial per (row chunk, column) is written.  No atomics.
 //   * mnn_bwd_reduce_kernel adds the partials in chunk order, applies sign(W) and scatters through the gradient table (the inverse of the
 //     partial's layout) into the flat parameter order; columns name distinct features, so every parameter has one writer.
-#include "zk_mnn_common.h"
+// The layouts, the geometry, the transpose, the partial stores and the reduction's launch are shared with UNAF's adjoint (csrc/umnn_backward.hip)
+// through csrc/zk_mnn_bwd_common.h; the reduction kernel itself lives here, with a flag for the family whose weights are signed.
+#include "zk_mnn_bwd_common.h"
 
 namespace zk {
-
-#define MNN_BWD_TM 4          // tiles per layer: widths <= 64
-#define MNN_BWD_SCRATCH 512   // floats of transpose scratch per wavefront
-#define MNN_BWD_BLOCKS 512    // the grid aims at this many blocks: two per CU
-#define MNN_WAVE_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-// Offsets (floats) behind the forward image, and of one (row chunk, column) partial; the arithmetic of zuko_amd/mnn_plan.py: layout_backward.
-struct MnnBwdLayout {
-  int ts;       // 16-wide tiles of the signal = ceil(S / 16)
-  int o_wT[3];  // l = 1, 2: [T_{l-1}][T_l][256], lane (j, q), r of tile (i, o): |W_l[16 o + 4 q + r][16 i + j]|
-  int o_w0sT;   // [ts][T_0][256], tile (i, o): |W_0[16 o + 4 q + r][1 + 16 i + j]| (zero behind S)
-  int total;    // the backward image
-  int g_w0s, g_w0x, g_b0, g_w[3], g_b[3], g_wl, g_bl, g_total;
-};
-
-static inline bool mnn_bwd_layout(const MnnLayout& L, MnnBwdLayout* B) {
-  for (int l = 0; l < L.nh; ++l)
-    if (L.T[l] > MNN_BWD_TM) return false;
-  B->ts = (L.S + 15) / 16;
-  int o = L.total;
-  B->o_wT[0] = 0;
-  for (int l = 1; l < 3; ++l) {
-    B->o_wT[l] = o;
-    if (l < L.nh) o += L.T[l] * L.T[l - 1] * 256;
-  }
-  B->o_w0sT = o; o += B->ts * L.T[0] * 256;
-  B->total = o;
-  int g = 0;
-  B->g_w0s = g; g += L.T[0] * B->ts * 256;
-  B->g_w0x = g; g += L.T[0] * 16;
-  B->g_b0 = g; g += L.T[0] * 16;
-  B->g_w[0] = B->g_b[0] = 0;
-  for (int l = 1; l < 3; ++l) {
-    B->g_w[l] = g; if (l < L.nh) g += L.T[l] * L.T[l - 1] * 256;
-    B->g_b[l] = g; if (l < L.nh) g += L.T[l] * 16;
-  }
-  B->g_wl = g; g += L.T[L.nh - 1] * 16;
-  B->g_bl = g; g += 4;
-  B->g_total = g;
-  return true;
-}
-
-static inline int mnn_bwd_lds_floats(const MnnBwdLayout& B) { return (B.total > B.g_total ? B.total : B.g_total) + (MNN_THREADS / 64) * MNN_BWD_SCRATCH; }
-
-// rows per chunk (a multiple of 64) and the number of chunks: a pure function of the two sizes
-static inline int mnn_bwd_geometry(long long N, long long Dsel, int* rows_per_chunk, int* n_chunks) {
-  if (N < 1 || Dsel < 1 || Dsel > 65535 || N > (1LL << 40) || !rows_per_chunk || !n_chunks) return ZK_EINVAL;
-  long long want = MNN_BWD_BLOCKS / Dsel;
-  if (want < 1) want = 1;
-  const long long t64 = (N + 63) / 64;
-  if (want > t64) want = t64;
-  const long long rows = ((t64 + want - 1) / want) * 64;
-  if (rows > 0x7fffffc0LL) return ZK_EINVAL;
-  *rows_per_chunk = (int)rows;
-  *n_chunks = (int)((N + rows - 1) / rows);
-  return 0;
-}
 
 struct MnnBwdArgs {
   const float* x;
@@ -103,11 +48,6 @@ struct MnnBwdArgs {
   MnnLayout L;
   MnnBwdLayout B;
 };
-
-typedef mnn_f4 (&bwd_tiles)[MNN_BWD_TM];
-typedef const mnn_f4 (&bwd_ctiles)[MNN_BWD_TM];
-
-__device__ __forceinline__ mnn_f4 bwd_zero() { return mnn_f4{0.f, 0.f, 0.f, 0.f}; }
 
 // v = act(p), t = act'(p) * pd for the T tiles of a layer (the two-way ELU of csrc/mnn.hip)
 __device__ __forceinline__ void bwd_act(bwd_ctiles p, bwd_ctiles pd, int T, int q, bwd_tiles v, bwd_tiles t) {
@@ -167,15 +107,6 @@ __device__ __forceinline__ void bwd_local(bwd_ctiles p, bwd_ctiles pd, int T, in
   });
 }
 
-// A 16 x 16 fragment held as (element = j, units 4 q + r) becomes the four k-steps of a matrix operand that contracts over the elements:
-// out[s] = fragment[unit = lane & 15][element = 4 s + (lane >> 4)].
-__device__ __forceinline__ void bwd_transpose(float* scr, const mnn_f4& a, int lane, int j, int q, float (&out)[4]) {
-  MNN_WAVE_SYNC();  // the reads of the fragment before this one are done
-  *reinterpret_cast<mnn_f4*>(scr + j * 16 + q * 4) = a;
-  MNN_WAVE_SYNC();
-  mnn_for<4>([&](auto s) MNN_INLINE { out[s] = scr[s * 64 + lane]; });
-}
-
 // acc[o][i] += pb[o] v[i]^T + pdb[o] t[i]^T, contracted over the wave's 16 elements
 __device__ __forceinline__ void bwd_outer(float* scr, int lane, int j, int q, int tout, int tin, bwd_ctiles pb, bwd_ctiles pdb, bwd_ctiles v, bwd_ctiles t,
                                           mnn_f4 (&acc)[MNN_BWD_TM][MNN_BWD_TM]) {
@@ -219,46 +150,6 @@ __device__ __forceinline__ void bwd_down(const float* WT, int tin, int tout, int
         }
       });
     }
-  });
-}
-
-__device__ __forceinline__ void bwd_add(bwd_tiles acc, bwd_ctiles v, int T) {
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    if (o < T) acc[o] += v[o];
-  });
-}
-
-// sum over the 16 lanes that share q: the same value in all of them, the same order everywhere
-__device__ __forceinline__ float bwd_sum_j(float p) {
-  p += __shfl_xor(p, 1, 64);
-  p += __shfl_xor(p, 2, 64);
-  p += __shfl_xor(p, 4, 64);
-  p += __shfl_xor(p, 8, 64);
-  return p;
-}
-
-// the wave's share of a bias-like gradient (per-lane sums over the rows of element lane j) into the block's partial
-__device__ __forceinline__ void bwd_put_units(float* G, bwd_ctiles acc, int T, int j, int q, bool set) {
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    if (o < T) {
-      mnn_f4 s;
-      mnn_for<4>([&](auto r) MNN_INLINE { s[(int)r] = bwd_sum_j(acc[o][(int)r]); });
-      if (j == 0) {
-        mnn_f4* dst = reinterpret_cast<mnn_f4*>(G + o * 16 + q * 4);
-        *dst = set ? s : *dst + s;
-      }
-    }
-  });
-}
-
-template <int TI> __device__ __forceinline__ void bwd_put_tiles(float* G, const mnn_f4 (&acc)[MNN_BWD_TM][TI], int tout, int tin, int lane, bool set) {
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    mnn_for<TI>([&](auto i) MNN_INLINE {
-      if (o < tout && i < tin) {
-        mnn_f4* dst = reinterpret_cast<mnn_f4*>(G + (o * tin + i) * 256 + lane * 4);
-        *dst = set ? acc[o][i] : *dst + acc[o][i];
-      }
-    });
   });
 }
 
@@ -451,10 +342,10 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_
   for (int i = tid * 4; i < B.g_total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(out + i) = *reinterpret_cast<const mnn_f4*>(G + i);
 }
 
-// gparams[table[f][pos]] = sign(W) * the partials of (column, pos) added in chunk order
+// gparams[table[f][pos]] = the partials of (column, pos) added in chunk order, times sign(W) with `apply_sign` (NAF; UNAF's weights are signed)
 __global__ __launch_bounds__(256) void mnn_bwd_reduce_kernel(const float* __restrict__ work, const int* __restrict__ table, const int* __restrict__ feat,
                                                              const float* __restrict__ params, float* __restrict__ gparams, int chunks, int Dsel, int g_total,
-                                                             int n_features, long long flat_weights, long long flat_total) {
+                                                             int n_features, long long flat_weights, long long flat_total, int apply_sign) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)Dsel * g_total) return;
   const int col = (int)(idx / g_total), pos = (int)(idx % g_total);
@@ -464,18 +355,19 @@ __global__ __launch_bounds__(256) void mnn_bwd_reduce_kernel(const float* __rest
   if (dst < 0 || dst >= flat_total) return;
   float s = 0.f;
   for (int c = 0; c < chunks; ++c) s += work[((size_t)c * Dsel + col) * g_total + pos];
-  if (dst < flat_weights) {
+  if (apply_sign && dst < flat_weights) {
     const float w = params[dst];
     s = w > 0.f ? s : (w < 0.f ? -s : 0.f);
   }
   gparams[dst] = s;
 }
 
-static bool mnn_bwd_shape(int S, int nh, int w0, int w1, int w2, MnnLayout* L, MnnBwdLayout* B) {
-  const int widths[3] = {w0, w1, w2};
-  if (!mnn_layout(S, nh, widths, L)) return false;
-  if (!mnn_bwd_layout(*L, B)) return false;
-  return mnn_bwd_lds_floats(*B) * 4 <= MNN_LDS_MAX;
+int mnn_bwd_reduce(const float* work, const int* table, const int* feat, const float* params, float* gparams, int chunks, int Dsel, int g_total, int n_features,
+                   long long flat_weights, long long flat_total, bool apply_sign, hipStream_t st) {
+  const long long n = (long long)Dsel * g_total;
+  hipLaunchKernelGGL(mnn_bwd_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, table, feat, params, gparams, chunks, Dsel, g_total, n_features,
+                     flat_weights, flat_total, apply_sign ? 1 : 0);
+  return ZK_LAUNCH_CHECK();
 }
 
 template <int NH> static const void* mnn_bwd_fn(int ts) {
@@ -513,10 +405,8 @@ static int mnn_backward(const zk_mnn_bwd_args_v1* p, void* stream) {
   const void* fn = a.L.nh == 1 ? mnn_bwd_fn<1>(a.B.ts) : (a.L.nh == 2 ? mnn_bwd_fn<2>(a.B.ts) : mnn_bwd_fn<3>(a.B.ts));
   const int rc = mnn_launch_dyn_lds(fn, dim3((unsigned)chunks, (unsigned)a.Dsel), mnn_bwd_lds_floats(a.B) * 4, &a, st);
   if (rc != 0 || !a.work) return rc;
-  const long long n = (long long)a.Dsel * a.B.g_total;
-  hipLaunchKernelGGL(mnn_bwd_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)a.work, (const int*)p->grad_table, a.feat,
-                     (const float*)p->params, (float*)p->gparams, chunks, a.Dsel, a.B.g_total, a.n_features, (long long)p->flat_weights, (long long)p->flat_total);
-  return ZK_LAUNCH_CHECK();
+  return mnn_bwd_reduce((const float*)a.work, (const int*)p->grad_table, a.feat, (const float*)p->params, (float*)p->gparams, chunks, a.Dsel, a.B.g_total, a.n_features,
+                        (long long)p->flat_weights, (long long)p->flat_total, true, st);
 }
 
 }  // namespace zk

@@ -20,7 +20,8 @@ The absolute value is taken when the image is made: `index_table` addresses the 
 csrc/zk_mnn_common.h: mnn_layout, which both kernel families use (zk_mnn_image_floats returns its total; tests compare the two).
 
 The integrand networks of an unconstrained monotone network (UNAF: a stacked `MLP(1 + S, 1, hidden, stack=F)` with ELU(alpha = 1), csrc/umnn.hip)
-use the same image with the SIGNED weights: `flat_parameters` takes no absolute value for them.
+use the same image with the SIGNED weights: `flat_parameters` takes no absolute value for them, and neither does their backward image
+(`backward_image_of(..., signed=True)`, csrc/umnn_backward.hip).
 """
 
 from __future__ import annotations
@@ -337,10 +338,11 @@ class BackwardImage(Image):
         self.version = None
 
 
-def backward_image_of(network, device) -> BackwardImage | None:
-    """The cached backward image of a MonotonicMLP stack on `device` (zuko_amd.invalidate drops it), or None outside the adjoint's envelope."""
+def backward_image_of(network, device, signed: bool = False) -> BackwardImage | None:
+    """The cached backward image of a MonotonicMLP stack (`signed`: of the integrand networks of a UMNN, whose weights enter as they are) on
+    `device` (zuko_amd.invalidate drops it), or None for the other kind of network and outside the adjoint's envelope."""
     sh = shape_of(network)
-    if sh is None or is_signed(network) or layout_backward(sh[0], sh[1]) is None:
+    if sh is None or is_signed(network) != bool(signed) or layout_backward(sh[0], sh[1]) is None:
         return None
     key = (str(device), sh)
     cache = network.__dict__.get("_mnn_bwd_image_cache")

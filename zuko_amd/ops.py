@@ -917,16 +917,28 @@ def gauss_inverse(y: Tensor, shift: Tensor, scale: Tensor, bound: float = GAUSS_
 
 
 # ------------------------------------------------------------------------------------------------
-# unconstrained monotone neural network (UNAF): zk_umnn_forward / zk_umnn_inverse, torch ops when the kernel does not serve the call
+# unconstrained monotone neural network (UNAF): zk_umnn_forward / zk_umnn_inverse / zk_umnn_backward, torch ops when the kernels do not serve the call
 # ------------------------------------------------------------------------------------------------
 
 UMNN_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_unaf.py measures the kernels against it)
 UMNN_QUAD_MAX = 64  # UMNN_QUAD_MAX of csrc/umnn.hip
+UMNN_ADJOINT = True  # False: calls that need gradients take the torch-op path (the quadrature re-run under autograd), as before zk_umnn_backward existed
 
 
 def umnn_supported(S: int, widths) -> bool:
     """True when zk_umnn_forward / zk_umnn_inverse serve per-feature integrand networks (1 + S) -> widths -> 1: the limits of mnn_supported."""
     return mnn_supported(S, widths)
+
+
+def umnn_backward_supported(S: int, widths, n: int = 32) -> bool:
+    """True when zk_umnn_backward serves per-feature integrand networks (1 + S) -> widths -> 1 with an n-point rule: the shapes of
+    mnn_backward_supported (widths <= 64) whose backward image, transpose scratch and quadrature table fit the LDS limit, 1 <= n <= 64."""
+    from . import mnn_plan
+
+    B = mnn_plan.layout_backward(int(S), tuple(widths))
+    if B is None or not 1 <= int(n) <= UMNN_QUAD_MAX:
+        return False
+    return 4 * (max(B.total, B.g_total) + mnn_plan.BWD_SCRATCH + 2 * UMNN_QUAD_MAX) <= mnn_plan.LDS_MAX
 
 
 @lru_cache(maxsize=None)
@@ -1052,13 +1064,133 @@ def _umnn_args(img, n: int, x2: Tensor, s3: Tensor, c2, strides: dict, feat, out
                    quad=_umnn_quad(n, x2.device).data_ptr(), feat=None if feat is None else feat.data_ptr(), y=out.data_ptr(), **strides, **extra)
 
 
+def _umnn_launch_forward(img, network, n: int, x2: Tensor, s3: Tensor, c2, strides: dict, feat, reduce: bool):
+    N, D = x2.shape
+    data = img.refresh(network)
+    y = torch.empty((N, D), dtype=torch.float32, device=x2.device)
+    ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x2.device)
+    work = torch.empty((N, D), dtype=torch.float32, device=x2.device) if reduce else None
+    a = _umnn_args(img, n, x2, s3, c2, strides, _mnn_feat(network, feat, x2.device), y, ladj=ladj.data_ptr(), work=None if work is None else work.data_ptr(),
+                   ladj_reduced=int(reduce))
+    _C.check(_C.lib().zk_umnn_forward(a, _stream()), "zk_umnn_forward")
+    del data
+    return y, ladj
+
+
+def umnn_backward_launch(bimg, network, n: int, x2: Tensor, s3: Tensor, strides: dict, feat, gy, gl, need_x: bool = True, need_signal: bool = True,
+                         need_params: bool = True):
+    """zk_umnn_backward on prepared operands: x2 [N, D] and s3 [N, D, S] as _umnn_prepare hands them out with their `strides` (the signal is read in
+    place), gy [N, D] or None, gl [N, D] / [N] or None (contiguous).  Returns (gx [N, D], gsignal [N, D S], gparams in mnn_plan.flat_parameters
+    order), None where not asked for.  Launches on the current stream; nothing synchronises."""
+    N, D = x2.shape
+    lay, B = bimg.layout, bimg.backward
+    dev = x2.device
+    data = bimg.refresh(network)
+    gx = torch.empty((N, D), dtype=torch.float32, device=dev) if need_x else None
+    gs = torch.empty((N, D * lay.S), dtype=torch.float32, device=dev) if need_signal else None
+    gp = torch.empty(bimg.flat_total, dtype=torch.float32, device=dev) if need_params else None
+    work = None
+    if need_params and N > 0:
+        import ctypes
+
+        rows, chunks = ctypes.c_int(0), ctypes.c_int(0)
+        _C.check(_C.lib().zk_umnn_backward_geometry(N, D, ctypes.byref(rows), ctypes.byref(chunks)), "zk_umnn_backward_geometry")
+        work = torch.empty(chunks.value * D * B.g_total, dtype=torch.float32, device=dev)
+    w = list(lay.widths) + [0, 0]
+    ft = _mnn_feat(network, feat, dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = _C.args("zk_umnn_bwd_args_v1", S=lay.S, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], n_features=bimg.features, image_floats=B.total,
+                grad_floats=B.g_total, gl_reduced=int(gl is not None and gl.dim() == 1), n_quad=n, N=N, Dsel=D, ldx=strides["ldx"], ld_signal=strides["ld_signal"],
+                ld_col=strides["ld_col"], ld_gx=D, ld_gsignal=D * lay.S, flat_total=bimg.flat_total, flat_weights=bimg.flat_weights, x=x2.data_ptr(),
+                signal=s3.data_ptr(), image=data.data_ptr(), quad=_umnn_quad(n, dev).data_ptr(), feat=ptr(ft), gy=ptr(gy), gl=ptr(gl),
+                grad_table=bimg.table.data_ptr() if need_params else None, gx=ptr(gx), gsignal=ptr(gs), gparams=ptr(gp), work=ptr(work))
+    _C.check(_C.lib().zk_umnn_backward(a, _stream()), "zk_umnn_backward")
+    del data
+    return gx, gs, gp
+
+
+class UmnnForwardFn(torch.autograd.Function):
+    """(y, ladj) of the unconstrained monotone networks under autograd: zk_umnn_forward forward, ONE zk_umnn_backward call backward (the adjoint
+    kernel and the chunk reduction), which recomputes the forward from x and the signal: nothing else is saved.  The constant's gradient is gy."""
+
+    @staticmethod
+    def forward(ctx, network, feat, reduce, n, strides, x2, s3, c2, *params):
+        from . import mnn_plan
+
+        ctx.network, ctx.feat, ctx.n, ctx.strides = network, feat, n, strides
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x2, s3, *params)
+        return _umnn_launch_forward(mnn_plan.image_of(network, x2.device), network, n, x2.detach(), s3.detach(), None if c2 is None else c2.detach(), strides, feat, reduce)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # raw-pointer HIP kernels on detached data: double backward (create_graph=True) must raise
+    def backward(ctx, gy, gl):
+        from . import mnn_plan
+
+        x2, s3, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_p = any(need[8:])
+        none = (None,) * 5
+        if gy is None and gl is None:
+            return none + (None,) * (3 + len(params))
+        bimg = mnn_plan.backward_image_of(ctx.network, x2.device, signed=True)
+        gy = None if gy is None else gy.contiguous()
+        gx, gs, gp = umnn_backward_launch(bimg, ctx.network, ctx.n, x2, s3, ctx.strides, ctx.feat, gy, None if gl is None else gl.contiguous(),
+                                          need_x=need[5], need_signal=need[6], need_params=need_p)
+        gparams = [None] * len(params)
+        if need_p:
+            o = 0
+            for i, p in enumerate(params):
+                gparams[i] = gp[o : o + p.numel()].view(p.shape) if need[8 + i] else None
+                o += p.numel()
+        return none + (gx, None if gs is None else gs.view(s3.shape), gy if need[7] else None, *gparams)
+
+
+def _umnn_adjoint_serves(network, x: Tensor, signal: Tensor, constant, feat, n: int):
+    """The dtype the adjoint path runs this call from (float32, or bfloat16 trained on float32 copies), or None: nothing asks for gradients,
+    switches off, another dtype, a network or rule outside umnn_backward_supported, or a feature named twice."""
+    from . import mnn_plan
+
+    if not (UMNN_KERNEL and UMNN_ADJOINT and torch.is_grad_enabled()) or n > UMNN_QUAD_MAX:
+        return None
+    ts = [x, signal, *network.parameters()] + ([] if constant is None else [constant])
+    if not any(t.requires_grad for t in ts):
+        return None
+    dt = x.dtype
+    if dt not in (torch.float32, torch.bfloat16) or any(t.dtype != dt for t in ts):
+        return None
+    bimg = mnn_plan.backward_image_of(network, x.device, signed=True)
+    if bimg is None or not umnn_backward_supported(bimg.S, bimg.widths, n) or not _mnn_feat_distinct(network, feat, x.device):
+        return None
+    return dt
+
+
+def _umnn_forward_adjoint(x: Tensor, signal: Tensor, constant, network, feat, reduce: bool, n: int, dt):
+    from . import mnn_plan
+
+    lins = mnn_plan._linears(network)
+    params = [l.weight for l in lins] + [l.bias for l in lins]  # (the order of mnn_plan.flat_parameters)
+    if dt == torch.bfloat16:
+        x, signal, params = x.float(), signal.float(), [p.float() for p in params]
+        constant = None if constant is None else constant.float()
+    shape, x2, s3, c2, strides = _umnn_prepare(x, signal, constant)  # (differentiable views: broadcast gradients are summed by autograd)
+    y, ladj = UmnnForwardFn.apply(network, feat, reduce, int(n), strides, x2, s3, c2, *params)
+    lshape = shape[:-1] if reduce else shape
+    y = y if y.shape == shape else y.reshape(shape)  # (two-dimensional calls hand out the node's own outputs)
+    return (y.to(dt) if dt != torch.float32 else y), (ladj if ladj.shape == lshape else ladj.reshape(lshape))
+
+
 def umnn_forward(x: Tensor, signal: Tensor, constant, network, feat=None, reduce: bool = False, n: int = 32):
     """(y, ladj) of the per-feature unconstrained monotone networks: y = x sum_i w_i g(t_i x) + constant over the n-point Gauss-Legendre rule,
     g = exp(squash(h)) with h = `network` (a stacked zuko_amd.nn.MLP(1 + S, 1, ...) with ELU), ladj = squash(h(x)) = log g(x).  x [..., D],
     signal [..., D, S], constant [..., D] | None; column j uses the network of feature feat[j] (`feat`: None, a (lo, hi) run or an index tensor).
-    zk_umnn_forward when it serves the call; otherwise (unsupported shape or activation, float64, gradients) the same expressions as torch ops
+    zk_umnn_forward when it serves the call, under autograd with zk_umnn_backward as its adjoint (UmnnForwardFn: float32 and bfloat16, shapes of
+    umnn_backward_supported); otherwise (unsupported shape or activation, float64, UMNN_ADJOINT = False) the same expressions as torch ops
     with the reference's autograd semantics (zuko/utils.py:282-326)."""
     _umnn_check(network, x, signal, constant, feat, n)
+    dt = _umnn_adjoint_serves(network, x, signal, constant, feat, n)
+    if dt is not None:
+        return _umnn_forward_adjoint(x, signal, constant, network, feat, reduce, n, dt)
     img = _umnn_kernel_serves(network, x, signal, constant, n)
     if img is None:
         y = _umnn_torch_f(network, signal, feat, n)(x)
@@ -1066,15 +1198,7 @@ def umnn_forward(x: Tensor, signal: Tensor, constant, network, feat=None, reduce
         ladj = _umnn_squash(_mnn_torch_f(network, x, signal, feat, signed=True)).expand(y.shape)
         return y, (ladj.sum(dim=-1) if reduce else ladj)
     shape, x2, s3, c2, strides = _umnn_prepare(x, signal, constant)
-    N, D = x2.shape
-    data = img.refresh(network)
-    y = torch.empty((N, D), dtype=torch.float32, device=x.device)
-    ladj = torch.empty((N,) if reduce else (N, D), dtype=torch.float32, device=x.device)
-    work = torch.empty((N, D), dtype=torch.float32, device=x.device) if reduce else None
-    a = _umnn_args(img, n, x2, s3, c2, strides, _mnn_feat(network, feat, x.device), y, ladj=ladj.data_ptr(), work=None if work is None else work.data_ptr(),
-                   ladj_reduced=int(reduce))
-    _C.check(_C.lib().zk_umnn_forward(a, _stream()), "zk_umnn_forward")
-    del data
+    y, ladj = _umnn_launch_forward(img, network, n, x2, s3, c2, strides, feat, reduce)
     return y.reshape(shape), ladj.reshape(shape[:-1] if reduce else shape)
 
 

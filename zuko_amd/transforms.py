@@ -259,8 +259,9 @@ class UnconstrainedMonotonicNetworkTransform(_Univariate):
     `zuko_amd.nn.MLP(1 + S, 1, ...)` with ELU), the integral by an n-point Gauss-Legendre rule: the univariate map of the unconstrained neural
     autoregressive flow.  Mirrors UMNN.g + UnconstrainedMonotonicTransform composed with AdditiveTransform (zuko/flows/neural.py:100-118,
     zuko/transforms.py:878-924): value and log-derivative in one launch (zk_umnn_forward), the inverse by the reference's bisection on
-    [-bound, bound] to `eps` (zk_umnn_inverse).  `features` as for MonotonicNetworkTransform.  Unsupported network shapes or activations,
-    float64 and calls that need gradients run the same expressions as torch ops (zuko_amd/ops.py: umnn_forward)."""
+    [-bound, bound] to `eps` (zk_umnn_inverse).  `features` as for MonotonicNetworkTransform.  Under autograd the forward launch sits in an
+    autograd node whose backward is one zk_umnn_backward call (ops.UmnnForwardFn: widths up to 64, at most 64 nodes).  Unsupported network shapes
+    or activations, float64 and the gradient of the inverse run the same expressions as torch ops (zuko_amd/ops.py: umnn_forward)."""
 
     def __init__(self, signal: Tensor, constant: Tensor | None, network, features=None, n: int = 32, bound: float = 10.0, eps: float = 1e-6, **kwargs) -> None:
         super().__init__(**kwargs)
