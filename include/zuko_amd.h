@@ -959,6 +959,69 @@ int zk_cnf_step(const zk_cnf_args_v1* args, void* stream);
 /* Floats of the weight image, or -1 outside the limits (host only). */
 int zk_cnf_image_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2);
 
+/* zk_cnf_adjoint_step makes ONE reverse step of the checkpoint adjoint (zuko/utils.py:556-593) for all N rows: a six-stage Dormand-Prince step of size
+ * -dt, without an error estimate, of the augmented system (x, a, g_phi) from the checkpoint AFTER the forward step (x, t, dt).  With
+ * beta = al * trace_scale, stage s evaluates at (t + c_s (-dt), x_s, a_s)
+ *     kx_s = -dt f(t_s, x_s)        ka_s = dt (a_s^T df/dx + beta d trace/dx)
+ * and adds b_s dt (a_s^T df/dphi + beta d trace/dphi) to every parameter gradient (b: the fifth-order weights).  The field, the split of the first
+ * layer and `pre` are those of zk_cnf_step.
+ *
+ *   x          [N, features], row stride ldx: the state after the forward step.  The x the reverse step reconstructs is not an output
+ *   ax         [N, features], row stride ld_ax: the adjoint of x;  ax_next [N, features], row stride ld_ax_next (may be ax itself)
+ *   al         [N]: the adjoint of the log-determinant component (constant along the integration), or NULL: the value alone, no trace term
+ *   pre        as for zk_cnf_step
+ *   image      the BACKWARD image (zuko_amd/cnf_plan.py: layout_backward): the forward image followed by the transposed tiles
+ *   gpre       [N, width0], row stride ld_gpre >= width0, a multiple of 4, 16-byte aligned: the gradient of `pre`, ACCUMULATED (the lane that owns an
+ *              element reads, adds and writes it; the caller zeroes it once per backward and turns it into the gradients of b0, W0c and c)
+ *   gparams    [flat_total] or NULL: the gradient in the order of the flat parameters (weights, then biases: cnf_plan.py: flat_offsets), ADDED to.
+ *              The columns of W0 that belong to the context, and b0, are not written.  Every block writes one partial per row chunk into `work`
+ *              and a second launch adds the partials in chunk order through grad_table (int32 [grad_floats]: position of a partial -> flat index
+ *              or -1; cnf_plan.py: grad_table).  No atomics: the same inputs give the same bits.
+ *   work       zk_cnf_adjoint_workspace_floats floats, 16-byte aligned, always: the partials, and behind them the k vectors of the stages (written
+ *              and read back by the lane that owns them).  Its contents mean nothing before or after a call
+ *   limits     those of zk_cnf_step with every width <= 64.
+ * A row's ax_next and gpre depend on its own x, ax, al and pre row only.  Refusals (hipErrorInvalidValue) come before any launch; N = 0 launches
+ * nothing. */
+typedef struct zk_cnf_adj_args_v1 {
+  uint32_t struct_size;    /* sizeof(zk_cnf_adj_args_v1) */
+  uint32_t version;        /* 1 */
+  int32_t features;
+  int32_t freqs;
+  int32_t n_hidden;
+  int32_t width0;
+  int32_t width1;
+  int32_t width2;
+  int32_t image_floats;    /* of the backward image: zk_cnf_adjoint_floats */
+  int32_t grad_floats;     /* of one partial: zk_cnf_adjoint_floats */
+  int64_t N;
+  int64_t ldx;
+  int64_t ld_ax;
+  int64_t ld_ax_next;
+  int64_t ld_pre;          /* 0: one shared row */
+  int64_t ld_gpre;
+  int64_t flat_total;      /* with gparams */
+  double t;
+  double dt;
+  double trace_scale;
+  const void* x;
+  const void* ax;
+  const void* al;            /* or NULL */
+  const void* pre;
+  const void* image;
+  const int32_t* grad_table; /* with gparams */
+  void* ax_next;
+  void* gpre;
+  void* gparams;             /* or NULL */
+  void* work;
+} zk_cnf_adj_args_v1;
+int zk_cnf_adjoint_step(const zk_cnf_adj_args_v1* args, void* stream);
+/* Host only.  Floats of the backward image and of one partial; hipErrorInvalidValue outside the limits. */
+int zk_cnf_adjoint_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats);
+/* Host only.  Rows per chunk (a multiple of 64) and the number of chunks of an N-row call: a pure function of N. */
+int zk_cnf_adjoint_geometry(int64_t N, int* rows_per_chunk, int* n_chunks);
+/* Host only.  Floats of `work` for an N-row call. */
+int zk_cnf_adjoint_workspace_floats(int64_t N, int features, int freqs, int n_hidden, int width0, int width1, int width2, int64_t* floats);
+
 /* ---- base density + final reduction (zuko/distributions.py:115-119, 337-363) ---------------------- *
  * out[n] = sum_d Normal(loc[d], scale[d]).log_prob(z[n, d]) (+ ladj[n] if ladj != NULL). */
 int zk_diag_normal_log_prob(int dtype, int64_t N, int64_t D, const void* z, const void* loc, const void* scale,

@@ -5,6 +5,11 @@ field evaluations per attempted step, each with a batched autograd Jacobian for 
 
     python scripts/bench_cnf.py                 # prints one JSON line
     rocprofv3 --kernel-trace --stats -- python scripts/bench_cnf.py --trace     # per-launch kernel times (kernel path only, few calls)
+    python scripts/bench_cnf.py --train         # one JSON line: an Adam step at batch 2^14 and 2^16 with ops.CNF_ADJOINT on and off
+    rocprofv3 --kernel-trace --stats -- python scripts/bench_cnf.py --train --trace   # per-launch times of the adjoint kernel (kernel path only)
+
+`--train`: the loss is -log_prob(x).mean(); a step is zero_grad, forward, backward, Adam.  With the switch on the forward runs on zk_cnf_step and the
+backward makes one zk_cnf_adjoint_step per accepted step; with it off (the default) both run in torch ops — the code path of the parent commit.
 
 FLOP per row and attempted step from the shapes, seven stages each: the value 2 [(2 Q + F) H1 + sum_l H_l H_{l+1} + H_last F] (the context's share
 of the first layer is one GEMM per integration, not counted) and F tangents of 2 [sum_l H_l H_{l+1} + H_last] each (a tangent enters the first
@@ -53,7 +58,80 @@ def timed(fn, min_seconds: float = 0.5, warmup: int = 2):
     return {"median_ms": 1e3 * times[len(times) // 2], "min_ms": 1e3 * times[0], "max_ms": 1e3 * times[-1], "calls": len(times)}
 
 
+def train_main() -> None:
+    dev = torch.device("cuda:0")
+    F, C, Q, hidden = 5, 3, 3, (64, 64)
+    g = torch.Generator().manual_seed(1)
+    X, Cx = torch.randn(2**16, F, generator=g).to(dev), torch.randn(2**16, C, generator=g).to(dev)
+
+    def stepper(on: bool, n: int):
+        torch.manual_seed(0)
+        flow = CNF(F, C).to(dev).train()
+        opt = torch.optim.Adam(flow.parameters(), lr=1e-3)
+        x, c = X[:n], Cx[:n]
+        stats = {}
+
+        def step():
+            ops.CNF_ADJOINT = on
+            try:
+                opt.zero_grad(set_to_none=True)
+                loss = -flow(c).log_prob(x).mean()
+                stats.update(ops.CNF_STATS)
+                loss.backward()
+                stats.update(ops.CNF_STATS)
+                opt.step()
+            finally:
+                ops.CNF_ADJOINT = False
+            return loss
+
+        return flow, step, stats
+
+    if "--trace" in sys.argv:
+        for n in (2**14, 2**16):
+            _, step, _ = stepper(True, n)
+            for _ in range(3):
+                step()
+        torch.cuda.synchronize()
+        return
+    out = {"workload": f"Adam step of CNF({F}, {C}), freqs {Q}, hidden {hidden}, loss -log_prob.mean(), weights as initialised (seed 0)", "version": zuko_amd.__version__}
+    for n in (2**14, 2**16):
+        key = f"batch_{n}"
+        # the first step's gradients of the two paths on the same weights and data
+        grads = {}
+        for on in (True, False):
+            flow, step, stats = stepper(on, n)
+            ops.CNF_ADJOINT = on
+            try:
+                (-flow(Cx[:n]).log_prob(X[:n]).mean()).backward()
+            finally:
+                ops.CNF_ADJOINT = False
+            grads[on] = torch.cat([p.grad.reshape(-1) for p in flow.parameters()])
+        out[key + "_grad_max_abs_diff_over_max_abs"] = float((grads[True] - grads[False]).abs().max() / grads[False].abs().max())
+        runs = {}
+        steppers = {on: stepper(on, n) for on in (True, False)}
+        for rnd in range(2):  # alternate the two paths: neither sees a systematically warmer or cooler device
+            for on in (True, False):
+                runs.setdefault(on, []).append(timed(steppers[on][1], min_seconds=1.0, warmup=2))
+        for on, name in ((True, "adjoint_on"), (False, "adjoint_off")):
+            best = min(runs[on], key=lambda r: r["median_ms"])
+            st = steppers[on][2]
+            out[f"{key}_{name}"] = best | {"medians_ms": [round(r["median_ms"], 3) for r in runs[on]], "path": st.get("path"),
+                                           "last_step": {k: st[k] for k in ("attempts", "accepted", "adjoint_steps") if k in st}}
+        out[key + "_speedup"] = out[f"{key}_adjoint_off"]["median_ms"] / out[f"{key}_adjoint_on"]["median_ms"]
+        # events around the entry points over one step on the kernel path
+        _C.PROFILE = {}
+        steppers[True][1]()
+        torch.cuda.synchronize()
+        prof, _C.PROFILE = _C.PROFILE, None
+        for sym in ("zk_cnf_step", "zk_cnf_adjoint_step"):
+            ts = [a.elapsed_time(b) for a, b, _ in prof.get(sym, [])]
+            out[f"{key}_{sym}_launch_ms"] = {"launches": len(ts), "mean": sum(ts) / max(len(ts), 1), "min": min(ts, default=0.0), "max": max(ts, default=0.0)}
+    print(json.dumps(out))
+
+
 def main() -> None:
+    if "--train" in sys.argv:
+        return train_main()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     F, C, Q, hidden = 5, 3, 3, (64, 64)

@@ -50,7 +50,7 @@ def _parse_structs(path: str) -> dict:
 
 
 STRUCTS = _parse_structs(_HEADER)
-_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_umnn_bwd_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1}
+_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_umnn_bwd_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1, "zk_cnf_adj_args_v1": 1}
 
 
 def args(struct: str, **fields):
@@ -102,6 +102,7 @@ _UMNN = POINTER(STRUCTS["zk_umnn_args_v1"])
 _UMNN_BWD = POINTER(STRUCTS["zk_umnn_bwd_args_v1"])
 _GMM = POINTER(STRUCTS["zk_gmm_args_v1"])
 _CNF = POINTER(STRUCTS["zk_cnf_args_v1"])
+_CNF_ADJ = POINTER(STRUCTS["zk_cnf_adj_args_v1"])
 
 # symbol -> argument types (return type is always int = hipError_t)
 SIGNATURES = {
@@ -183,6 +184,10 @@ SIGNATURES = {
     "zk_gmm_launch_geometry": [I, I, I, I, I, POINTER(c_int)],
     "zk_cnf_step": [_CNF, P],
     "zk_cnf_image_floats": [I, I, I, I, I, I],
+    "zk_cnf_adjoint_step": [_CNF_ADJ, P],
+    "zk_cnf_adjoint_floats": [I, I, I, I, I, I, POINTER(c_int), POINTER(c_int)],
+    "zk_cnf_adjoint_geometry": [L, POINTER(c_int), POINTER(c_int)],
+    "zk_cnf_adjoint_workspace_floats": [L, I, I, I, I, I, I, POINTER(c_int64)],
 }
 
 

@@ -34,6 +34,7 @@ def invalidate(module) -> None:
         for k in ("_mnn_image_cache", "_mnn_bwd_image_cache", "_mnn_feat_cache"):  # weight image of the monotone networks of a NAF (mnn_plan.py)
             m.__dict__.pop(k, None)
         m.__dict__.pop("_cnf_image_cache", None)  # weight image of the field of a CNF (cnf_plan.py)
+        m.__dict__.pop("_cnf_bwd_image_cache", None)  # and the backward image of its adjoint kernel
         from . import train as _train
         from .flows import coupling as _cp
 

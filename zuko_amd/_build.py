@@ -47,6 +47,7 @@ SOURCES = {
     "umnn_backward.hip": ["-ffp-contract=off"],
     "gmm.hip": ["-ffp-contract=off"],
     "cnf.hip": ["-ffp-contract=off"],
+    "cnf_backward.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"] + (["-DZK_INC_FAST_BUILD"] if os.environ.get("ZUKO_AMD_FAST_BUILD") == "1" else [])
 

@@ -140,6 +140,140 @@ def index_table(F: int, Q: int, C: int, widths) -> np.ndarray:
     return idx.astype(np.int32)
 
 
+WIDTH_MAX_BACKWARD = 64  # MNN_BWD_TM tiles of csrc/zk_mnn_bwd_common.h: the adjoint keeps every weight's gradient in registers
+SCRATCH_BACKWARD = 4 * (512 + 512)  # transpose scratch and column sums of a block's four wavefronts (floats)
+
+
+@dataclass
+class BackwardLayout:
+    """The BACKWARD image of csrc/cnf_backward.hip — the forward image followed by the transposed tiles — and one row chunk's partial:
+
+        wT_l   [T_{l-1}][T_l][256]  lane (j, q), r of tile (i, o): W_l[16 o + 4 q + r][16 i + j]                       (l = 1, 2)
+        woT    [T_last][kx][64]     lane (j, q) of tile o, k-step s: W_last[4 s + q][16 o + j]                         (zeros behind F)
+        w0xT   [T_0][256]           lane (j, q), r of tile i: W0x[16 i + 4 q + r][feature 4 (j & 3) + (j >> 2)]        (zeros behind F)
+
+    partial (g_*): every weight tile as lane (j, q), r -> [16 o + 4 q + r][16 i + j]; for w0t the column is the embedding's entry j, for w0x
+    the feature j, for wo the row is feature j and the column unit 16 o + 4 q + r; biases in unit order; bo as the image's bo."""
+
+    fwd: Layout
+    o_wT: list = field(default_factory=list)
+    o_woT: int = 0
+    o_w0xT: int = 0
+    total: int = 0
+    g_w0t: int = 0
+    g_w0x: int = 0
+    g_w: list = field(default_factory=list)
+    g_b: list = field(default_factory=list)
+    g_wo: int = 0
+    g_bo: int = 0
+    g_total: int = 0
+
+
+def layout_backward(F: int, Q: int, widths) -> BackwardLayout | None:
+    """Offsets of the backward image and of a partial (csrc/cnf_backward.hip: cnf_adj_layout), or None for a shape the adjoint does not serve."""
+    L = layout(F, Q, widths)
+    if L is None or any(w > WIDTH_MAX_BACKWARD for w in L.widths):
+        return None
+    T, n = L.T, len(L.widths)
+    B = BackwardLayout(L)
+    o = L.total
+    B.o_wT = [0]
+    for l in range(1, n):
+        B.o_wT.append(o)
+        o += T[l] * T[l - 1] * 256
+    B.o_woT, o = o, o + T[-1] * L.kx * 64
+    B.o_w0xT, o = o, o + T[0] * 256
+    B.total = o
+    g = 0
+    B.g_w0t, g = g, g + T[0] * 256
+    B.g_w0x, g = g, g + T[0] * 256
+    B.g_w, B.g_b = [0], [0]
+    for l in range(1, n):
+        B.g_w.append(g)
+        g += T[l] * T[l - 1] * 256
+        B.g_b.append(g)
+        g += L.widths[l]
+    B.g_wo, g = g, g + T[-1] * 256
+    B.g_bo, g = g, g + 16
+    B.g_total = g
+    return B if 4 * (max(B.total, B.g_total) + SCRATCH_BACKWARD) <= LDS_MAX else None
+
+
+def index_table_backward(F: int, Q: int, C: int, widths) -> np.ndarray:
+    """int32 [backward image floats]: `index_table` followed by the transposed tiles' sources."""
+    B = layout_backward(F, Q, widths)
+    assert B is not None
+    L = B.fwd
+    widths = L.widths
+    dims = [2 * Q + F + C, *widths, F]
+    w_off, _, _, _ = flat_offsets(F, Q, C, widths)
+    idx = np.full(B.total, -1, dtype=np.int64)
+    idx[: L.total] = index_table(F, Q, C, widths)
+
+    def W(l, out, inp):
+        return w_off[l] + out * dims[l] + inp
+
+    e = np.arange(256)
+    el, er = e >> 2, e & 3
+    ej, eq = el & 15, el >> 4
+    n = len(widths)
+    for l in range(1, n):
+        for i in range(L.T[l - 1]):
+            for o in range(L.T[l]):
+                base = B.o_wT[l] + (i * L.T[l] + o) * 256
+                idx[base : base + 256] = W(l, 16 * o + 4 * eq + er, 16 * i + ej)
+    lane = np.arange(64)
+    j, q = lane & 15, lane >> 4
+    for o in range(L.T[-1]):
+        for s in range(L.kx):
+            k = 4 * s + q
+            base = B.o_woT + (o * L.kx + s) * 64
+            idx[base : base + 64] = np.where(k < F, W(n, np.minimum(k, F - 1), 16 * o + j), -1)
+    feat = 4 * (ej & 3) + (ej >> 2)
+    for i in range(L.T[0]):
+        base = B.o_w0xT + i * 256
+        idx[base : base + 256] = np.where(feat < F, W(0, 16 * i + 4 * eq + er, 2 * Q + np.minimum(feat, F - 1)), -1)
+    assert idx.max() < 2**31
+    return idx.astype(np.int32)
+
+
+def grad_table(F: int, Q: int, C: int, widths) -> np.ndarray:
+    """int32 [partial floats]: where every float of a partial goes in the flat gradient (-1 = nowhere: padding).  Every parameter the kernel owns —
+    all but the context's columns of W0 and b0 — has exactly one position."""
+    B = layout_backward(F, Q, widths)
+    assert B is not None
+    L = B.fwd
+    widths = L.widths
+    dims = [2 * Q + F + C, *widths, F]
+    w_off, b_off, _, _ = flat_offsets(F, Q, C, widths)
+    tab = np.full(B.g_total, -1, dtype=np.int64)
+
+    def W(l, out, inp):
+        return w_off[l] + out * dims[l] + inp
+
+    e = np.arange(256)
+    el, er = e >> 2, e & 3
+    ej, eq = el & 15, el >> 4
+    n = len(widths)
+    for o in range(L.T[0]):
+        unit = 16 * o + 4 * eq + er
+        tab[B.g_w0t + o * 256 : B.g_w0t + (o + 1) * 256] = np.where(ej < 2 * Q, W(0, unit, np.minimum(ej, 2 * Q - 1)), -1)
+        tab[B.g_w0x + o * 256 : B.g_w0x + (o + 1) * 256] = np.where(ej < F, W(0, unit, 2 * Q + np.minimum(ej, F - 1)), -1)
+    for l in range(1, n):
+        for o in range(L.T[l]):
+            for i in range(L.T[l - 1]):
+                base = B.g_w[l] + (o * L.T[l - 1] + i) * 256
+                tab[base : base + 256] = W(l, 16 * o + 4 * eq + er, 16 * i + ej)
+        tab[B.g_b[l] : B.g_b[l] + widths[l]] = b_off[l] + np.arange(widths[l])
+    for o in range(L.T[-1]):
+        tab[B.g_wo + o * 256 : B.g_wo + (o + 1) * 256] = np.where(ej < F, W(n, np.minimum(ej, F - 1), 16 * o + 4 * eq + er), -1)
+    m = np.arange(16)
+    fb = 4 * (m & 3) + (m >> 2)
+    tab[B.g_bo : B.g_bo + 16] = np.where(fb < F, b_off[n] + np.minimum(fb, F - 1), -1)
+    assert tab.max() < 2**31
+    return tab.astype(np.int32)
+
+
 def _linears(ode):
     return [m for m in ode if hasattr(m, "weight")]
 
@@ -202,4 +336,33 @@ def image_of(module, device) -> Image | None:
     if cache is None or cache[0] != key:
         cache = (key, Image(module, device))
         module.__dict__["_cnf_image_cache"] = cache
+    return cache[1]
+
+
+class BackwardImage:
+    """Device image of the adjoint kernel (csrc/cnf_backward.hip) and its gradient table, rebuilt like `Image`."""
+
+    def __init__(self, module, device):
+        self.F, self.C, self.widths, self.Q = shape_of(module)
+        self.layout = layout_backward(self.F, self.Q, self.widths)
+        self.idx = torch.from_numpy(index_table_backward(self.F, self.Q, self.C, self.widths)).to(device)
+        self.table = torch.from_numpy(grad_table(self.F, self.Q, self.C, self.widths)).to(device)
+        self.data = torch.empty(self.idx.numel(), dtype=torch.float32, device=device)
+        self.flat_total = flat_offsets(self.F, self.Q, self.C, self.widths)[2]  # weights and biases: the flat gradient's length
+        self.version = None
+
+    refresh = Image.refresh
+
+
+def backward_image_of(module, device) -> BackwardImage | None:
+    """The cached backward image of an `FFJTransform` on `device` (zuko_amd.invalidate drops it), or None for a field the adjoint kernel does not
+    serve."""
+    sh = shape_of(module)
+    if sh is None or layout_backward(sh[0], sh[3], sh[2]) is None:
+        return None
+    key = (str(device), sh)
+    cache = module.__dict__.get("_cnf_bwd_image_cache")
+    if cache is None or cache[0] != key:
+        cache = (key, BackwardImage(module, device))
+        module.__dict__["_cnf_bwd_image_cache"] = cache
     return cache[1]

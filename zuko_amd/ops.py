@@ -1414,19 +1414,11 @@ def cnf_step(img, x: Tensor, l, pre: Tensor, t: float, dt: float, atol: float, r
     _C.check(_C.lib().zk_cnf_step(a, _stream()), "zk_cnf_step")
 
 
-def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool):
-    """(x(t1), l(t1) | None) of the free-form Jacobian ODE of `module` (a zuko_amd.flows.FFJTransform) from x(t0) = x, l(t0) = 0, on the step kernel —
-    or None when the kernel does not serve the call (the caller then integrates in torch ops).  l is the log-determinant times `trace_scale`.
-
-    The loop is the reference's (zuko/utils.py:532-552) with t and dt carried in float32: per attempt `err` is zeroed, zk_cnf_step writes the step
-    into the spare buffers, the largest ratio is read back (the one synchronisation per attempt the reference has too), dt is multiplied by
-    min(10, max(0.1, 0.9 / ratio^(1/5))), and the buffers swap when ratio < 1.  The last step is clamped to the rest of the interval and ends at t1
-    exactly.  A non-finite ratio raises RuntimeError (utils.odeint does likewise)."""
+def _cnf_run(module, img, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool, keep: bool):
+    """The controller's loop on zk_cnf_step: (x(t1) [N, F], l(t1) [N] | None, the broadcast shape, pre, the accepted steps, the statistics).  With
+    `keep` every accepted step leaves (a clone of the state after it, the time after it, its size) for the adjoint: N F floats per step."""
     from .utils import step_factor
 
-    img = _cnf_kernel_serves(module, c, x)
-    if img is None:
-        return None
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("zuko_amd: a continuous flow cannot be captured into a HIP graph: its step loop reads the error estimate back after every "
                            "attempt and the number of attempts depends on the data")
@@ -1437,7 +1429,7 @@ def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
         shape, pre = x.shape, lin0.bias.detach()
     else:
         shape = torch.broadcast_shapes(x.shape[:-1], c.shape[:-1]) + (F,)
-        c2 = c.reshape(-1, c.shape[-1])
+        c2 = c.detach().reshape(-1, c.shape[-1])
         pre = torch.addmm(lin0.bias.detach(), c2, lin0.weight.detach()[:, Q2 + F :].t())  # once per integration: it does not depend on t or x
         if c2.shape[0] == 1:
             pre = pre[0]
@@ -1446,7 +1438,7 @@ def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
     pre = pre.contiguous()
     if pre.data_ptr() % 16:
         pre = pre.clone()  # (a parameter that is a view into a larger buffer: the kernel reads 16-byte pieces)
-    cur = x.expand(shape).reshape(-1, F).contiguous().clone()
+    cur = x.detach().expand(shape).reshape(-1, F).contiguous().clone()
     N = cur.shape[0]
     spare = torch.empty_like(cur)
     l_cur = torch.zeros(N, dtype=torch.float32, device=x.device) if with_ladj else None
@@ -1459,6 +1451,7 @@ def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
     dt = f32(end - t)
     sign = f32(np.sign(dt))
     attempts = accepted = 0
+    steps = []
     while sign * (end - t) > 0:
         rest = f32(end - t)
         dt = f32(sign * min(abs(dt), abs(rest)))
@@ -1475,10 +1468,165 @@ def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
                 cur, spare, l_cur, l_spare = spare, cur, l_spare, l_cur
                 t = end if dt == rest else f32(t + dt)
                 accepted += 1
+                if keep:
+                    steps.append((cur.clone(), float(t), float(dt)))
             dt = f32(dt * f32(step_factor(ratio)))
             if ok:
                 break
     del data
+    return cur, l_cur, shape, pre, steps, dict(path="kernel", attempts=attempts, accepted=accepted, t_end=float(t))
+
+
+def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool, phi=()):
+    """(x(t1), l(t1) | None) of the free-form Jacobian ODE of `module` (a zuko_amd.flows.FFJTransform) from x(t0) = x, l(t0) = 0, on the step kernel —
+    or None when the kernel does not serve the call (the caller then integrates in torch ops).  l is the log-determinant times `trace_scale`.
+
+    The loop is the reference's (zuko/utils.py:532-552) with t and dt carried in float32: per attempt `err` is zeroed, zk_cnf_step writes the step
+    into the spare buffers, the largest ratio is read back (the one synchronisation per attempt the reference has too), dt is multiplied by
+    min(10, max(0.1, 0.9 / ratio^(1/5))), and the buffers swap when ratio < 1.  The last step is clamped to the rest of the interval and ends at t1
+    exactly.  A non-finite ratio raises RuntimeError (utils.odeint does likewise).
+
+    A call that asks for gradients is served only with CNF_ADJOINT on and a field zk_cnf_adjoint_step serves (cnf_backward_supported): it goes
+    through CnfIntegrateFn, which gives gradients to x and to the tensors of `phi` (the transform's: the context and, in train() mode, the
+    parameters), as the reference's adjoint does."""
+    img = _cnf_kernel_serves(module, c, x)
+    if img is None:
+        img = _cnf_adjoint_serves(module, c, x, phi)
+        if img is None:
+            return None
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in phi)):
+            out = CnfIntegrateFn.apply((module, c, t0, t1, atol, rtol, trace_scale, with_ladj), x, *phi)
+            return (out[0], out[1]) if with_ladj else (out, None)
+    cur, l_cur, shape, _, _, stats = _cnf_run(module, img, c, x, t0, t1, atol, rtol, trace_scale, with_ladj, False)
     CNF_STATS.clear()
-    CNF_STATS.update(path="kernel", attempts=attempts, accepted=accepted, t_end=float(t))
+    CNF_STATS.update(stats)
     return cur.reshape(shape), (l_cur.reshape(shape[:-1]) if with_ladj else None)
+
+
+# ---- training: the checkpoint adjoint on zk_cnf_adjoint_step ---------------------------------------------------------------------------
+
+CNF_ADJOINT = False  # True: calls that ask for gradients integrate on the kernels too (CnfIntegrateFn); False: they take the torch-op path
+
+
+def cnf_backward_supported(features: int, context: int = 0, hidden_features=(64, 64), freqs: int = 3, activation=None) -> bool:
+    """True when zk_cnf_adjoint_step serves the field: the envelope of `cnf_supported` with every hidden width at most 64."""
+    from . import cnf_plan
+
+    if not cnf_supported(features, context, hidden_features, freqs, activation):
+        return False
+    return cnf_plan.layout_backward(int(features), int(freqs), tuple(hidden_features)) is not None
+
+
+def _cnf_adjoint_serves(module, c, x: Tensor, phi):
+    """The forward image when CnfIntegrateFn serves this call: the switch on, the conditions of `_cnf_kernel_serves` but for the gradients, a
+    field the adjoint kernel serves, and a `phi` made of the context and the field's own weights and biases."""
+    from . import cnf_plan
+
+    if not (CNF_KERNEL and CNF_ADJOINT) or not x.is_cuda:
+        return None
+    ts = [x, *module.ode.parameters(), module.freqs] + ([] if c is None else [c])
+    if any(t.dtype != torch.float32 for t in ts):
+        return None
+    sh = cnf_plan.shape_of(module)
+    if sh is None or x.dim() < 1 or x.shape[-1] != sh[0] or (sh[1] > 0) != (c is not None) or (c is not None and c.shape[-1] != sh[1]) or x.numel() == 0:
+        return None
+    own = {id(p) for lin in cnf_plan._linears(module.ode) for p in (lin.weight, lin.bias)}
+    if any(p is not c and id(p) not in own for p in phi):
+        return None
+    if cnf_plan.backward_image_of(module, x.device) is None:
+        return None
+    return cnf_plan.image_of(module, x.device)
+
+
+def cnf_adjoint_step(bimg, x: Tensor, ax: Tensor, al, pre: Tensor, t: float, dt: float, trace_scale: float, ax_next: Tensor, gpre: Tensor, gparams, work: Tensor) -> None:
+    """One reverse step on zk_cnf_adjoint_step: x [N, F] the checkpoint after the forward step (t, dt), ax [N, F], al [N] | None -> ax_next; gpre
+    [N, H1] and gparams [flat] | None are added to.  `work`: cnf_adjoint_workspace(bimg, N) floats."""
+    lay = bimg.layout
+    w = list(lay.fwd.widths) + [0, 0]
+    N, F = x.shape
+    a = _C.args("zk_cnf_adj_args_v1", features=F, freqs=lay.fwd.Q, n_hidden=len(lay.fwd.widths), width0=w[0], width1=w[1], width2=w[2], image_floats=lay.total,
+                grad_floats=lay.g_total, N=N, ldx=x.stride(0) if N > 1 else F, ld_ax=ax.stride(0) if N > 1 else F, ld_ax_next=ax_next.stride(0) if N > 1 else F,
+                ld_pre=0 if pre.dim() == 1 else (pre.stride(0) if N > 1 else w[0]), ld_gpre=gpre.stride(0) if N > 1 else w[0],
+                flat_total=0 if gparams is None else gparams.numel(), t=t, dt=dt, trace_scale=trace_scale, x=x.data_ptr(), ax=ax.data_ptr(),
+                al=None if al is None else al.data_ptr(), pre=pre.data_ptr(), image=bimg.data.data_ptr(), grad_table=bimg.table.data_ptr(), ax_next=ax_next.data_ptr(),
+                gpre=gpre.data_ptr(), gparams=None if gparams is None else gparams.data_ptr(), work=work.data_ptr())
+    _C.check(_C.lib().zk_cnf_adjoint_step(a, _stream()), "zk_cnf_adjoint_step")
+
+
+def cnf_adjoint_workspace(bimg, N: int) -> int:
+    lay = bimg.layout
+    w = list(lay.fwd.widths) + [0, 0]
+    n = ctypes.c_int64(0)
+    _C.check(_C.lib().zk_cnf_adjoint_workspace_floats(N, lay.fwd.F, lay.fwd.Q, len(lay.fwd.widths), w[0], w[1], w[2], ctypes.byref(n)), "zk_cnf_adjoint_workspace_floats")
+    return int(n.value)
+
+
+class CnfIntegrateFn(torch.autograd.Function):
+    """x(t1) (and l(t1)) on zk_cnf_step, keeping every accepted step; backward makes one zk_cnf_adjoint_step per kept step in reverse — no host
+    synchronisation — and turns gpre into the gradients of b0, the context's columns of W0 and the context.  Inputs: the settings, x, and the
+    transform's phi; gradients go to x and to exactly those tensors."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, *phi):
+        from . import cnf_plan
+
+        module, c, t0, t1, atol, rtol, trace_scale, with_ladj = cfg
+        img = cnf_plan.image_of(module, x.device)
+        cur, l_cur, shape, pre, steps, stats = _cnf_run(module, img, c, x, t0, t1, atol, rtol, trace_scale, with_ladj, True)
+        ctx.set_materialize_grads(False)
+        ctx.cfg, ctx.steps, ctx.pre, ctx.shape, ctx.x_shape, ctx.phi = cfg, steps, pre, shape, x.shape, phi
+        CNF_STATS.clear()
+        CNF_STATS.update(stats)
+        y = cur.reshape(shape)
+        return (y, l_cur.reshape(shape[:-1])) if with_ladj else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, gl=None):
+        from . import cnf_plan
+
+        module, c, _, _, _, _, trace_scale, with_ladj = ctx.cfg
+        shape, pre, phi = ctx.shape, ctx.pre, ctx.phi
+        F = shape[-1]
+        dev = pre.device
+        bimg = cnf_plan.backward_image_of(module, dev)
+        data = bimg.refresh(module)
+        N = math.prod(shape[:-1])
+        ax = torch.zeros(N, F, dtype=torch.float32, device=dev) if gy is None else gy.float().expand(shape).reshape(N, F).contiguous().clone()
+        al = None if (not with_ladj or gl is None) else gl.float().expand(shape[:-1]).reshape(N).contiguous()
+        spare = torch.empty_like(ax)
+        H0 = bimg.widths[0]
+        gpre = torch.zeros(N, H0, dtype=torch.float32, device=dev)
+        want_params = any(p is not c for p in phi)
+        gparams = torch.zeros(bimg.flat_total, dtype=torch.float32, device=dev) if want_params else None
+        work = torch.empty(max(cnf_adjoint_workspace(bimg, N), 4), dtype=torch.float32, device=dev)
+        for xs, t, dt in reversed(ctx.steps):
+            cnf_adjoint_step(bimg, xs, ax, al, pre, t, dt, trace_scale, spare, gpre, gparams, work)
+            ax, spare = spare, ax
+        del data
+        CNF_STATS["adjoint_steps"] = len(ctx.steps)
+        gx = ax.reshape(shape).sum_to_size(ctx.x_shape) if ctx.needs_input_grad[1] else None
+        lins = cnf_plan._linears(module.ode)
+        Q2, C = 2 * bimg.Q, bimg.C
+        w_off, b_off, _, _ = cnf_plan.flat_offsets(F, bimg.Q, C, bimg.widths)
+        where = {}
+        for l, lin in enumerate(lins):
+            where[id(lin.weight)] = ("w", l)
+            where[id(lin.bias)] = ("b", l)
+        out = []
+        for k, p in enumerate(phi):
+            if not ctx.needs_input_grad[2 + k]:
+                out.append(None)
+            elif p is c:
+                gc = gpre @ lins[0].weight.detach()[:, Q2 + F :]
+                out.append(gc.reshape(shape[:-1] + (C,)).sum_to_size(c.shape))
+            else:
+                kind, l = where[id(p)]
+                if kind == "b":
+                    out.append(gpre.sum(dim=0) if l == 0 else gparams[b_off[l] : b_off[l] + p.numel()].clone())
+                else:
+                    g = gparams[w_off[l] : w_off[l] + p.numel()].reshape(p.shape).clone()
+                    if l == 0 and C > 0:
+                        g[:, Q2 + F :] = gpre.t() @ c.detach().expand(shape[:-1] + (C,)).reshape(N, C)
+                    out.append(g)
+        return (None, gx, *out)

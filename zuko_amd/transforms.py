@@ -588,7 +588,9 @@ class FreeFormJacobianTransform(Transform):
 
     `kernel` = (module, c), given by `zuko_amd.flows.FFJTransform`: the field's module and the context.  A call without gradients in float32 on
     the device, `exact=True`, on a field csrc/cnf.hip serves (ops.cnf_supported) is integrated by ops.cnf_integrate — one launch per attempted
-    step.  Every other call integrates `f` in torch ops (zuko_amd.utils.odeint), with the reference's adjoint for the gradients."""
+    step.  With `ops.CNF_ADJOINT` on, a call that asks for gradients on a field csrc/cnf_backward.hip serves (ops.cnf_backward_supported) goes
+    through ops.CnfIntegrateFn: the same forward, and one zk_cnf_adjoint_step per accepted step backwards.  Every other call integrates `f` in torch
+    ops (zuko_amd.utils.odeint), with the reference's adjoint for the gradients."""
 
     domain = constraints.real_vector
     codomain = constraints.real_vector
@@ -613,7 +615,7 @@ class FreeFormJacobianTransform(Transform):
         if self.kernel is None or (with_ladj and not self.exact):
             return None
         module, c = self.kernel
-        return ops.cnf_integrate(module, c, x, float(t0), float(t1), self.atol, self.rtol, self.trace_scale, with_ladj)
+        return ops.cnf_integrate(module, c, x, float(t0), float(t1), self.atol, self.rtol, self.trace_scale, with_ladj, self.phi)
 
     def _call(self, x: Tensor) -> Tensor:
         out = self._integrate(x, self.t0, self.t1, False)
