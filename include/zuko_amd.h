@@ -187,7 +187,7 @@ int zk_linear_bf16_rqs_lanes(int64_t N, int in_features, int panels, const void*
  * ints is a silent wrong answer; a mis-named field is a compile error / a Python KeyError): set struct_size = sizeof(the struct)
  * and version = 1, fill the fields the entry point reads (listed per function), leave the rest zero.  The library rejects a
  * version it does not know, and a struct_size larger than its own, with hipErrorInvalidValue.  zk_ar_args_v1 GREW within version 1
- * (phi_packed .. base_scale were appended after gh3): a block of the earlier size — struct_size == offsetof(zk_ar_args_v1, phi_packed) or anything
+ * (phi_packed .. flow_table were appended after gh3): a block of the earlier size — struct_size == offsetof(zk_ar_args_v1, phi_packed) or anything
  * between that and sizeof — is accepted and the fields it lacks read as zero, so callers built against the earlier header keep working.
  * Behaviour change that came with the growth: zk_ar_forward_train used to ignore y / ladj / bound / slope / accumulate and now honours
  * them when y != NULL (y == NULL keeps the conditioner-only launch).  zuko_amd/_C.py builds its ctypes.Structure classes by
@@ -253,6 +253,11 @@ typedef struct zk_ar_args_v1 {
   const void* base_loc;    /* zk_ar_forward_static on an operand-split kernel, the LAST transform of a log_prob (both set, or both NULL = not terminal; a block that */
   const void* base_scale;  /* ends before them reads as not terminal): DEVICE fp32 [D] loc / scale of a diagonal-normal base.  y is then NOT written (may be NULL) and */
                            /* ladj [N] (required) receives (accumulate ? ladj : 0) + log|dy/dx| + sum_f log N(y_f; loc_f, scale_f): the flow's log-density */
+  int32_t flow_transforms; /* zk_ar_forward_static, > 0: the FLOW launch of a two-part kernel — all T = flow_transforms transforms of a composed autoregressive flow */
+  int32_t flow_bias_stride;/* in one persistent launch (see zk_ar_forward_static).  floats between two of the T bias images in `bias`: a multiple of 256, >= bias_floats */
+  int32_t flow_featmaps;   /* distinct feature maps in `featmap`, n_groups * 4 * (features per lane) words each */
+  int32_t pad2_;
+  const void* flow_table;  /* DEVICE, T rows of 8 words: wdescale0..3 of the transform's stream as float, the index of its feature map as int32, 1 as int32 when its first layer follows the kernel's alternative pattern, two unused */
 } zk_ar_args_v1;
 
 /* y, ladj of one layer on the generic tile-skipping kernel.  Reads: uni_kind, N, D, DIN, x, ldx, y, ldy, ladj, accumulate, wstream,
@@ -433,7 +438,16 @@ int zk_ar_lds_bytes(int variant, int bias_floats);
  * product launch plus the bin index used and the knots searched, as zk_ar_forward_diag (the f32-instruction static kernels return
  * hipErrorInvalidValue for it: they are bit-identical to zk_ar_forward, whose twin serves); base_loc + base_scale (both or neither): the
  * TERMINAL launch of an operand-split kernel for the last transform of a log_prob, see the fields (not with bin_out; the f32-instruction
- * static kernels return hipErrorInvalidValue for it). */
+ * static kernels return hipErrorInvalidValue for it).
+ * flow_transforms = T > 0: the FLOW launch of a generated TWO-PART kernel (csrc/fused_ar_half_impl.h: arhf_kernel; `launcher` is then the address of the
+ * flow unit's `zk_arhf_launch`: zuko_amd/static_ar.py, ARHF).  A workgroup carries its 128-row tile through the T transforms of a composed autoregressive flow before it moves on: x is
+ * read once, y and ladj (the sum of the T log-determinants) are written once, or, with base_loc / base_scale, only the flow's log-density.  The
+ * transforms share one conditioner architecture (one generated kernel serves them all), take no context (DIN == D) and differ in weights and feature
+ * order.  The caller owns every buffer: wstream — the T two-part streams (zk_gather_split_f16) back to back, n_chunks whole chunks each; bias — T
+ * bias images, flow_bias_stride floats apart; featmap — the flow_featmaps distinct feature maps; flow_table.  wdescale0..3, accumulate, rev, bin_out
+ * and knots_out must be zero.  Results are bitwise those of T calls without the flow fields (accumulate from the second on, the last one terminal when
+ * a base is given).  hipErrorInvalidValue when the kernel's shape has no flow launch (three ring slots, rows not staged in LDS, one chunk per pass) or
+ * the tables do not fit the LDS: the caller keeps the T launches.  No allocation is made. */
 int zk_ar_forward_static(const zk_ar_args_v1* args, void* stream);
 /* Conditioner-only launch of a generated static-shape kernel for the training forward (zuko_amd/train.py): phi [N, D * total] =
  * net(x) in module order (what the last MaskedLinear of zuko/nn.py:221-318 returns) and the hidden activations h_l [N, width_l]

@@ -579,6 +579,32 @@ int zk_ar_forward_diag(const zk_ar_args_v1* args, void* stream) {
   return ar_launch_v1(part, false, p, stream);
 }
 
+// The FLOW launch of zk_ar_forward_static (flow_transforms > 0): all T transforms of a composed autoregressive flow in one launch of a generated two-part
+// kernel (fused_ar_half_impl.h: arhf_kernel); `launcher` is the address of the unit's `zk_arhf_launch`.  The kernel checks the shape, the tables' sizes and
+// the LDS it needs, and declines with hipErrorInvalidValue what it is not built for; nothing is allocated here.
+static int ar_flow_launch(const zk_ar_args_v1* p, void* stream) {
+  if (p->N < 0 || p->N > 0x7fffffff || p->D < 4 || p->D > 256 || p->D % 4 || p->DIN != p->D || p->ldx % 4 || ((uintptr_t)p->x % 16) || p->n_chunks < 1 || p->n_layers < 2) return ZK_EINVAL;
+  if (p->n_groups * 8 > ArLds::FMAP_WORDS || (p->base_loc != nullptr) != (p->base_scale != nullptr) || !p->ladj || p->accumulate || p->rev || p->bin_out || p->knots_out) return ZK_EINVAL;
+  if (p->wdescale0 != 0.0 || p->wdescale1 != 0.0 || p->wdescale2 != 0.0 || p->wdescale3 != 0.0) return ZK_EINVAL;  // (per transform: flow_table)
+  if (p->N == 0) return 0;
+  ArArgs a{};
+  a.N = p->N; a.D = p->D; a.DIN = p->D;
+  a.x = (const float*)p->x; a.ldx = p->ldx;
+  a.y = (float*)p->y; a.ldy = p->ldy; a.ladj = (float*)p->ladj;
+  a.stream = (const float*)p->wstream;
+  a.L = p->n_layers; a.NG = p->n_groups; a.n_chunks = p->n_chunks; a.act = p->act; a.bias_floats = p->bias_floats;
+  a.bound = (float)p->bound; a.ls = (float)log(p->slope);
+  a.lc = rqs_lean_const(p->bound, log(p->slope));
+  a.g0 = 0; a.g1 = p->n_groups;
+  for (int l = 0; l < 8; ++l) a.olim[l] = 3;
+  a.eps = 1e-6f;
+  a.base_loc = (const float*)p->base_loc; a.base_scale = (const float*)p->base_scale;
+  ArhFlow f{};
+  f.T = p->flow_transforms; f.bias_stride = p->flow_bias_stride; f.n_fmaps = p->flow_featmaps;
+  f.bias = (const float*)p->bias; f.featmap = p->featmap; f.table = (const float*)p->flow_table;
+  return ((arhf_launch_fn)p->launcher)(&a, &f, ARS_ABI, (int)sizeof(ArArgs), (int)sizeof(ArhFlow), stream);
+}
+
 // zk_ar_forward through a generated static-shape kernel (zuko_amd/static_ar.py): `launcher` is the address of the `zk_ars_launch`
 // symbol of the kernel's shared object, `rev` selects the alternative first-layer pattern the kernel was generated with (descending
 // feature order).  wstream is the PER-TILE stream of the plan (ArPlan.fine_gather), n_chunks its length.  The kernel re-checks
@@ -586,6 +612,7 @@ int zk_ar_forward_diag(const zk_ar_args_v1* args, void* stream) {
 int zk_ar_forward_static(const zk_ar_args_v1* args, void* stream) {
   zk_ar_args_v1 args_norm_;
   if (!AR_ARGS_OK(args) || !args->launcher) return ZK_EINVAL;
+  if (args->flow_transforms != 0) return args->flow_transforms > 0 ? ar_flow_launch(args, stream) : ZK_EINVAL;
   ArPartial part;
   part.static_fn = args->launcher; part.rev = args->rev;
   part.gl_nodes01 = args->gl_nodes01; part.gl_weights01 = args->gl_weights01; part.eps = args->eps;

@@ -165,7 +165,7 @@ template <int WAVES, int CH, int NR> struct ArhRing : ArRingS<WAVES, CH, NR> {
 // chunk, B stands behind the chunk's last image and drains the LDS queue too (once per tile).  XV: as ArhRing's — vector-memory loads
 // younger than the pieces waited for (the next tile's rows: arh_body's XPOS); every other B waits for vmcnt(0), a whole chunk after the
 // request (the running log-derivative's load and a tile's stores, if still in flight, are sat out at the tile's first B).
-template <int WAVES, int CH, int IMAGES, int BPOS> struct ArhRing4 {
+template <int WAVES, int CH, int IMAGES, int BPOS, bool FLOW = false> struct ArhRing4 {
   static constexpr int NR = 4, PER = CH / WAVES, PIVOT = PER > 4 ? 4 : 0, CHB = CH * AR_TF * 4, NCH = (IMAGES + CH - 1) / CH;
   static_assert(PER * WAVES == CH && PER <= 6 && BPOS % 2 == 0 && BPOS >= 2 * (ARH_LOOK + 1) && BPOS + 1 < CH && CH % 2 == 0 && IMAGES % 2 == 0, "ring geometry");
   static constexpr int trigger(int c) {  // the image of chunk c behind whose request B stands (static_ar.half_trigger)
@@ -185,6 +185,18 @@ template <int WAVES, int CH, int IMAGES, int BPOS> struct ArhRing4 {
   unsigned lane_off;   // LDS byte address of the ring + lane * 16
   unsigned lane16;     // lane * 16
   unsigned cur_off;    // lane_off + read_off
+  // FLOW (arhf_kernel: the passes of T transforms follow each other on one stream): whether the pass in progress requests the next tile's rows
+  // (its XV boundary then leaves them in flight; in every other pass that boundary waits for vmcnt(0) like the rest), and the NEXT pass's bias
+  // image — bias_n pieces of 1 KiB from bias_src to bias_dst (LDS), requested behind the barrier of the pass's last chunk but one, so that the
+  // last chunk's barrier (which waits for everything but the rows) publishes it before the next pass reads its first bias tile
+  bool rows_in_flight;
+  const char* bias_src;
+  char* bias_dst;
+  int bias_n, wave_id;
+  __device__ __forceinline__ void bias_request() {
+    for (int p = wave_id; p < bias_n; p += WAVES)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bias_src + p * 1024 + (size_t)lane16), (__attribute__((address_space(3))) void*)(bias_dst + p * 1024), 16, 0, 0);
+  }
   __device__ __forceinline__ void start(float* lds, const float* stream, int n_chunks, int wave, int lane) {
     const int b0 = wave * PER + PIVOT;
     gsrc = reinterpret_cast<const char*>(stream + b0 * AR_TF);
@@ -192,6 +204,7 @@ template <int WAVES, int CH, int IMAGES, int BPOS> struct ArhRing4 {
     goff = 0; gend = (unsigned)n_chunks * CHB; fill_off = 0;
     lane16 = (unsigned)lane * 16;
     lane_off = (unsigned)(size_t)((__attribute__((address_space(3))) float*)lds) + lane16;
+    if constexpr (FLOW) { wave_id = wave; rows_in_flight = false; bias_n = 0; }
 #pragma unroll
     for (int i = 0; i < NR - 1; ++i) issue();
     read_off = (NR - 1) * CHB;  // (the first read, position 0, moves on to slot 0)
@@ -209,9 +222,17 @@ template <int WAVES, int CH, int IMAGES, int BPOS> struct ArhRing4 {
     goff = (goff + CHB == gend) ? 0 : goff + CHB;
     fill_off = (fill_off + CHB == NR * CHB) ? 0 : fill_off + CHB;
   }
-  template <int XV, bool DRAIN> __device__ __forceinline__ void boundary() {
+  template <int XV, bool DRAIN> __device__ __forceinline__ void wait() {
     if constexpr (DRAIN) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(XV) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XV) : "memory");
+  }
+  template <int XV, bool DRAIN> __device__ __forceinline__ void boundary() {
+    if constexpr (FLOW && XV != 0) {
+      if (rows_in_flight) wait<XV, DRAIN>();
+      else wait<0, DRAIN>();
+    } else {
+      wait<XV, DRAIN>();
+    }
     if (ARX_ABL != 4) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     issue();
@@ -231,12 +252,21 @@ template <int WAVES, int CH, int IMAGES, int BPOS> struct ArhRing4 {
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(cur_off), "n"((S % CH) * AR_TF * 4));
     }
     if constexpr (S == trigger(S / CH)) boundary<XV, (S % CH != BPOS + 1)>();
+    if constexpr (FLOW && NCH >= 2) {
+      if constexpr (S == trigger(NCH - 2)) bias_request();
+    }
     return v;
   }
 };
 
 // one hidden layer: out = fma(W' in', d, bias) over the blocks of the generated pattern (W', in': the scaled operands; d = 2^-(ew + ea))
-template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d) {
+template <class S, int L, bool ALT> constexpr int arh_ip(int s) {  // the in pair of block s of layer L
+  if constexpr (ALT) return S::B_IP_ALT[s];
+  else return ArxPat<S>::ip(L, s);
+}
+// (ALT, the flow kernel's first layer only: the blocks take the in pairs S::B_IP_ALT names — the pattern of the flow's OTHER feature order, which
+//  differs from this one in nothing else)
+template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d) {
   typedef ArxPat<S> P;
   constexpr int NB = S::NB[L], BASE = S::BASE[L], HTL = S::HT[L];
   ars_for<HTL>([&](auto t_) ARS_ALWAYS_INLINE {
@@ -254,7 +284,8 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
       ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { a[b][p] = ring.template read<BASE + 2 * b + decltype(p)::value>(); });
     });
     ars_for<NB>([&](auto s_) ARS_ALWAYS_INLINE {
-      constexpr int s = s_, ot = P::ot(L, s), ip = P::ip(L, s), cur = s % (LOOK + 1);
+      constexpr int s = s_, ot = P::ot(L, s), cur = s % (LOOK + 1);
+      constexpr int ip = arh_ip<S, L, ALT>(s);
       constexpr bool first_of_tile = (s == 0 || P::ot(L, s - 1) != ot), last_of_tile = (s + 1 == NB || P::ot(L, s + 1) != ot);
       if constexpr (first_of_tile) acc = f32x4{0.f, 0.f, 0.f, 0.f};
       if constexpr (last_of_tile) bs = arx_lds_raw<ot * 64>(bias_addr);
@@ -285,10 +316,18 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
   }
 }
 
-template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden_stack(Ring& ring, const float* bias_lds, int q, ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], const ArArgs& a,
-                                                                                       float& inv_s, float& poison) {
+// (wd: the per-layer descale factors 2^-ew_l of the stream being read — ArArgs::wdescale, or the transform's row of the flow kernel's table)
+// HAS_ALT / alt (flow kernel): this pass's first layer follows S::B_IP_ALT
+template <class S, int L, class Ring, bool HAS_ALT = false> __device__ __forceinline__ void arh_hidden_stack(Ring& ring, const float* bias_lds, int q, ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], const float* wd,
+                                                                                                         float& inv_s, float& poison, bool alt = false) {
   if constexpr (L < S::NH) {
-    arh_hidden<S, L>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, a.wdescale[L] * inv_s);
+    if constexpr (HAS_ALT && L == 0) {
+      static_assert(S::BASE[0] == 0, "B_IP_ALT lists the first layer's blocks");
+      if (alt) arh_hidden<S, L, Ring, true>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s);
+      else arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s);
+    } else {
+      arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s);
+    }
     constexpr int HTL = S::HT[L];
     float amax = 0.f;
     if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
@@ -328,8 +367,204 @@ template <class S, int L, class Ring> __device__ __forceinline__ void arh_hidden
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int p = 0; p < (HTL + 1) / 2; ++p) arh_split(out[2 * p], 2 * p + 1 < HTL ? out[2 * p + 1] : zero, s, in[p]);
-    arh_hidden_stack<S, L + 1, Ring>(ring, bias_lds, q, in, out, a, inv_s, poison);
+    arh_hidden_stack<S, L + 1, Ring, HAS_ALT>(ring, bias_lds, q, in, out, wd, inv_s, poison, alt);
   }
+}
+
+// One PASS of a row tile through the conditioner and the univariate map: the body of arh_body's tile loop, and of the flow kernel's loop over the
+// transforms of a tile (FLOW; arhf_body).  wd: the stream's per-layer descale factors.  FLOW differs at the edges only: the rows come from the LDS row
+// tile (the tile's x in the first pass, the y of the pass before in the others) and y goes back to it; the next tile's rows are requested in the tile's
+// last pass; the log-derivative is added to `total` (a register) and stored, with the rows, behind the last pass — or, term, the last pass ends in
+// the base's log-density and no rows are written.  The matrix part and the arithmetic of the epilogue are the same lines for both.
+template <typename Uni> __device__ __forceinline__ void arh_flow_epilogue(float (&p)[4 * Uni::NT], const ArArgs& a, const int (&fid)[Uni::FPL], const float (&xin)[Uni::FPL], float poison, float* xr,
+                                                                          const float* base, int D, bool term, float& lacc) {
+  constexpr int FPL = Uni::FPL, TOTAL = Uni::TOTAL;
+#pragma unroll
+  for (int fi = 0; fi < FPL; ++fi) Uni::template poison<false>(p, fi * TOTAL, poison);
+  auto ld = [&](int i) { return p[i]; };
+#pragma unroll
+  for (int fi = 0; fi < FPL; ++fi) {
+    const int f = fid[fi];
+    if (f >= 0) {
+      float yv, lj;
+      Uni::fwd(ld, fi * TOTAL, a, xin[fi], yv, lj);
+      lacc += lj;
+      if (term) {  // (ar_uni_epilogue's TERM branch with the base's table entries read here: ArLds::stage_base)
+        const float df = yv - base[f];
+        lacc += __builtin_fmaf(-(df * df), base[D + f], base[2 * D + f]);
+      } else {
+        xr[f] = yv;
+      }
+    }
+  }
+}
+
+template <class S, typename Uni, bool DIAG, bool TERM, bool FLOW, class Ring, class XReq, class Fids>
+__device__ __forceinline__ void arh_pass(const ArArgs& a, Ring& ring, XReq& x_request, f32x4 (&xnext)[S::NIT], float* bias_lds, const Fids& fids, float* xr, const float* base, const ArLane& ln,
+                                         int64_t tile, const float* wd, bool first, bool last, bool term, float& total, bool alt = false) {
+  constexpr bool RING4 = S::NR == 4;
+  static_assert(!FLOW || (RING4 && S::XLDS && S::DIN == S::D && !DIAG && !TERM), "flow pass: four-slot ring, rows in LDS, no context columns");
+  constexpr int NT = Uni::NT, FPL = Uni::FPL, WAVES = S::WAVES;
+  constexpr int NG = S::NG;
+  constexpr int NSTEP = S::GOFF[NG];  // (group, in pair) steps of the last layer, NT blocks each
+  constexpr bool XLDS = S::XLDS;
+  const int wave = ln.wave, j = ln.j, q = ln.q;
+  const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
+  const unsigned bias_last_addr = arx_lds_addr(bias_last + 4 * q);
+  if constexpr (FLOW) {  // (the row tile was written by this wavefront's other lanes: ar_rows_in, or the pass before)
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+  }
+  const int64_t n = tile * (16 * WAVES) + wave * 16 + j;
+  const bool live = n < a.N;
+  const int64_t nc = live ? n : a.N - 1;
+  const float* xrow = a.x + nc * a.ldx;
+
+  ArhB in[S::TMAX / 2];
+  f32x4 out[S::TMAX];
+  float poison;
+  float inv_s;  // 2^-ea of the operands `in` currently holds
+  {
+    f32x4 xin[S::NIT + 1];
+#pragma unroll
+    for (int it = 0; it < S::NIT; ++it) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (FLOW) {  // (the row tile holds them: the tile's rows, or the y of the transform before this one)
+        if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = *reinterpret_cast<const f32x4*>(xr + it * 16 + 4 * q);
+      } else if (ARH_PREFETCH) {
+        if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = xnext[it];
+      } else {
+        if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = *reinterpret_cast<const f32x4*>(xrow + it * 16 + 4 * q);
+      }
+      xin[it] = v;
+    }
+    xin[S::NIT] = f32x4{0.f, 0.f, 0.f, 0.f};
+    poison = ar_poison_of<S::NIT>(xin);
+    float amax = 0.f;
+#pragma unroll
+    for (int it = 0; it < S::NIT; ++it)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(xin[it][r]));
+    if constexpr (XLDS && !FLOW) ar_rows_in<S::D>(xr, q, xin);
+    float s;
+    arh_scale(amax, s, inv_s);
+    if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
+      if (!(amax < ARH_AMAX_OVERFLOW)) poison = __builtin_nanf("");  // (finite, but its f16 parts are not: the one-instruction ReLU would flatten the NaN they make)
+    }
+#pragma unroll
+    for (int p = 0; p < (S::NIT + 1) / 2; ++p) arh_split(xin[2 * p], xin[2 * p + 1], s, in[p]);
+  }
+
+  float ladj_in = 0.f;  // the running log-derivative this launch adds to: requested HERE, a whole tile ahead of the add
+  if constexpr (!FLOW) {
+    if (ARH_PREFETCH && a.ladj && a.accumulate && live && q == 0) ladj_in = a.ladj[n];
+  }
+
+  // ---- hidden layers ---------------------------------------------------------------------------------------------
+  if constexpr (FLOW) arh_hidden_stack<S, 0, Ring, S::FLOW_ALT>(ring, bias_lds, q, in, out, wd, inv_s, poison, alt);
+  else arh_hidden_stack<S, 0, Ring>(ring, bias_lds, q, in, out, wd, inv_s, poison);
+
+  // ---- last layer + univariate transform, one group of 4 * FPL features at a time --------------------------------
+  const float dl = wd[S::NH] * inv_s;
+  float lacc = 0.f;
+  constexpr int NBL = NSTEP * NT;                          // blocks of the last layer
+  constexpr int LOOKL = ARH_LOOK < NBL ? ARH_LOOK : NBL;
+  f32x4 w[LOOKL + 1][2];
+  // the next tile of this workgroup: its rows travel during the last layer.  The LAST tile requests its own rows again, so that the
+  // count of loads in flight does not depend on the tile; XPOS is the one advance of the ring that finds them younger than its chunk
+  // (four-slot ring: the first barrier behind the last layer's first request)
+  constexpr int XPOS = []() constexpr {
+    if constexpr (!ARH_PREFETCH) return -1;
+    else if constexpr (RING4) return Ring::first_trigger_from(S::LAST_BASE);
+    else return (S::LAST_BASE + S::CH - 1) / S::CH * S::CH;
+  }();
+  if constexpr (FLOW) {
+    // the rows travel during the tile's LAST pass only; every other pass gives xnext a fresh (undefined) value instead, so that the registers
+    // are free from the tile's start to here
+    asm volatile("" ::: "memory");
+    if (last) {
+      x_request(tile + gridDim.x < a.n_tiles ? tile + gridDim.x : tile, xnext);
+    } else {
+#pragma unroll
+      for (int it = 0; it < S::NIT; ++it) asm("" : "=v"(xnext[it]));
+    }
+    ring.rows_in_flight = last;
+    asm volatile("" ::: "memory");
+  } else if (ARH_PREFETCH) {
+    asm volatile("" ::: "memory");
+    x_request(tile + gridDim.x < a.n_tiles ? tile + gridDim.x : tile, xnext);
+    asm volatile("" ::: "memory");
+  }
+#define ARH_READ_LAST(POS) ring.template read<(POS), ((POS) == XPOS ? S::NIT : 0)>()
+  ars_for<LOOKL>([&](auto b_) ARS_ALWAYS_INLINE {
+    constexpr int b = b_;
+    ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[b][p] = ARH_READ_LAST(S::LAST_BASE + 2 * b + decltype(p)::value); });
+  });
+  ars_for<NG>([&](auto g_) ARS_ALWAYS_INLINE {
+    constexpr int g = g_, ST0 = S::GOFF[g], GN = S::GOFF[g + 1] - S::GOFF[g];
+    int fid[FPL];
+    float xin[FPL];
+    fids.template fetch<XLDS>(g, xr, xrow, fid, xin);
+    float bv[3 * FPL];
+    if constexpr (TERM && !FLOW) fids.fetch_base(fid, base, S::D, bv);
+    f32x4 acc[NT], bs[NT];  // the group's bias tiles: raw reads in front of the look-ahead request of the group's LAST block, whose counted wait settles them
+    if constexpr (GN == 0) {
+      const float* bg = bias_last + (g * NT) * 16 + 4 * q;
+      ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { bs[t] = *reinterpret_cast<const f32x4*>(bg + t * 16); });
+    }
+    ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+    ars_for<GN>([&](auto i_) ARS_ALWAYS_INLINE {
+      constexpr int st = ST0 + decltype(i_)::value, ip = S::G_IP[st];
+      ars_for<NT>([&](auto t_) ARS_ALWAYS_INLINE {
+        constexpr int t = t_, blk = st * NT + t, cur = blk % (LOOKL + 1);
+        constexpr bool last_of_group = (decltype(i_)::value == GN - 1 && t == NT - 1);
+        if constexpr (last_of_group) {
+          ars_for<NT>([&](auto u) ARS_ALWAYS_INLINE { bs[u] = arx_lds_raw<(g * NT + decltype(u)::value) * 64>(bias_last_addr); });
+        }
+        if constexpr (blk + LOOKL < NBL) {
+          constexpr int nx = (blk + LOOKL) % (LOOKL + 1);
+          ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[nx][p] = ARH_READ_LAST(S::LAST_BASE + 2 * (blk + LOOKL) + decltype(p)::value); });
+        }
+        constexpr int ahead = (blk + LOOKL < NBL ? LOOKL : NBL - 1 - blk);
+        if constexpr (last_of_group) arh_settle<(blk + LOOKL < NBL ? 2 : 0)>(w[cur][0], w[cur][1]);
+        else arh_settle<2 * ahead>(w[cur][0], w[cur][1]);
+        if constexpr (last_of_group) {  // (the bias tiles are older than this step's request: the same wait has settled them)
+#pragma unroll
+          for (int u = 0; u < NT; ++u) arh_touch(bs[u]);
+        }
+        if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+        arh_block(w[cur], in[ip], acc[t]);
+        if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+      });
+    });
+    float p[4 * NT];
+    ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        p[4 * t + r] = __builtin_fmaf(acc[t][r], dl, bs[t][r]);
+        // one fma per parameter, written where the spline wants it: left alone, the vectoriser pairs parameter j with parameter K + j (the
+        // spline's two axes) in FRONT of the fma and gathers accumulator and bias elements into register pairs for it (3 v_mov per pair)
+        if (ARH_POISON_ONE) asm("" : "+v"(p[4 * t + r]));
+      }
+    });
+    if constexpr (FLOW) arh_flow_epilogue<Uni>(p, a, fid, xin, poison, xr, base, S::D, last && term, lacc);
+    else ar_uni_epilogue<Uni, DIAG, XLDS, true, TERM>(p, a, fid, xin, poison, xr, n, live, S::D, lacc, bv);
+  });
+#undef ARH_READ_LAST
+  if constexpr (FLOW) {
+    // the transform's log-derivative joins the running sum as a launch of its own would add it to the buffer: summed over the sample's four lanes first
+    lacc += __shfl_xor(lacc, 16, 64);
+    lacc += __shfl_xor(lacc, 32, 64);
+    total = first ? lacc : total + lacc;
+    if (last) {
+      if (live && q == 0) a.ladj[n] = total;
+      if (!term) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
+    }
+    return;
+  }
+  if (ARH_PREFETCH) ar_ladj_store<true>(a, lacc, n, live, q, ladj_in);  // in FRONT of the y rows: the wait for ladj_in (requested a tile ago) must not find stores it would have to sit out
+  if constexpr (XLDS && !TERM) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
+  if (!ARH_PREFETCH) ar_ladj_store(a, lacc, n, live, q);
 }
 
 // The kernel's body.  DIAG: the diagnostic twin of the product launch (also writes the bin index the spline USED and the knots it searched), as
@@ -339,11 +574,10 @@ template <class S, typename Uni, bool DIAG, bool TERM> __device__ __forceinline_
   constexpr bool RING4 = S::NR == 4;
   typedef std::conditional_t<RING4, ArhRing4<S::WAVES, S::CH, S::IMAGES, S::BPOS>, ArhRing<S::WAVES, S::CH, S::NR>> Ring;
   static_assert(S::WAVES == 8 && (S::NR == 3 || S::NR == 4) && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::OCC == 2, "two-part split kernels: widths <= 256, two wavefronts per SIMD");
-  constexpr int NT = Uni::NT, FPL = Uni::FPL, TOTAL = Uni::TOTAL, WAVES = S::WAVES;
+  constexpr int NT = Uni::NT, FPL = Uni::FPL, WAVES = S::WAVES;
   constexpr int NG = S::NG;
   constexpr int NSTEP = S::GOFF[NG];  // (group, in pair) steps of the last layer, NT blocks each
   static_assert(S::IMAGES == S::LAST_BASE + 2 * NSTEP * NT && (S::IMAGES + S::CH - 1) / S::CH == S::NCHUNK, "stream length");
-  constexpr bool XLDS = S::XLDS;
   const ArLane ln;
   const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
 
@@ -382,133 +616,11 @@ template <class S, typename Uni, bool DIAG, bool TERM> __device__ __forceinline_
   float* const base = ArLds::base(fmap_lds, NG * 4 * FPL);
   if constexpr (TERM) ArLds::stage_base<64 * WAVES>(a, tid, base, S::D);
   ArLds::stage<64 * WAVES>(a, tid, bias_lds, fmap_lds, NG * 4 * FPL);
-  const float* bias_last = bias_lds + S::NH * S::BIAS_STRIDE;
-  const unsigned bias_last_addr = arx_lds_addr(bias_last + 4 * q);
   const ArFids<NG, FPL, (NG * FPL <= 32)> fids(fmap_lds, q);
 
-  for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-    const int64_t n = tile * (16 * WAVES) + wave * 16 + j;
-    const bool live = n < a.N;
-    const int64_t nc = live ? n : a.N - 1;
-    const float* xrow = a.x + nc * a.ldx;
-
-    ArhB in[S::TMAX / 2];
-    f32x4 out[S::TMAX];
-    float poison;
-    float inv_s;  // 2^-ea of the operands `in` currently holds
-    {
-      f32x4 xin[S::NIT + 1];
-#pragma unroll
-      for (int it = 0; it < S::NIT; ++it) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (ARH_PREFETCH) {
-          if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = xnext[it];
-        } else {
-          if ((it + 1) * 16 <= S::DIN || it * 16 + 4 * q < S::DIN) v = *reinterpret_cast<const f32x4*>(xrow + it * 16 + 4 * q);
-        }
-        xin[it] = v;
-      }
-      xin[S::NIT] = f32x4{0.f, 0.f, 0.f, 0.f};
-      poison = ar_poison_of<S::NIT>(xin);
-      float amax = 0.f;
-#pragma unroll
-      for (int it = 0; it < S::NIT; ++it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(xin[it][r]));
-      if constexpr (XLDS) ar_rows_in<S::D>(xr, q, xin);
-      float s;
-      arh_scale(amax, s, inv_s);
-      if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
-        if (!(amax < ARH_AMAX_OVERFLOW)) poison = __builtin_nanf("");  // (finite, but its f16 parts are not: the one-instruction ReLU would flatten the NaN they make)
-      }
-#pragma unroll
-      for (int p = 0; p < (S::NIT + 1) / 2; ++p) arh_split(xin[2 * p], xin[2 * p + 1], s, in[p]);
-    }
-
-    float ladj_in = 0.f;  // the running log-derivative this launch adds to: requested HERE, a whole tile ahead of the add
-    if (ARH_PREFETCH && a.ladj && a.accumulate && live && q == 0) ladj_in = a.ladj[n];
-
-    // ---- hidden layers ---------------------------------------------------------------------------------------------
-    arh_hidden_stack<S, 0, Ring>(ring, bias_lds, q, in, out, a, inv_s, poison);
-
-    // ---- last layer + univariate transform, one group of 4 * FPL features at a time --------------------------------
-    const float dl = a.wdescale[S::NH] * inv_s;
-    float lacc = 0.f;
-    constexpr int NBL = NSTEP * NT;                          // blocks of the last layer
-    constexpr int LOOKL = ARH_LOOK < NBL ? ARH_LOOK : NBL;
-    f32x4 w[LOOKL + 1][2];
-    // the next tile of this workgroup: its rows travel during the last layer.  The LAST tile requests its own rows again, so that the
-    // count of loads in flight does not depend on the tile; XPOS is the one advance of the ring that finds them younger than its chunk
-    // (four-slot ring: the first barrier behind the last layer's first request)
-    constexpr int XPOS = []() constexpr {
-      if constexpr (!ARH_PREFETCH) return -1;
-      else if constexpr (RING4) return Ring::first_trigger_from(S::LAST_BASE);
-      else return (S::LAST_BASE + S::CH - 1) / S::CH * S::CH;
-    }();
-    if (ARH_PREFETCH) {
-      asm volatile("" ::: "memory");
-      x_request(tile + gridDim.x < a.n_tiles ? tile + gridDim.x : tile, xnext);
-      asm volatile("" ::: "memory");
-    }
-#define ARH_READ_LAST(POS) ring.template read<(POS), ((POS) == XPOS ? S::NIT : 0)>()
-    ars_for<LOOKL>([&](auto b_) ARS_ALWAYS_INLINE {
-      constexpr int b = b_;
-      ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[b][p] = ARH_READ_LAST(S::LAST_BASE + 2 * b + decltype(p)::value); });
-    });
-    ars_for<NG>([&](auto g_) ARS_ALWAYS_INLINE {
-      constexpr int g = g_, ST0 = S::GOFF[g], GN = S::GOFF[g + 1] - S::GOFF[g];
-      int fid[FPL];
-      float xin[FPL];
-      fids.template fetch<XLDS>(g, xr, xrow, fid, xin);
-      float bv[3 * FPL];
-      if constexpr (TERM) fids.fetch_base(fid, base, S::D, bv);
-      f32x4 acc[NT], bs[NT];  // the group's bias tiles: raw reads in front of the look-ahead request of the group's LAST block, whose counted wait settles them
-      if constexpr (GN == 0) {
-        const float* bg = bias_last + (g * NT) * 16 + 4 * q;
-        ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { bs[t] = *reinterpret_cast<const f32x4*>(bg + t * 16); });
-      }
-      ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; });
-      ars_for<GN>([&](auto i_) ARS_ALWAYS_INLINE {
-        constexpr int st = ST0 + decltype(i_)::value, ip = S::G_IP[st];
-        ars_for<NT>([&](auto t_) ARS_ALWAYS_INLINE {
-          constexpr int t = t_, blk = st * NT + t, cur = blk % (LOOKL + 1);
-          constexpr bool last_of_group = (decltype(i_)::value == GN - 1 && t == NT - 1);
-          if constexpr (last_of_group) {
-            ars_for<NT>([&](auto u) ARS_ALWAYS_INLINE { bs[u] = arx_lds_raw<(g * NT + decltype(u)::value) * 64>(bias_last_addr); });
-          }
-          if constexpr (blk + LOOKL < NBL) {
-            constexpr int nx = (blk + LOOKL) % (LOOKL + 1);
-            ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[nx][p] = ARH_READ_LAST(S::LAST_BASE + 2 * (blk + LOOKL) + decltype(p)::value); });
-          }
-          constexpr int ahead = (blk + LOOKL < NBL ? LOOKL : NBL - 1 - blk);
-          if constexpr (last_of_group) arh_settle<(blk + LOOKL < NBL ? 2 : 0)>(w[cur][0], w[cur][1]);
-          else arh_settle<2 * ahead>(w[cur][0], w[cur][1]);
-          if constexpr (last_of_group) {  // (the bias tiles are older than this step's request: the same wait has settled them)
-#pragma unroll
-            for (int u = 0; u < NT; ++u) arh_touch(bs[u]);
-          }
-          if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
-          arh_block(w[cur], in[ip], acc[t]);
-          if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
-        });
-      });
-      float p[4 * NT];
-      ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          p[4 * t + r] = __builtin_fmaf(acc[t][r], dl, bs[t][r]);
-          // one fma per parameter, written where the spline wants it: left alone, the vectoriser pairs parameter j with parameter K + j (the
-          // spline's two axes) in FRONT of the fma and gathers accumulator and bias elements into register pairs for it (3 v_mov per pair)
-          if (ARH_POISON_ONE) asm("" : "+v"(p[4 * t + r]));
-        }
-      });
-      ar_uni_epilogue<Uni, DIAG, XLDS, true, TERM>(p, a, fid, xin, poison, xr, n, live, S::D, lacc, bv);
-    });
-#undef ARH_READ_LAST
-    if (ARH_PREFETCH) ar_ladj_store<true>(a, lacc, n, live, q, ladj_in);  // in FRONT of the y rows: the wait for ladj_in (requested a tile ago) must not find stores it would have to sit out
-    if constexpr (XLDS && !TERM) ar_rows_out<S::D>(xr, q, a.y + n * a.ldy, live);
-    if (!ARH_PREFETCH) ar_ladj_store(a, lacc, n, live, q);
-  }
+  float unused = 0.f;
+  for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x)
+    arh_pass<S, Uni, DIAG, TERM, false>(a, ring, x_request, xnext, bias_lds, fids, xr, base, ln, tile, a.wdescale, true, true, TERM, unused);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
 
@@ -542,6 +654,107 @@ template <class S, typename Uni> static int arh_launch(const ArArgs* in, int abi
   }
   if (!fn) return ZK_EINVAL;
   return ar_launch_dyn_lds(fn, 256, 64 * S::WAVES, lds, a, stream);
+}
+
+// ---- the FLOW launch: a workgroup carries its row tile through ALL T transforms of a composed autoregressive flow --------------------------------
+// The transforms share one Shape (the same conditioner architecture; their feature orders and weights differ).  What differs per transform comes
+// from the flow's own device buffers (zk_ar_common.h: ArhFlow; zuko_amd/fused.py: FusedFlow):
+//   stream    (ArArgs::stream) the T transforms' streams back to back, S::NCHUNK whole chunks each: ONE ring over T NCHUNK chunks, whose look-ahead
+//             crosses a transform boundary like any chunk boundary
+//   bias      T bias images, bias_stride floats apart (whole 1 KiB pieces).  Two LDS buffers: a pass reads one while the ring requests the next
+//             transform's into the other (ArhRing4::bias_request)
+//   featmap   the n_fmaps DISTINCT feature maps of the flow (a flow that alternates two feature orders has two), all resident in LDS
+//   table     per transform 8 words: the four descale factors of its stream (float), the index of its feature map (int), whether its first layer
+//             follows the Shape's alternative in pairs (int; S::FLOW_ALT, S::B_IP_ALT: a flow that alternates two feature orders has two first-layer
+//             patterns and nothing else that differs — one pass body serves both but for the 24-block first layer), 2 unused
+// x is read and y, ladj (or, term, the log-density) are written once per tile; between two transforms the rows stay in the LDS row tile and the running
+// log-derivative in a register.  Every transform's arithmetic is arh_pass's: the results are bitwise those of T launches of arh_kernel / arht_kernel.
+template <class S, typename Uni> __device__ __forceinline__ void arhf_body(const ArArgs& a, const ArhFlow& f) {
+  typedef ArhRing4<S::WAVES, S::CH, S::IMAGES, S::BPOS, true> Ring;
+  static_assert(S::WAVES == 8 && S::NR == 4 && S::TMAX <= 16 && S::TMAX % 2 == 0 && S::OCC == 2 && S::NCHUNK >= 2, "flow kernel: the four-slot two-part geometry, two chunks or more per pass");
+  constexpr int NT = Uni::NT, FPL = Uni::FPL, WAVES = S::WAVES, NG = S::NG, NFM = NG * 4 * FPL;
+  static_assert(S::IMAGES == S::LAST_BASE + 2 * S::GOFF[NG] * NT && (S::IMAGES + S::CH - 1) / S::CH == S::NCHUNK, "stream length");
+  const ArLane ln;
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, j = ln.j, q = ln.q;
+
+  Ring ring;
+  ring.start(ars_lds, a.stream, f.T * a.n_chunks, wave, lane);
+  auto x_request = [&](int64_t tile, f32x4 (&xv)[S::NIT]) ARS_ALWAYS_INLINE {  // (arh_body's)
+    const int64_t n = tile * (16 * WAVES) + wave * 16 + j;
+    const float* row = a.x + (n < a.N ? n : a.N - 1) * a.ldx;
+#pragma unroll
+    for (int it = 0; it < S::NIT; ++it) {
+      const int col = it * 16 + 4 * q;
+      xv[it] = *reinterpret_cast<const f32x4*>(row + ((it + 1) * 16 <= S::DIN || col < S::DIN ? col : S::DIN - 4));
+    }
+  };
+  f32x4 xnext[S::NIT];
+  x_request(blockIdx.x, xnext);
+
+  float* const bias_lds = ars_lds + S::NR * S::CH * AR_TF;  // two buffers of bias_stride floats
+  int* const fmap_lds = ArLds::fmap(bias_lds, 2 * f.bias_stride);
+  float* const xr = ArLds::row(fmap_lds, wave, j, a.xs);
+  float* const base = ArLds::base(fmap_lds, f.n_fmaps * NFM);
+  if (f.term) ArLds::stage_base<64 * WAVES>(a, tid, base, S::D);
+  for (int i = tid; i < a.bias_floats; i += 64 * WAVES) bias_lds[i] = f.bias[i];  // the first transform's image; the others arrive through the ring
+  for (int i = tid; i < f.n_fmaps * NFM; i += 64 * WAVES) fmap_lds[i] = f.featmap[i];
+  __syncthreads();
+  ring.bias_n = f.bias_stride / 256;
+  const __attribute__((address_space(4))) float* const table = (const __attribute__((address_space(4))) float*)f.table;  // (uniform reads: scalar loads)
+
+  int buf = 0;  // the bias buffer the pass in progress reads
+  for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
+    ar_rows_in<S::D>(xr, q, xnext);
+    float total = 0.f;
+#pragma unroll 1
+    for (int t = 0; t < f.T; ++t) {
+      float wd[4];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) wd[l] = table[t * 8 + l];
+      const int fm = __builtin_bit_cast(int, table[t * 8 + 4]);
+      const bool alt = __builtin_bit_cast(int, table[t * 8 + 5]) != 0;
+      const int tn = t + 1 == f.T ? 0 : t + 1;
+      ring.bias_src = reinterpret_cast<const char*>(f.bias + (size_t)tn * f.bias_stride);
+      ring.bias_dst = reinterpret_cast<char*>(bias_lds + (buf ^ 1) * f.bias_stride);
+      const ArFids<NG, FPL, (NG * FPL <= 32)> fids(fmap_lds + fm * NFM, q);
+      arh_pass<S, Uni, false, false, true>(a, ring, x_request, xnext, bias_lds + buf * f.bias_stride, fids, xr, base, ln, tile, wd, t == 0, t + 1 == f.T, f.term != 0, total, alt);
+      buf ^= 1;
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
+}
+
+template <class S, typename Uni> __global__ __launch_bounds__(64 * S::WAVES, S::OCC) void arhf_kernel(ArArgs a, ArhFlow f) { arhf_body<S, Uni>(a, f); }
+
+// Launcher of the flow kernel (the entry point zk_arhf_launch of a unit of its own: zuko_amd/static_ar.py, ARHF).  A shape the kernel is not built for — three ring slots, rows not
+// staged in LDS, context columns, a single chunk per pass — declines: the caller keeps the T launches.
+template <class S, typename Uni> static int arhf_launch(const ArArgs* in, const ArhFlow* fin, int abi, int args_bytes, int flow_bytes, void* stream) {
+  if (abi != ARS_ABI || args_bytes != (int)sizeof(ArArgs) || flow_bytes != (int)sizeof(ArhFlow)) return ZK_EINVAL;
+  if constexpr (S::NR != 4 || !S::XLDS || S::DIN != S::D || S::D % 4 != 0 || S::NCHUNK < 2) {
+    return ZK_EINVAL;
+  } else {
+    ArArgs a = *in;
+    ArhFlow f = *fin;
+    if (a.D != S::D || a.DIN != S::DIN || a.L != S::NH + 1 || a.act != S::ACT || a.sched || a.NG != S::NG || a.n_chunks != S::NCHUNK || a.l1rev) return ZK_EINVAL;
+    if (f.T < 1 || f.T > 64 || f.n_fmaps < 1 || f.n_fmaps > f.T || f.bias_stride % 256 || f.bias_stride < a.bias_floats || !f.bias || !f.featmap || !f.table) return ZK_EINVAL;
+    if (!a.x || !a.stream || !a.ladj || a.accumulate || a.bin_out || a.knots_out) return ZK_EINVAL;
+    a.n_tiles = (a.N + 16 * S::WAVES - 1) / (16 * S::WAVES);
+    a.xs = ((S::D + 3) / 4) * 4 + 4;
+    f.term = a.base_loc != nullptr;
+    if (f.term ? !a.base_scale : (!a.y || a.ldy % 4 != 0 || (uintptr_t)a.y % 16 != 0)) return ZK_EINVAL;
+    if (f.n_fmaps * S::NG * 4 * Uni::FPL + (f.term ? 3 * S::D : 0) > ArLds::FMAP_WORDS) return ZK_EINVAL;
+    a.xlds = 1;
+    const int lds = ArLds::bytes(S::NR * S::CH * AR_TF, 2 * f.bias_stride, S::WAVES, a.xs);
+    if (lds > 160 * 1024) return ZK_EINVAL;
+    const void* fn = (const void*)arhf_kernel<S, Uni>;
+    hipError_t e = grant_dyn_lds(fn, lds);
+    if (e != hipSuccess) return (int)e;
+    const unsigned grid = (unsigned)(a.n_tiles < 256 ? a.n_tiles : 256);
+    void* kargs[] = {&a, &f};
+    e = hipLaunchKernel(fn, dim3(grid), dim3(64 * S::WAVES), kargs, lds, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    return ZK_LAUNCH_CHECK();
+  }
 }
 
 }  // namespace zk

@@ -80,6 +80,20 @@ struct ArArgs {
   const float* base_scale;
 };
 
+// Second argument of the two-part kernels' FLOW launch (fused_ar_half_impl.h: arhf_kernel — all T transforms of a composed flow in one launch):
+// what differs per transform.  ArArgs::stream then holds the T streams back to back (ArArgs::n_chunks chunks each).
+struct ArhFlow {
+  int T;                   // transforms
+  int bias_stride;         // floats between two bias images in `bias`: whole 1 KiB pieces, >= ArArgs::bias_floats
+  int n_fmaps;             // distinct feature maps in `featmap`, NG * 4 * FPL words each
+  int term;                // set by the launcher: the last pass ends in the base's log-density (ArArgs::base_loc), no y
+  const float* bias;       // T bias images
+  const int32_t* featmap;
+  const float* table;      // per transform 8 words: the four descale factors of its stream (float), the index of its feature map (int), first layer on the alternative pattern (int), 2 unused
+};
+// launcher of the flow kernel exported by a generated two-part unit (zuko_amd/static_ar.py: FLOW_ENTRY)
+typedef int (*arhf_launch_fn)(const ArArgs* a, const ArhFlow* f, int abi, int args_bytes, int flow_bytes, void* stream);
+
 __device__ __forceinline__ float act_f32(float v, int act) {
   switch (act) {
     case 1: return v < 0.f ? 0.f : v;

@@ -746,3 +746,45 @@ class MAF(Flow):
         ]
         base = UnconditionalDistribution(DiagNormal, loc=torch.zeros(features), scale=torch.ones(features), buffer=True)
         super().__init__(layers, base)
+
+
+def fused_flow_call(transforms, x: Tensor, base=None):
+    """A composition of autoregressive transforms in ONE persistent launch (zuko_amd/fused.py: FusedFlow; csrc/fused_ar_half_impl.h: arhf_kernel): (y, ladj),
+    or (None, log_prob) when base = (loc, scale) of a diagonal-normal base is folded into the launch — what ComposedTransform.call_and_ladj computes with one
+    launch per member, bit for bit.  None when the composition does not qualify: fewer than two members, a member that is not an autoregressive
+    transform on the two-part static kernel of the first one's shape, a context, gradients wanted, ZUKO_AMD_NO_FUSED_FLOW=1 — the caller then
+    walks the members as before."""
+    if len(transforms) < 2 or not fused.fused_flow_enabled() or not torch.is_tensor(x) or x.dim() < 1:
+        return None
+    if any(type(t) is not FusedAutoregressiveTransform or t.c is not None for t in transforms):
+        return None
+    states = []
+    for t in transforms:
+        st = t._fused(x)  # (device, dtype, gradients; may compile the member's kernels at a large batch)
+        if st is None or not isinstance(st, fused.FusedAR):
+            return None
+        states.append(st)
+    flow = fused.flow_state(states, x.numel() // max(x.shape[-1], 1))
+    if flow is None:
+        return None
+    for t, st in zip(transforms, states):
+        t._check_widths(x, st)
+        st.refresh([m for m in t.lazy.hyper if isinstance(m, MaskedLinear)])
+    D = transforms[0].lazy.features
+    term = None
+    if base is not None and states[-1].serves_terminal() and all(v.dtype == torch.float32 and v.device == x.device and tuple(v.shape) == (D,) for v in base):
+        term = (base[0].contiguous(), base[1].contiguous())
+    if not flow.serves(term is not None):
+        return None
+    flow.sync()
+    batch = x.shape[:-1]
+    x2 = x.reshape(-1, D)
+    if not (x2.stride(-1) == 1 and x2.stride(0) % 4 == 0 and x2.data_ptr() % 16 == 0):
+        x2 = x2.contiguous()
+    ladj = torch.empty(x2.shape[0], dtype=x.dtype, device=x.device)
+    if term is not None:
+        flow.run(x2, None, ladj, base=term)
+        return None, ladj.reshape(batch)
+    y = torch.empty((x2.shape[0], D), dtype=x.dtype, device=x.device)
+    flow.run(x2, y, ladj)
+    return y.reshape(batch + (D,)), ladj.reshape(batch)

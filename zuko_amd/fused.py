@@ -499,6 +499,119 @@ def default_variant() -> int:
 HALF, GSPLIT, STATIC, GENERIC = range(4)  # FusedAR._product(): the kernel that serves a launch
 
 
+def fused_flow_enabled() -> bool:
+    """Whether a composed autoregressive flow may run as ONE persistent launch (FusedFlow).  ZUKO_AMD_NO_FUSED_FLOW=1, read per call, keeps one
+    launch per transform: same results, bit for bit."""
+    return os.environ.get("ZUKO_AMD_NO_FUSED_FLOW", "0") != "1"
+
+
+class FusedFlow:
+    """The T autoregressive transforms of a composed flow on ONE launch of their two-part kernel's flow instantiation (csrc/fused_ar_half_impl.h:
+    arhf_kernel; include/zuko_amd.h: zk_ar_forward_static with flow_transforms): a workgroup carries its row tile through all T transforms, so x is read once and y / ladj
+    (or the log-density) are written once.  Owns what the kernel reads per transform: the T two-part streams back to back, the T bias images, the
+    distinct feature maps and the table of descale factors.  A transform's slice is copied from its FusedAR state when that state's stream was
+    re-gathered (its parameter stamp changed); with frozen weights that is once."""
+
+    def __init__(self, states: list, kernel, alt: list) -> None:
+        st0 = states[0]
+        self.states = list(states)
+        self.T = len(states)
+        self.kernel = kernel  # StaticKernel of the flow unit (zuko_amd/static_ar.py: ARHF)
+        self.per = st0.half_stream.buf.numel()  # floats of one transform's stream: whole chunks
+        self.bias_stride = -(-st0.bias_floats // 256) * 256  # whole 1 KiB pieces (the kernel requests the next image by LDS DMA)
+        dev = st0.device
+        self.stream = torch.zeros(self.T * self.per, dtype=torch.float32, device=dev)
+        self.bias = torch.zeros(self.T * self.bias_stride, dtype=torch.float32, device=dev)
+        maps, self.map_of = [], []
+        for st in states:
+            fm = np.asarray(st.plan.featmap, dtype=np.int32)
+            k = next((i for i, m in enumerate(maps) if np.array_equal(m, fm)), None)
+            if k is None:
+                maps.append(fm)
+                k = len(maps) - 1
+            self.map_of.append(k)
+        self.n_maps = len(maps)
+        self.featmap = torch.from_numpy(np.concatenate(maps)).to(dev)
+        self.table_host = np.zeros((self.T, 8), dtype=np.float32)
+        self.table_host.view(np.int32)[:, 4] = self.map_of
+        self.table_host.view(np.int32)[:, 5] = alt  # 1: the transform's first layer follows the kernel's alternative in pairs
+        self.table = torch.zeros(self.T * 8, dtype=torch.float32, device=dev)
+        self.stamps = [None] * self.T
+
+    @staticmethod
+    def build(states: list, rows):
+        """The FusedFlow of these states, or None.  Static conditions (the per-call ones are FusedAR._half_serves of every member): every member holds a
+        two-part kernel, their tables differ in the first layer's in pairs at most (static_ar.flow_tables), a flow kernel for them is on disk or
+        `rows` allows compiling it, and the tables fit the LDS."""
+        from . import static_ar
+
+        st0 = states[0]
+        if len(states) < 2 or len(states) > 64 or any(st.half is None or st.half_stream is None or st.plan.fine_gather is None for st in states):
+            return None
+        if any(st.bias_floats != st0.bias_floats or st.act != st0.act or st.bound != st0.bound or st.slope != st0.slope or st.plan.layout.kind != st0.plan.layout.kind for st in states):
+            return None
+        tabs = [static_ar.half_tables(st.plan, st.plan.layout.kind, st.act) for st in states]
+        tf = None if any(t is None for t in tabs) else static_ar.flow_tables([t[0] for t in tabs])
+        if tf is None:
+            return None
+        p = st0.plan
+        n_maps = len({np.asarray(st.plan.featmap, dtype=np.int32).tobytes() for st in states})
+        stride = -(-st0.bias_floats // 256) * 256
+        xs = ((p.features + 3) // 4) * 4 + 4
+        if n_maps * len(p.featmap) > 1024 or (4 * tf[0]["CH"] * 256 + 2 * stride + 1024 + 256 + 8 * 16 * xs) * 4 > 160 * 1024:
+            return None
+        kernel = static_ar.lookup_flow(tf[0], rows)
+        return None if kernel is None else FusedFlow(states, kernel, tf[1])
+
+    def serves(self, terminal: bool) -> bool:
+        """After every member's refresh(): each would launch its two-part kernel, and (terminal) the base's tables fit behind the feature maps."""
+        p = self.states[0].plan
+        if terminal and self.n_maps * len(p.featmap) + 3 * p.features > 1024:
+            return False
+        return all(st._half_serves(None) for st in self.states)
+
+    def sync(self) -> None:
+        """Bring the slices of the transforms whose streams were re-gathered up to date (device-to-device copies on the launch stream)."""
+        dirty = False
+        for t, st in enumerate(self.states):
+            stamp = st.half_stream.stamp
+            if stamp != self.stamps[t]:
+                self.stream[t * self.per : (t + 1) * self.per].copy_(st.half_stream.buf)
+                self.bias[t * self.bias_stride : t * self.bias_stride + st.bias_floats].copy_(st.bias)
+                d = list(st.half_descale) + [1.0] * (4 - len(st.half_descale))
+                self.table_host[t, :4] = d
+                self.stamps[t] = stamp
+                dirty = True
+        if dirty:
+            self.table.copy_(torch.from_numpy(self.table_host.reshape(-1)))
+
+    def run(self, x: Tensor, y: Tensor | None, ladj: Tensor, base=None) -> None:
+        """x [N, D] (rows 16-byte aligned), ladj [N]; y [N, D], or None with base = (loc [D], scale [D]): ladj receives the log-density."""
+        from . import _C
+        from .ops import _ptr, _stream
+
+        st0 = self.states[0]
+        p = st0.plan
+        io = dict(base_loc=_ptr(base[0]), base_scale=_ptr(base[1])) if base is not None else dict(y=_ptr(y), ldy=y.stride(0))
+        a = _C.args("zk_ar_args_v1", uni_kind=p.layout.kind, D=p.features, DIN=p.features, flow_transforms=self.T, n_layers=p.n_layers, n_groups=p.n_groups, n_chunks=st0.half_stream.n_chunks, act=st0.act,
+                    bias_floats=st0.bias_floats, flow_bias_stride=self.bias_stride, flow_featmaps=self.n_maps, N=x.shape[0], ldx=x.stride(0), bound=st0.bound, slope=st0.slope, x=_ptr(x), ladj=_ptr(ladj),
+                    wstream=_ptr(self.stream), bias=_ptr(self.bias), featmap=_ptr(self.featmap), flow_table=_ptr(self.table), launcher=self.kernel.launcher, **io)
+        _C.check(_C.lib().zk_ar_forward_static(a, _stream()), "zk_ar_forward_static (flow launch)")
+
+
+def flow_state(states: list, rows: int):
+    """The FusedFlow of these FusedAR states (cached on the first of them), or None when they cannot share a flow launch.  A flow kernel that is not on
+    disk is compiled once a call brings `rows` to the JIT threshold (zuko_amd/static_ar.py: lookup_flow)."""
+    from . import static_ar
+
+    cache = states[0].__dict__.setdefault("_flows", {})
+    key = tuple((id(st), id(st.half)) for st in states)  # (a member may acquire its kernel later: compiled on first use at a large batch)
+    jit = static_ar._jit_allowed(rows)
+    if key not in cache or (cache[key][0] is None and jit and not cache[key][1]):
+        cache[key] = (FusedFlow.build(states, rows), jit)
+    return cache[key][0]
+
+
 class FusedAR:
     """Runs zk_ar_forward for one MaskedAutoregressiveTransform on one device."""
 

@@ -395,6 +395,36 @@ def half_tables(plan, uni_kind: int, act: int = 1):
     return out, g
 
 
+def flow_tables(tables: list):
+    """Tables of the flow kernel that serves transforms with these two-part tables (half_tables, in the flow's order), and per transform whether its
+    first layer follows the alternative pattern; or None.  The members may differ from the first one in the first layer's in pairs only, and all that
+    differ must agree (a flow that alternates the ascending and the descending feature order: the orders mirror the input tiles).  The kernel wants
+    the four-slot ring, rows staged in LDS, no context columns and two chunks or more per pass."""
+    t0 = tables[0]
+    if t0["NR"] != 4 or not t0["XLDS"] or t0["DIN"] != t0["D"] or t0["D"] % 4 or t0["NCHUNK"] < 2 or t0["STREAM_IMAGES"] != t0["NCHUNK"] * t0["CH"] or t0["BASE"][0] != 0:
+        return None
+    nb0 = t0["NB"][0]
+    alt, flags = None, []
+    for t in tables:
+        if t == t0:
+            flags.append(0)
+            continue
+        if {k: v for k, v in t.items() if k != "B_IP"} != {k: v for k, v in t0.items() if k != "B_IP"} or t["B_IP"][nb0:] != t0["B_IP"][nb0:] or (alt is not None and t["B_IP"][:nb0] != alt):
+            return None
+        alt = t["B_IP"][:nb0]
+        flags.append(1)
+    out = dict(t0, flow=1, FLOW_ALT=int(alt is not None), B_IP_ALT=alt if alt is not None else t0["B_IP"][:nb0])
+    return out, flags
+
+
+def lookup_flow(tf: dict, rows: int | None = None):
+    """The flow kernel (StaticKernel) of flow_tables' tables, or None: found on disk, or compiled when `rows` reaches the JIT threshold."""
+    if not _enabled() or not half_enabled():
+        return None
+    found = find_or_compile(ARHF, tf, _jit_allowed(rows), verbose=_jit_verbose())
+    return None if found is None else found[0]
+
+
 HALF_LOOK = 1  # == ARH_LOOK of csrc/fused_ar_half_impl.h: blocks of weight images requested ahead of the matrix instructions that consume them
 HALF_BPOS = 8  # four-slot ring: the chunk's barrier stands behind the request of the block at images BPOS, BPOS + 1 (even, >= 2 (HALF_LOOK + 1))
 
@@ -419,9 +449,35 @@ def half_schedule(t: dict) -> tuple:
         ("settle", n)         s_waitcnt lgkmcnt(n): all but the youngest n image reads have returned
 
     (the bias reads that share the LDS queue stand in front of the request a settle leaves outstanding: they do not change which images return)."""
+    return _half_prologue(t), _half_pass(t)
+
+
+def _half_prologue(t: dict) -> list:
+    return [("issue",)] * (t["NR"] - 1) + [("x", t["NIT"]), ("wait", 0, True), ("barrier",)]  # (ArLds::stage ends in __syncthreads())
+
+
+def half_flow_bias_chunk(t: dict) -> int:
+    """Flow kernel: the chunk of a pass behind whose barrier the NEXT pass's bias image is requested — the last but one, so that the last chunk's
+    barrier publishes it (ArhRing4::bias_request)."""
+    return t["NCHUNK"] - 2
+
+
+def half_flow_schedule(t: dict, T: int) -> tuple:
+    """half_schedule for the FLOW kernel (arhf_kernel: the passes of T transforms over one tile follow each other on one stream of T NCHUNK chunks):
+    (prologue, [pass of transform 0, ..., pass of transform T - 1]).  The passes differ at the edges only: the next tile's rows are requested in
+    the LAST pass — in the others the barrier at that place waits for vmcnt(0) like every other —, and every pass carries one more event,
+
+        ("bias",)             the LDS-DMA request of the next pass's bias image into the buffer the pass in progress does not read
+
+    behind the barrier of chunk half_flow_bias_chunk(t).  Four-slot ring only."""
+    assert t["NR"] == 4 and t["NCHUNK"] >= 2
+    return _half_prologue(t), [_half_pass(t, rows=(k == T - 1), bias_at=half_flow_bias_chunk(t)) for k in range(T)]
+
+
+def _half_pass(t: dict, rows: bool = True, bias_at: int | None = None) -> list:
+    """One tile pass of half_schedule.  rows: the pass requests the next tile's rows; bias_at: the chunk behind whose barrier ("bias",) stands."""
     ch, nr, per, look = t["CH"], t["NR"], t["CH"] // t["WAVES"], HALF_LOOK
     nit, last_base, images = t["NIT"], t["LAST_BASE"], t["IMAGES"]
-    pro = [("issue",)] * (nr - 1) + [("x", nit), ("wait", 0, True), ("barrier",)]  # (ArLds::stage ends in __syncthreads())
     if nr == 4:
         trig = {half_trigger(t, c): c for c in range(t["NCHUNK"])}
         xpos = min((p for p in trig if p >= last_base), default=-1)  # (none: the rows are consumed, at the next tile's start, in front of the next barrier)
@@ -431,10 +487,12 @@ def half_schedule(t: dict) -> tuple:
 
     def read(pos):
         if nr != 4 and pos % ch == 0:
-            ev.extend([("wait", (nr - 2) * per + (nit if pos == xpos else 0), True), ("barrier",), ("issue",)])
+            ev.extend([("wait", (nr - 2) * per + (nit if pos == xpos and rows else 0), True), ("barrier",), ("issue",)])
         ev.append(("read", pos))
         if nr == 4 and pos in trig:
-            ev.extend([("wait", nit if pos == xpos else 0, pos % ch != t["BPOS"] + 1), ("barrier",), ("issue",)])
+            ev.extend([("wait", nit if pos == xpos and rows else 0, pos % ch != t["BPOS"] + 1), ("barrier",), ("issue",)])
+            if trig[pos] == bias_at:
+                ev.append(("bias",))
 
     def layer(base, nb, last_of):
         lk = min(look, nb)
@@ -452,12 +510,13 @@ def half_schedule(t: dict) -> tuple:
         ots = t["B_OT"][off : off + nb]
         layer(t["BASE"][l], nb, lambda s: s + 1 == nb or ots[s + 1] != ots[s])
         off += nb
-    ev.append(("x", nit))
+    if rows:
+        ev.append(("x", nit))
     nbl = (images - last_base) // 2
     nt = nbl // max(t["GOFF"][-1], 1)
     ends = {g1 * nt - 1 for g1 in t["GOFF"][1:]}
     layer(last_base, nbl, lambda s: s in ends)
-    return pro, ev
+    return ev
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -504,6 +563,7 @@ class Family:
     meta: object         # tables -> the family's own fields of the meta JSON
 
 
+FLOW_ENTRY = "zk_arhf_launch"
 _FORWARD = dict(entry="zk_ars_launch", params=(("const zk::ArArgs*", "a"), ("int", "abi"), ("int", "args_bytes"), ("int", "train"), ("void*", "stream")))
 _BACKWARD = dict(entry="zk_ars_dgrad_launch", params=(("const zk::ArArgs*", "a"), ("int", "abi"), ("int", "args_bytes"), ("void*", "stream")))
 
@@ -536,6 +596,16 @@ ARH = dataclasses.replace(
     index=lambda t: "h" + _digest(t),
     meta=lambda t: dict(_pick(t, "uni", "ACT", "D", "DIN", "HT", "WAVES", "CH", "TRAIN_OK", "XLDS", "NCHUNK"), half=1, split=2),
 )
+# the FLOW launch of the two-part kernel: all transforms of a composed flow in one persistent launch (arhf_kernel; zuko_amd/fused.py: FusedFlow).  A unit of
+# its own, from flow_tables: the two-part tables of the flow's first transform plus the first layer's in pairs under the flow's other feature order
+ARHF = dataclasses.replace(
+    ARH, prefix="arhf", entry=FLOW_ENTRY, launcher="zk::arhf_launch<Shape, {uni}>",
+    params=(("const zk::ArArgs*", "a"), ("const zk::ArhFlow*", "f"), ("int", "abi"), ("int", "args_bytes"), ("int", "flow_bytes"), ("void*", "stream")),
+    shape=ARH.shape + (("bool", ("FLOW_ALT",)), ("unsigned char[]", ("B_IP_ALT",))),
+    sig=lambda t, alt: {"flow": t},
+    index=lambda t: "f" + _digest(t),
+    meta=lambda t: dict(_pick(t, "uni", "ACT", "D", "DIN", "HT", "WAVES", "CH", "XLDS", "NCHUNK", "NR", "FLOW_ALT"), half=1, flow=1),
+)
 # the backward kernels, in three shapes told apart by the tables' "chain" field (chain_tables: 1, chain_split_tables: 2 and 3).  Their signature
 # covers the whole tables, so they are found by file name
 ARSD_F32 = Family(  # dgrad through the hidden layers on the f32 instruction (csrc/fused_ar_static_impl.h: ars_dgrad_kernel)
@@ -555,7 +625,7 @@ ARSD_SPLIT = dataclasses.replace(  # dgrad through every layer, operand-split (c
 )
 ARSD_FULL = dataclasses.replace(  # the whole backward of the transform in one launch (arxb_kernel)
     ARSD_SPLIT, launcher="zk::arxb_launch<Shape, {uni}>", shape=ARSD_SPLIT.shape + (("int", ("NG",)), ("int[]", ("PB",))))
-FAMILIES = {"ars": ARS, "arx": ARX, "arh": ARH, "arsd": {1: ARSD_F32, 2: ARSD_SPLIT, 3: ARSD_FULL}}
+FAMILIES = {"ars": ARS, "arx": ARX, "arh": ARH, "arhf": ARHF, "arsd": {1: ARSD_F32, 2: ARSD_SPLIT, 3: ARSD_FULL}}
 
 
 def emit(fam: Family, t: dict, alt: list | None = None) -> str:
@@ -1047,6 +1117,10 @@ def prebuild(verbose: bool = True, jobs: int = 4) -> list[str]:
             th = half_tables(pl, layout.kind, act)  # the two-part twin (inference launches)
             if th is not None:
                 want(ARH, th[0])
+        tha, thd = (half_tables(pl, layout.kind, act) if pl is not None else None for pl in (pa, pd))
+        tf = flow_tables([tha[0], thd[0]]) if tha is not None and thd is not None else None  # the flow launch of a composition that starts in the ascending order
+        if tf is not None:
+            want(ARHF, tf[0])
         if layout.kind in SPLIT_ONLY_KINDS:
             continue  # (no f32-instruction kernel, no training chain for this kind)
         ta, td = tables(pa, layout.kind, act), tables(pd, layout.kind, act)

@@ -478,6 +478,12 @@ class ComposedTransform(Transform):
         """(y, log|det dy/dx|).  base = (loc, scale) of a diagonal-normal base over the last axis (NormalizingFlow.log_prob): when the LAST transform can
         fold the base's log-density into its own launch (call_and_log_prob) the result is (None, log_prob) instead — y is never written."""
         dim = self.domain_dim
+        if dim == 1 and torch.is_tensor(x) and x.is_cuda and len(self.transforms) > 1:
+            from .flows.autoregressive import fused_flow_call
+
+            out = fused_flow_call(self.transforms, x, base)  # all members in one persistent launch, where they are autoregressive transforms of one shape
+            if out is not None:
+                return out
         total = None
         owned = False  # `total` is a tensor this loop may write: allocated by a fused transform for this call, or the result of `total + ladj`
         last = self.transforms[-1]
