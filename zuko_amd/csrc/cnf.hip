@@ -29,8 +29,9 @@ namespace zk {
 
 #define CNF_ROWS 64  // rows per block: one 16-row tile per wavefront
 
-// (the image's layout CnfLayout, the Dormand-Prince tableau CNF_C / CNF_A / CNF_E and the activation cnf_act: csrc/zk_cnf_common.h, shared with the
-//  adjoint kernel of csrc/cnf_backward.hip)
+// (the image's layout CnfLayout, the Dormand-Prince tableau CNF_C / CNF_A / CNF_E, the time embedding and the first layer's pre-activation:
+//  csrc/zk_cnf_common.h, shared with the adjoint kernel of csrc/cnf_backward.hip; the paired layer product mnn_matvec and the activation mnn_elu:
+//  csrc/zk_mnn_common.h)
 struct CnfArgs {
   const float* x;
   const float* l;
@@ -48,39 +49,16 @@ struct CnfArgs {
 // max that keeps a NaN from either side (torch.max does; fmaxf drops it)
 __device__ __forceinline__ float cnf_max(float a, float b) { return (a > b || a != a) ? a : b; }
 
-// out_g = W in_g (+ b) for G column tiles at once: the A fragment of a (out tile, in tile) pair is read once and feeds 4 G products; out tiles go
-// in pairs, so 2 G accumulator chains are independent.  tin / tout tiles; the tiles of one out tile are consecutive in the image.
-template <int TM, int G, bool BIAS>
-__device__ __forceinline__ void cnf_matvec(const float* W, const float* B, int tin, int tout, int lane, int q, const mnn_f4 (&in)[G][TM], mnn_f4 (&out)[G][TM]) {
-  const int rowstride = tin * 256;
-  mnn_for<TM / 2>([&](auto P) MNN_INLINE {
-    constexpr int o0 = 2 * P, o1 = o0 + 1;
-    if (o0 < tout) {
-      const bool two = o1 < tout;
-      const float* const p0 = W + o0 * rowstride + lane * 4;
-      const float* const p1 = p0 + rowstride;
-      mnn_for<G>([&](auto g) MNN_INLINE {
-        out[g][o0] = mnn_f4{0.f, 0.f, 0.f, 0.f};
-        out[g][o1] = mnn_f4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (BIAS) {
-          out[g][o0] = *reinterpret_cast<const mnn_f4*>(B + o0 * 16 + q * 4);
-          if (two) out[g][o1] = *reinterpret_cast<const mnn_f4*>(B + o1 * 16 + q * 4);
-        }
-      });
-      mnn_for<TM>([&](auto it) MNN_INLINE {
-        if (it < tin) {
-          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(p0 + it * 256);
-          mnn_for<4>([&](auto r) MNN_INLINE {
-            mnn_for<G>([&](auto g) MNN_INLINE { out[g][o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], in[g][it][(int)r], out[g][o0], 0, 0, 0); });
-          });
-          if (two) {
-            const mnn_f4 a1 = *reinterpret_cast<const mnn_f4*>(p1 + it * 256);
-            mnn_for<4>([&](auto r) MNN_INLINE {
-              mnn_for<G>([&](auto g) MNN_INLINE { out[g][o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], in[g][it][(int)r], out[g][o1], 0, 0, 0); });
-            });
-          }
-        }
-      });
+// v = ELU(p) and, with TAN, D = ELU'(p) of one tile
+template <bool TAN> __device__ __forceinline__ void cnf_elu_tile(const mnn_f4& p, mnn_f4& v, mnn_f4& D) {
+  mnn_for<4>([&](auto r) MNN_INLINE {
+    if constexpr (TAN) {
+      float av, ad;
+      mnn_elu(p[(int)r], av, ad);
+      v[(int)r] = av;
+      D[(int)r] = ad;
+    } else {
+      v[(int)r] = mnn_elu(p[(int)r]);
     }
   });
 }
@@ -99,7 +77,7 @@ __device__ __forceinline__ float cnf_tangents(const CnfLayout& L, const float* l
     });
   });
   if (L.nh > 1) {
-    cnf_matvec<TM, G, false>(lds + L.o_w[1], nullptr, L.T[0], L.T[1], lane, q, a, b);
+    mnn_matvec<TM, G, 0>(lds + L.o_w[1], nullptr, L.T[0], L.T[1], lane, q, a, b);
     mnn_for<G>([&](auto g) MNN_INLINE {
       mnn_for<TM>([&](auto o) MNN_INLINE {
         if (o < L.T[1]) mnn_for<4>([&](auto r) MNN_INLINE { a[g][o][(int)r] = D[1][o][(int)r] * b[g][o][(int)r]; });
@@ -107,7 +85,7 @@ __device__ __forceinline__ float cnf_tangents(const CnfLayout& L, const float* l
     });
   }
   if (L.nh > 2) {
-    cnf_matvec<TM, G, false>(lds + L.o_w[2], nullptr, L.T[1], L.T[2], lane, q, a, b);
+    mnn_matvec<TM, G, 0>(lds + L.o_w[2], nullptr, L.T[1], L.T[2], lane, q, a, b);
     mnn_for<G>([&](auto g) MNN_INLINE {
       mnn_for<TM>([&](auto o) MNN_INLINE {
         if (o < L.T[2]) mnn_for<4>([&](auto r) MNN_INLINE { a[g][o][(int)r] = D[2][o][(int)r] * b[g][o][(int)r]; });
@@ -132,68 +110,25 @@ __device__ __forceinline__ float cnf_tangents(const CnfLayout& L, const float* l
 // f(ts, xin) of the wave's 16 rows: fo[r] = component 4 r + q of the field, tr = the trace of its Jacobian (TAN)
 template <int TM, bool TAN>
 __device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, const float* __restrict__ prow, int lane, int q, float ts, const float (&xin)[4], float (&fo)[4], float& tr) {
-  mnn_f4 v[1][TM], w[1][TM], D[3][TM];
+  mnn_f4 v[TM], w[TM], D[3][TM];
   float emb[4];
   mnn_for<4>([&](auto s) MNN_INLINE {
-    const int e = 4 * s + q;
     emb[s] = 0.f;
-    if (s < L.kt) {
-      const float arg = lds[L.o_fr + (e < L.Q ? e : (e < 2 * L.Q ? e - L.Q : 0))] * ts;
-      emb[s] = e < L.Q ? cosf(arg) : (e < 2 * L.Q ? sinf(arg) : 0.f);
-    }
+    if (s < L.kt) emb[s] = cnf_embed(L, lds, 4 * s + q, ts);
   });
-  // first layer: pre + W0t emb + W0x x
-  const float* const pt = lds + L.o_w0t + lane;
-  const float* const px = lds + L.o_w0x + lane;
   mnn_for<TM>([&](auto o) MNN_INLINE {
-    if (o < L.T[0]) {
-      mnn_f4 c = *reinterpret_cast<const mnn_f4*>(prow + o * 16 + q * 4);
-      mnn_for<4>([&](auto s) MNN_INLINE {
-        if (s < L.kt) c = __builtin_amdgcn_mfma_f32_16x16x4f32(pt[(o * L.kt + s) * 64], emb[s], c, 0, 0, 0);
-      });
-      mnn_for<4>([&](auto s) MNN_INLINE {
-        if (s < L.kx) c = __builtin_amdgcn_mfma_f32_16x16x4f32(px[(o * L.kx + s) * 64], xin[s], c, 0, 0, 0);
-      });
-      mnn_for<4>([&](auto r) MNN_INLINE {
-        if constexpr (TAN) {
-          float av, ad;
-          cnf_act(c[(int)r], av, ad);
-          v[0][o][(int)r] = av;
-          D[0][o][(int)r] = ad;
-        } else {
-          v[0][o][(int)r] = cnf_act(c[(int)r]);
-        }
-      });
-    }
+    if (o < L.T[0]) cnf_elu_tile<TAN>(cnf_first_layer(L, lds, prow, lane, q, o, emb, xin), v[o], D[0][o]);
   });
   if (L.nh > 1) {
-    cnf_matvec<TM, 1, true>(lds + L.o_w[1], lds + L.o_b[1], L.T[0], L.T[1], lane, q, v, w);
+    mnn_matvec<TM, 1, 1>(lds + L.o_w[1], lds + L.o_b[1], L.T[0], L.T[1], lane, q, &v, &w);
     mnn_for<TM>([&](auto o) MNN_INLINE {
-      if (o < L.T[1]) mnn_for<4>([&](auto r) MNN_INLINE {
-        if constexpr (TAN) {
-          float av, ad;
-          cnf_act(w[0][o][(int)r], av, ad);
-          v[0][o][(int)r] = av;
-          D[1][o][(int)r] = ad;
-        } else {
-          v[0][o][(int)r] = cnf_act(w[0][o][(int)r]);
-        }
-      });
+      if (o < L.T[1]) cnf_elu_tile<TAN>(w[o], v[o], D[1][o]);
     });
   }
   if (L.nh > 2) {
-    cnf_matvec<TM, 1, true>(lds + L.o_w[2], lds + L.o_b[2], L.T[1], L.T[2], lane, q, v, w);
+    mnn_matvec<TM, 1, 1>(lds + L.o_w[2], lds + L.o_b[2], L.T[1], L.T[2], lane, q, &v, &w);
     mnn_for<TM>([&](auto o) MNN_INLINE {
-      if (o < L.T[2]) mnn_for<4>([&](auto r) MNN_INLINE {
-        if constexpr (TAN) {
-          float av, ad;
-          cnf_act(w[0][o][(int)r], av, ad);
-          v[0][o][(int)r] = av;
-          D[2][o][(int)r] = ad;
-        } else {
-          v[0][o][(int)r] = cnf_act(w[0][o][(int)r]);
-        }
-      });
+      if (o < L.T[2]) cnf_elu_tile<TAN>(w[o], v[o], D[2][o]);
     });
   }
   // last layer: its rows are stored so that register r of lane (j, q) is feature 4 r + q
@@ -202,7 +137,7 @@ __device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, 
   mnn_for<TM>([&](auto it) MNN_INLINE {
     if (it < tl) {
       const mnn_f4 a = *reinterpret_cast<const mnn_f4*>(lds + L.o_wo + it * 256 + lane * 4);
-      mnn_for<4>([&](auto r) MNN_INLINE { c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[(int)r], v[0][it][(int)r], c, 0, 0, 0); });
+      mnn_for<4>([&](auto r) MNN_INLINE { c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[(int)r], v[it][(int)r], c, 0, 0, 0); });
     }
   });
   mnn_for<4>([&](auto r) MNN_INLINE { fo[r] = c[(int)r]; });
@@ -221,7 +156,7 @@ extern __shared__ __attribute__((aligned(16))) float cnf_lds[];
 template <int TM, bool TAN> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 2 : 1) void cnf_step_kernel(CnfArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
   const CnfLayout& L = a.L;
-  for (int i = tid * 4; i < L.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(cnf_lds + i) = *reinterpret_cast<const mnn_f4*>(a.image + i);
+  mnn_stage_image(cnf_lds, a.image, L.total, tid);
   __syncthreads();
   const long long row0 = (long long)blockIdx.x * CNF_ROWS + wave * 16;
   if (row0 >= a.N) return;  // (the whole wavefront; no barrier follows)
@@ -307,9 +242,8 @@ static int cnf_step(const zk_cnf_args_v1* p, void* stream) {
   if (!cnf_layout(p->features, p->freqs, p->n_hidden, widths, &a.L)) return ZK_EINVAL;
   if (p->image_floats != a.L.total || (p->n_tangents != 0 && p->n_tangents != p->features) || p->N < 0) return ZK_EINVAL;
   if (p->ldx < p->features || p->ldy < p->features) return ZK_EINVAL;
-  if (p->ld_pre != 0 && (p->ld_pre < p->width0 || p->ld_pre % 4 != 0)) return ZK_EINVAL;
-  if (!std::isfinite(p->t) || !std::isfinite(p->dt) || !(p->atol >= 0) || !(p->rtol >= 0) || !std::isfinite(p->atol) || !std::isfinite(p->rtol)) return ZK_EINVAL;
-  if (p->n_tangents != 0 && !(p->trace_scale > 0 && std::isfinite(p->trace_scale))) return ZK_EINVAL;
+  if (!cnf_step_fields_ok(p, p->n_tangents != 0)) return ZK_EINVAL;
+  if (!(p->atol >= 0) || !(p->rtol >= 0) || !std::isfinite(p->atol) || !std::isfinite(p->rtol)) return ZK_EINVAL;
   if (p->N == 0) return 0;
   if (!p->x || !p->pre || !p->image || !p->y || !p->err) return ZK_EINVAL;
   if (p->n_tangents != 0 && (!p->l || !p->l_next)) return ZK_EINVAL;

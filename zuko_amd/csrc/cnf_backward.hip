@@ -87,18 +87,6 @@ static inline bool cnf_adj_shape(int F, int Q, int nh, int w0, int w1, int w2, C
   return cnf_adj_lds_floats(*B) * 4 <= MNN_LDS_MAX;
 }
 
-// rows per chunk (a multiple of 64) and the number of chunks: a pure function of N
-static inline int cnf_adj_geometry(long long N, int* rows_per_chunk, int* n_chunks) {
-  if (N < 1 || N > (1LL << 40) || !rows_per_chunk || !n_chunks) return ZK_EINVAL;
-  const long long t64 = (N + 63) / 64;
-  const long long want = t64 < CNF_ADJ_BLOCKS ? t64 : CNF_ADJ_BLOCKS;
-  const long long rows = ((t64 + want - 1) / want) * 64;
-  if (rows > 0x7fffffc0LL) return ZK_EINVAL;
-  *rows_per_chunk = (int)rows;
-  *n_chunks = (int)((N + rows - 1) / rows);
-  return 0;
-}
-
 struct CnfAdjArgs {
   const float* x;
   const float* ax;
@@ -116,7 +104,9 @@ struct CnfAdjArgs {
   CnfAdjLayout B;
 };
 
-// out = W in (+ b): tiles [tout][tin][256] of the image — a forward product, or a transposed one through the transposed tiles
+// out = W in (+ b): tiles [tout][tin][256] of the image — a forward product, or a transposed one through the transposed tiles.  bwd_mv<1, NB> of
+// csrc/zk_mnn_bwd_common.h without the run-time test of `Bias`: kept, because cnf_adj_kernel<3, true> takes 507 registers with that one and 506 with
+// this (profiles/small_net_frame/census.md)
 __device__ __forceinline__ void adj_mv(const float* W, const float* Bias, int tin, int tout, int lane, int q, bwd_ctiles in, bwd_tiles out) {
   mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
     out[o] = bwd_zero();
@@ -140,52 +130,9 @@ __device__ __forceinline__ void adj_state_transpose(float* scr, const float (&v)
   mnn_for<4>([&](auto s) MNN_INLINE { out[s] = scr[s * 64 + lane]; });
 }
 
-// acc[o][i] += (scale pb[o]) v[i]^T, contracted over the wave's 16 rows
-__device__ __forceinline__ void adj_outer(float* scr, int lane, int j, int q, int tout, int tin, float scale, bwd_ctiles pb, bwd_ctiles v,
-                                          mnn_f4 (&acc)[MNN_BWD_TM][MNN_BWD_TM]) {
-  float PA[MNN_BWD_TM][4];
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    if (o < tout) {
-      const mnn_f4 sc = pb[o] * scale;
-      bwd_transpose(scr, sc, lane, j, q, PA[o]);
-    }
-  });
-  mnn_for<MNN_BWD_TM>([&](auto i) MNN_INLINE {
-    if (i < tin) {
-      float VB[4];
-      bwd_transpose(scr + 256, v[i], lane, j, q, VB);
-      mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-        if (o < tout) {
-          mnn_for<4>([&](auto s) MNN_INLINE { acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(PA[o][s], VB[s], acc[o][i], 0, 0, 0); });
-        }
-      });
-    }
-  });
-}
-
 // out = a o b over the T tiles of a layer (zero behind them)
 __device__ __forceinline__ void adj_mul(bwd_ctiles a, bwd_ctiles b, int T, bwd_tiles out) {
   mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE { out[o] = o < T ? a[o] * b[o] : bwd_zero(); });
-}
-
-// the first layer's pre-activation of the wave's rows: pre + W0t emb + W0x x
-__device__ __forceinline__ void adj_first(const CnfLayout& L, const float* lds, const float* __restrict__ prow, int lane, int q, const float (&emb)[4], const float (&xin)[4],
-                                          bwd_tiles p) {
-  const float* const pt = lds + L.o_w0t + lane;
-  const float* const px = lds + L.o_w0x + lane;
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    p[o] = bwd_zero();
-    if (o < L.T[0]) {
-      mnn_f4 c = *reinterpret_cast<const mnn_f4*>(prow + o * 16 + q * 4);
-      mnn_for<4>([&](auto s) MNN_INLINE {
-        if (s < L.kt) c = __builtin_amdgcn_mfma_f32_16x16x4f32(pt[(o * L.kt + s) * 64], emb[s], c, 0, 0, 0);
-      });
-      mnn_for<4>([&](auto s) MNN_INLINE {
-        if (s < L.kx) c = __builtin_amdgcn_mfma_f32_16x16x4f32(px[(o * L.kx + s) * 64], xin[s], c, 0, 0, 0);
-      });
-      p[o] = c;
-    }
-  });
 }
 
 // h = ELU(p) (VALUE) or D = ELU'(p) (!VALUE) of a layer; `h` is also the next layer's input
@@ -196,10 +143,10 @@ template <bool VALUE> __device__ __forceinline__ void adj_act(bwd_ctiles p, int 
     if (o < T) {
       mnn_for<4>([&](auto r) MNN_INLINE {
         if constexpr (VALUE) {
-          h[o][(int)r] = cnf_act(p[o][(int)r]);
+          h[o][(int)r] = mnn_elu(p[o][(int)r]);
         } else {
           float av, ad;
-          cnf_act(p[o][(int)r], av, ad);
+          mnn_elu(p[o][(int)r], av, ad);
           h[o][(int)r] = av;
           D[o][(int)r] = ad;
         }
@@ -215,7 +162,9 @@ __device__ __forceinline__ void adj_forward(const CnfLayout& L, const float* lds
                                             mnn_f4 (&H)[3][MNN_BWD_TM], mnn_f4 (&D)[3][MNN_BWD_TM], float (&fo)[4]) {
   constexpr int TM = MNN_BWD_TM;
   mnn_f4 p[TM], v[TM];
-  adj_first(L, lds, prow, lane, q, emb, xin, p);
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < L.T[0]) p[o] = cnf_first_layer(L, lds, prow, lane, q, o, emb, xin);
+  });
   if constexpr (VALUE) adj_act<true>(p, L.T[0], H[0], D[0]); else adj_act<false>(p, L.T[0], v, D[0]);
   if constexpr (NH > 1) {
     if constexpr (VALUE) adj_mv(lds + L.o_w[1], lds + L.o_b[1], L.T[0], L.T[1], lane, q, H[0], p); else adj_mv(lds + L.o_w[1], lds + L.o_b[1], L.T[0], L.T[1], lane, q, v, p);
@@ -225,7 +174,7 @@ __device__ __forceinline__ void adj_forward(const CnfLayout& L, const float* lds
     if constexpr (VALUE) adj_mv(lds + L.o_w[2], lds + L.o_b[2], L.T[1], L.T[2], lane, q, H[1], p); else adj_mv(lds + L.o_w[2], lds + L.o_b[2], L.T[1], L.T[2], lane, q, v, p);
     if constexpr (VALUE) adj_act<true>(p, L.T[2], H[2], D[2]); else adj_act<false>(p, L.T[2], v, D[2]);
   }
-  if constexpr (!VALUE) {  // the last layer: its rows are stored so that register r of lane (j, q) is feature 4 r + q
+  if constexpr (!VALUE) {  // the last layer, as in cnf_field of csrc/cnf.hip: its rows are stored so that register r of lane (j, q) is feature 4 r + q
     const int tl = L.T[NH - 1];
     mnn_f4 c = *reinterpret_cast<const mnn_f4*>(lds + L.o_bo + q * 4);
     mnn_for<TM>([&](auto it) MNN_INLINE {
@@ -298,7 +247,7 @@ __device__ __forceinline__ void adj_tangent(const CnfLayout& L, const CnfAdjLayo
     });
     adj_mul(Tb, D[2], T2, Zb);
     adj_mul(D[1], Z2, T1, Tt);
-    adj_outer(scr, lane, j, q, T2, T1, sigma, Zb, Tt, aW2);
+    bwd_outer<1, true>(scr, lane, j, q, T2, T1, &Zb, &Tt, aW2, sigma);
     adj_mv(lds + B.o_wT[2], nullptr, T2, T1, lane, q, Zb, Tb);
   }
   if constexpr (NH > 1) {
@@ -307,7 +256,7 @@ __device__ __forceinline__ void adj_tangent(const CnfLayout& L, const CnfAdjLayo
     });
     adj_mul(Tb, D[1], T1, Zb);
     first(Tt);
-    adj_outer(scr, lane, j, q, T1, T0, sigma, Zb, Tt, aW1);
+    bwd_outer<1, true>(scr, lane, j, q, T1, T0, &Zb, &Tt, aW1, sigma);
     adj_mv(lds + B.o_wT[1], nullptr, T1, T0, lane, q, Zb, Tb);
   }
   mnn_for<TM>([&](auto o) MNN_INLINE {
@@ -328,7 +277,7 @@ template <int NH, bool TAN> __global__ __launch_bounds__(MNN_THREADS, 1) void cn
   float* const scr = cnf_adj_lds + a.lds_main + wave * MNN_BWD_SCRATCH;
   float* const cs = cnf_adj_lds + a.lds_main + (MNN_THREADS / 64) * MNN_BWD_SCRATCH + wave * CNF_ADJ_COLS;  // (touched by this wave's lanes j = 0 only)
   for (int i = lane; i < CNF_ADJ_COLS; i += 64) cs[i] = 0.f;
-  for (int i = tid * 4; i < B.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(lds + i) = *reinterpret_cast<const mnn_f4*>(a.image + i);
+  mnn_stage_image(lds, a.image, B.total, tid);
   __syncthreads();
 
   const int T0 = L.T[0], T1 = L.T[1], T2 = L.T[2], TL = L.T[NH - 1];
@@ -376,12 +325,8 @@ template <int NH, bool TAN> __global__ __launch_bounds__(MNN_THREADS, 1) void cn
       const float sigma = CNF_A[6][s] * a.dt;
       float emb[4];
       mnn_for<4>([&](auto k) MNN_INLINE {
-        const int e = 4 * k + q;
         emb[k] = 0.f;
-        if (k < L.kt) {
-          const float arg = lds[L.o_fr + (e < L.Q ? e : (e < 2 * L.Q ? e - L.Q : 0))] * ts;
-          emb[k] = e < L.Q ? cosf(arg) : (e < 2 * L.Q ? sinf(arg) : 0.f);
-        }
+        if (k < L.kt) emb[k] = cnf_embed(L, lds, 4 * k + q, ts);
       });
       mnn_f4 H[3][TM], D[3][TM], Db[3][TM];
       float fo[4];
@@ -434,13 +379,13 @@ template <int NH, bool TAN> __global__ __launch_bounds__(MNN_THREADS, 1) void cn
       if constexpr (NH > 2) {
         local(std::integral_constant<int, 2>{}, T2);
         adj_colsum(cs + 64, pb, sigma, T2, j, q);
-        adj_outer(scr, lane, j, q, T2, T1, sigma, pb, H[1], aW2);
+        bwd_outer<1, true>(scr, lane, j, q, T2, T1, &pb, &H[1], aW2, sigma);
         adj_mv(lds + B.o_wT[2], nullptr, T2, T1, lane, q, pb, hb);
       }
       if constexpr (NH > 1) {
         local(std::integral_constant<int, 1>{}, T1);
         adj_colsum(cs, pb, sigma, T1, j, q);
-        adj_outer(scr, lane, j, q, T1, T0, sigma, pb, H[0], aW1);
+        bwd_outer<1, true>(scr, lane, j, q, T1, T0, &pb, &H[0], aW1, sigma);
         adj_mv(lds + B.o_wT[1], nullptr, T1, T0, lane, q, pb, hb);
       }
       local(std::integral_constant<int, 0>{}, T0);
@@ -493,10 +438,7 @@ template <int NH, bool TAN> __global__ __launch_bounds__(MNN_THREADS, 1) void cn
   if (!a.work) return;  // (uniform over the grid: nobody asked for parameter gradients)
 
   float ej[6];  // emb(t_s)[j] of the six stages, for g W0t (read from the image before the partial overwrites it)
-  mnn_for<6>([&](auto s) MNN_INLINE {
-    const float ee = lds[L.o_fr + (j < L.Q ? j : (j < 2 * L.Q ? j - L.Q : 0))] * (a.t + CNF_C[s] * hstep);
-    ej[s] = j < L.Q ? cosf(ee) : (j < 2 * L.Q ? sinf(ee) : 0.f);
-  });
+  mnn_for<6>([&](auto s) MNN_INLINE { ej[s] = cnf_embed(L, lds, j, a.t + CNF_C[s] * hstep); });
 
   // ---- the block's four waves, added in the order 0, 1, 2, 3 over the LDS the image occupied
   float* const G = lds;
@@ -557,10 +499,7 @@ static int cnf_adjoint_step(const zk_cnf_adj_args_v1* p, void* stream) {
   if (!cnf_adj_shape(p->features, p->freqs, p->n_hidden, p->width0, p->width1, p->width2, &a.L, &a.B)) return ZK_EINVAL;
   if (p->image_floats != a.B.total || p->grad_floats != a.B.g_total || p->N < 0) return ZK_EINVAL;
   if (p->ldx < p->features || p->ld_ax < p->features || p->ld_ax_next < p->features) return ZK_EINVAL;
-  if (p->ld_pre != 0 && (p->ld_pre < p->width0 || p->ld_pre % 4 != 0)) return ZK_EINVAL;
-  if (p->ld_gpre < p->width0 || p->ld_gpre % 4 != 0) return ZK_EINVAL;
-  if (!std::isfinite(p->t) || !std::isfinite(p->dt)) return ZK_EINVAL;
-  if (!(p->trace_scale > 0 && std::isfinite(p->trace_scale))) return ZK_EINVAL;
+  if (!cnf_step_fields_ok(p, true) || p->ld_gpre < p->width0 || p->ld_gpre % 4 != 0) return ZK_EINVAL;
   if (p->gparams && p->flat_total < 1) return ZK_EINVAL;
   if (!p->ax || !p->ax_next) return ZK_EINVAL;
   if (p->N == 0) return 0;
@@ -568,7 +507,7 @@ static int cnf_adjoint_step(const zk_cnf_adj_args_v1* p, void* stream) {
   if (p->gparams && !p->grad_table) return ZK_EINVAL;
   if (((uintptr_t)p->pre | (uintptr_t)p->image | (uintptr_t)p->gpre | (uintptr_t)p->work) % 16 != 0) return ZK_EINVAL;
   int chunks = 0;
-  if (cnf_adj_geometry(p->N, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
+  if (mnn_bwd_geometry(p->N, 1, CNF_ADJ_BLOCKS, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
   a.x = (const float*)p->x; a.ax = (const float*)p->ax; a.al = (const float*)p->al; a.pre = (const float*)p->pre; a.image = (const float*)p->image;
   a.ax_next = (float*)p->ax_next; a.gpre = (float*)p->gpre; a.work = p->gparams ? (float*)p->work : nullptr;
   a.kbuf = (float*)p->work + (size_t)chunks * a.B.g_total;  // (behind the partials: the stages' k vectors, written and read by the lane that owns them)
@@ -598,7 +537,7 @@ extern "C" int zk_cnf_adjoint_floats(int features, int freqs, int n_hidden, int 
   *grad_floats = B.g_total;
   return 0;
 }
-extern "C" int zk_cnf_adjoint_geometry(int64_t N, int* rows_per_chunk, int* n_chunks) { return zk::cnf_adj_geometry(N, rows_per_chunk, n_chunks); }
+extern "C" int zk_cnf_adjoint_geometry(int64_t N, int* rows_per_chunk, int* n_chunks) { return zk::mnn_bwd_geometry(N, 1, CNF_ADJ_BLOCKS, rows_per_chunk, n_chunks); }
 extern "C" int zk_cnf_adjoint_workspace_floats(int64_t N, int features, int freqs, int n_hidden, int width0, int width1, int width2, int64_t* floats) {
   zk::CnfLayout L;
   zk::CnfAdjLayout B;
@@ -606,7 +545,7 @@ extern "C" int zk_cnf_adjoint_workspace_floats(int64_t N, int features, int freq
   *floats = 0;
   if (N == 0) return 0;
   int rows = 0, chunks = 0;
-  if (zk::cnf_adj_geometry(N, &rows, &chunks) != 0) return ZK_EINVAL;
+  if (zk::mnn_bwd_geometry(N, 1, CNF_ADJ_BLOCKS, &rows, &chunks) != 0) return ZK_EINVAL;
   *floats = (int64_t)chunks * B.g_total + ((N + 15) / 16) * CNF_ADJ_KTILE;
   return 0;
 }

@@ -42,14 +42,12 @@ struct MnnArgs {
 
 // two-way ELU (zuko/nn.py:335-353): units below `half` take ELU(p), the others -ELU(-p); d = its derivative
 __device__ __forceinline__ void mnn_act(float p, bool first, float& v, float& d) {
-  const float s = first ? p : -p;
-  const float a = s > 0.f ? s : expm1f(s);
-  d = s > 0.f ? 1.f : expf(s);
+  float a;
+  mnn_elu(first ? p : -p, a, d);
   v = first ? a : -a;
 }
 __device__ __forceinline__ float mnn_act(float p, bool first) {
-  const float s = first ? p : -p;
-  const float a = s > 0.f ? s : expm1f(s);
+  const float a = mnn_elu(first ? p : -p);
   return first ? a : -a;
 }
 
@@ -57,35 +55,9 @@ __device__ __forceinline__ float mnn_act(float p, bool first) {
 template <int TM, bool TAN>
 __device__ __forceinline__ void mnn_hidden(const float* W, const float* B, int tin, int tout, int half, int lane, int q, mnn_f4 (&v)[TM], mnn_f4 (&t)[TM]) {
   mnn_f4 ov[TM], ot[TM];
-  const int rowstride = tin * 256;  // the tiles of one out tile are consecutive: the in tile is an immediate offset of the read
-  mnn_for<TM / 2>([&](auto P) MNN_INLINE {
-    constexpr int o0 = 2 * P, o1 = o0 + 1;
-    if (o0 < tout) {
-      const bool two = o1 < tout;
-      const float* const p0 = W + o0 * rowstride + lane * 4;
-      const float* const p1 = p0 + rowstride;
-      ov[o0] = *reinterpret_cast<const mnn_f4*>(B + o0 * 16 + q * 4);
-      ov[o1] = two ? *reinterpret_cast<const mnn_f4*>(B + o1 * 16 + q * 4) : mnn_f4{0.f, 0.f, 0.f, 0.f};
-      ot[o0] = mnn_f4{0.f, 0.f, 0.f, 0.f};
-      ot[o1] = mnn_f4{0.f, 0.f, 0.f, 0.f};
-      mnn_for<TM>([&](auto it) MNN_INLINE {
-        if (it < tin) {
-          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(p0 + it * 256);
-          mnn_for<4>([&](auto r) MNN_INLINE {
-            ov[o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], v[it][(int)r], ov[o0], 0, 0, 0);
-            if constexpr (TAN) ot[o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], t[it][(int)r], ot[o0], 0, 0, 0);
-          });
-          if (two) {
-            const mnn_f4 a1 = *reinterpret_cast<const mnn_f4*>(p1 + it * 256);
-            mnn_for<4>([&](auto r) MNN_INLINE {
-              ov[o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], v[it][(int)r], ov[o1], 0, 0, 0);
-              if constexpr (TAN) ot[o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], t[it][(int)r], ot[o1], 0, 0, 0);
-            });
-          }
-        }
-      });
-    }
-  });
+  const mnn_f4* const in[2] = {v, t};
+  mnn_f4* const out[2] = {ov, ot};
+  mnn_matvec<TM, TAN ? 2 : 1, 1>(W, B, tin, tout, lane, q, in, out);
   mnn_for<TM>([&](auto o) MNN_INLINE {
     if (o < tout) {
       mnn_for<4>([&](auto r) MNN_INLINE {
@@ -155,7 +127,7 @@ template <int TM, bool INVERSE> __global__ __launch_bounds__(MNN_THREADS, 2) voi
     f = f < 0 ? 0 : (f >= a.n_features ? a.n_features - 1 : f);  // (a memory guard only: the caller checks the range, zuko_amd/ops.py: _mnn_feat)
     const float* img = a.image + (size_t)f * L.total;
     __syncthreads();  // the previous column's image is no longer read
-    for (int i = tid * 4; i < L.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(mnn_lds + i) = *reinterpret_cast<const mnn_f4*>(img + i);
+    mnn_stage_image(mnn_lds, img, L.total, tid);
     __syncthreads();
     for (int tile = wave; tile * 16 < a.rows_per_block && row0 + tile * 16 < a.N; tile += MNN_THREADS / 64) {
       const long long row = row0 + tile * 16 + j;

@@ -57,9 +57,8 @@ __device__ __forceinline__ void bwd_act(bwd_ctiles p, bwd_ctiles pd, int T, int 
       mnn_for<4>([&](auto r) MNN_INLINE {
         const bool first = o * 16 + q * 4 + r < half;
         const float pr = p[o][(int)r];
-        const float s = first ? pr : -pr;
-        const float a = s > 0.f ? s : expm1f(s);
-        const float d = s > 0.f ? 1.f : expf(s);
+        float a, d;
+        mnn_elu(first ? pr : -pr, a, d);
         v[o][(int)r] = first ? a : -a;
         t[o][(int)r] = d * pd[o][(int)r];
       });
@@ -67,26 +66,7 @@ __device__ __forceinline__ void bwd_act(bwd_ctiles p, bwd_ctiles pd, int T, int 
   });
 }
 
-// p = |W| v + b, pd = |W| t of one hidden-to-hidden layer (forward tile order)
-__device__ __forceinline__ void bwd_pre(const float* W, const float* Bias, int tin, int tout, int lane, int q, bwd_ctiles v, bwd_ctiles t, bwd_tiles p, bwd_tiles pd) {
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    if (o < tout) {
-      p[o] = *reinterpret_cast<const mnn_f4*>(Bias + o * 16 + q * 4);
-      pd[o] = bwd_zero();
-      mnn_for<MNN_BWD_TM>([&](auto it) MNN_INLINE {
-        if (it < tin) {
-          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(W + (o * tin + it) * 256 + lane * 4);
-          mnn_for<4>([&](auto r) MNN_INLINE {
-            p[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], v[it][(int)r], p[o], 0, 0, 0);
-            pd[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], t[it][(int)r], pd[o], 0, 0, 0);
-          });
-        }
-      });
-    }
-  });
-}
-
-// pb = vb act'(p) + tb act''(p) pd, pdb = tb act'(p)
+// pb = vb act'(p) + tb act''(p) pd, pdb = tb act'(p) (the second derivative wants exp(s) itself: not mnn_elu)
 __device__ __forceinline__ void bwd_local(bwd_ctiles p, bwd_ctiles pd, int T, int q, bwd_ctiles vb, bwd_ctiles tb, bwd_tiles pb, bwd_tiles pdb) {
   const int half = (T * 16 + 1) / 2;
   mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
@@ -107,7 +87,8 @@ __device__ __forceinline__ void bwd_local(bwd_ctiles p, bwd_ctiles pd, int T, in
   });
 }
 
-// acc[o][i] += pb[o] v[i]^T + pdb[o] t[i]^T, contracted over the wave's 16 elements
+// acc[o][i] += pb[o] v[i]^T + pdb[o] t[i]^T, contracted over the wave's 16 elements.  Not bwd_outer<2> of the header: that one adds member by member,
+// this one k-step by k-step (pb v, then pdb t), and the order of the additions into one accumulator decides the bits.
 __device__ __forceinline__ void bwd_outer(float* scr, int lane, int j, int q, int tout, int tin, bwd_ctiles pb, bwd_ctiles pdb, bwd_ctiles v, bwd_ctiles t,
                                           mnn_f4 (&acc)[MNN_BWD_TM][MNN_BWD_TM]) {
   float PA[MNN_BWD_TM][4], PT[MNN_BWD_TM][4];
@@ -134,25 +115,6 @@ __device__ __forceinline__ void bwd_outer(float* scr, int lane, int j, int q, in
   });
 }
 
-// vb = A^T pb, tb = A^T pdb through the transposed tiles WT [tin][tout][256] (tin: the tiles of the layer below, the product's rows)
-__device__ __forceinline__ void bwd_down(const float* WT, int tin, int tout, int lane, bwd_ctiles pb, bwd_ctiles pdb, bwd_tiles vb, bwd_tiles tb) {
-  mnn_for<MNN_BWD_TM>([&](auto i) MNN_INLINE {
-    vb[i] = bwd_zero();
-    tb[i] = bwd_zero();
-    if (i < tin) {
-      mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-        if (o < tout) {
-          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(WT + (i * tout + o) * 256 + lane * 4);
-          mnn_for<4>([&](auto r) MNN_INLINE {
-            vb[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], pb[o][(int)r], vb[i], 0, 0, 0);
-            tb[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], pdb[o][(int)r], tb[i], 0, 0, 0);
-          });
-        }
-      });
-    }
-  });
-}
-
 extern __shared__ __attribute__((aligned(16))) float mnn_bwd_lds[];
 
 template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_bwd_kernel(MnnBwdArgs a) {
@@ -166,7 +128,7 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_
   const float* img = a.image + (size_t)f * B.total;
   float* const lds = mnn_bwd_lds;
   float* const scr = mnn_bwd_lds + a.lds_main + wave * MNN_BWD_SCRATCH;
-  for (int i = tid * 4; i < B.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(lds + i) = *reinterpret_cast<const mnn_f4*>(img + i);
+  mnn_stage_image(lds, img, B.total, tid);
   __syncthreads();
 
   const int T0 = L.T[0], T1 = L.T[1], T2 = L.T[2], TL = L.T[NH - 1];
@@ -189,7 +151,8 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_
     const float glv = (valid && a.gl) ? (a.gl_reduced ? a.gl[row] : a.gl[row * a.Dsel + col]) : 0.f;
 
     // ---- the forward, keeping the pre-activations p_l and their tangents pd_l
-    mnn_f4 p0[TM], p1[TM], p2[TM], pd1[TM], pd2[TM], w0x[TM], v[TM], t[TM];
+    mnn_f4 p0[TM], w0x[TM], P1[2][TM], P2[2][TM], VT[2][TM];  // the pairs (p_l, pd_l) and (v, t) go through a layer product together
+    bwd_tiles p1 = P1[0], pd1 = P1[1], p2 = P2[0], pd2 = P2[1], v = VT[0], t = VT[1];
     mnn_signal<TM>(L, lds, a.signal + rc * a.lds + (size_t)col * L.S, lane, q, p0);
     mnn_for<TM>([&](auto o) MNN_INLINE {
       p1[o] = p2[o] = pd1[o] = pd2[o] = bwd_zero();
@@ -202,16 +165,17 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_
     });
     bwd_act(p0, w0x, T0, q, v, t);
     if constexpr (NH > 1) {
-      bwd_pre(lds + L.o_w[1], lds + L.o_b[1], T0, T1, lane, q, v, t, p1, pd1);
+      bwd_mv<2, 1>(lds + L.o_w[1], lds + L.o_b[1], T0, T1, lane, q, VT, P1);
       bwd_act(p1, pd1, T1, q, v, t);
     }
     if constexpr (NH > 2) {
-      bwd_pre(lds + L.o_w[2], lds + L.o_b[2], T1, T2, lane, q, v, t, p2, pd2);
+      bwd_mv<2, 1>(lds + L.o_w[2], lds + L.o_b[2], T1, T2, lane, q, VT, P2);
       bwd_act(p2, pd2, T2, q, v, t);
     }
 
     // ---- the last layer
-    mnn_f4 vb[TM], tb[TM], pb[TM], pdb[TM];
+    mnn_f4 VB[2][TM], PB[2][TM];  // (vb, tb) and (pb, pdb)
+    bwd_tiles vb = VB[0], tb = VB[1], pb = PB[0], pdb = PB[1];
     {
       mnn_f4 wl[TM];
       float pdy = 0.f;
@@ -243,14 +207,14 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_
       bwd_add(aB2, pb, T2);
       bwd_act(p1, pd1, T1, q, v, t);
       bwd_outer(scr, lane, j, q, T2, T1, pb, pdb, v, t, aW2);
-      bwd_down(lds + B.o_wT[2], T1, T2, lane, pb, pdb, vb, tb);
+      bwd_mv<2, 0>(lds + B.o_wT[2], nullptr, T2, T1, lane, q, PB, VB);  // (vb, tb) = A_2^T (pb, pdb)
     }
     if constexpr (NH > 1) {
       bwd_local(p1, pd1, T1, q, vb, tb, pb, pdb);
       bwd_add(aB1, pb, T1);
       bwd_act(p0, w0x, T0, q, v, t);
       bwd_outer(scr, lane, j, q, T1, T0, pb, pdb, v, t, aW1);
-      bwd_down(lds + B.o_wT[1], T0, T1, lane, pb, pdb, vb, tb);
+      bwd_mv<2, 0>(lds + B.o_wT[1], nullptr, T1, T0, lane, q, PB, VB);
     }
     bwd_local(p0, w0x, T0, q, vb, tb, pb, pdb);
     bwd_add(aB0, pb, T0);
@@ -327,14 +291,7 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void mnn_
         bwd_put_units(G + B.g_b[2], aB2, T2, j, q, set);
       }
       bwd_put_units(G + B.g_wl, aWl, TL, j, q, set);
-      const float sb = bwd_sum_j(aBl);
-      if (lane == 0) {
-        if (set) {
-          G[B.g_bl] = sb; G[B.g_bl + 1] = 0.f; G[B.g_bl + 2] = 0.f; G[B.g_bl + 3] = 0.f;
-        } else {
-          G[B.g_bl] += sb;
-        }
-      }
+      bwd_put_scalar(G + B.g_bl, aBl, lane, set);
     }
   }
   __syncthreads();
@@ -393,7 +350,7 @@ static int mnn_backward(const zk_mnn_bwd_args_v1* p, void* stream) {
   }
   if (!p->x || !p->signal || !p->image) return ZK_EINVAL;
   int chunks = 0;
-  if (mnn_bwd_geometry(p->N, p->Dsel, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
+  if (mnn_bwd_geometry(p->N, p->Dsel, MNN_BWD_BLOCKS, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
   a.x = (const float*)p->x; a.signal = (const float*)p->signal; a.image = (const float*)p->image; a.feat = (const int*)p->feat;
   a.gy = (const float*)p->gy; a.gl = (const float*)p->gl; a.gx = (float*)p->gx; a.gsignal = (float*)p->gsignal;
   a.work = p->gparams ? (float*)p->work : nullptr;
@@ -412,23 +369,12 @@ static int mnn_backward(const zk_mnn_bwd_args_v1* p, void* stream) {
 }  // namespace zk
 
 extern "C" int zk_mnn_backward(const zk_mnn_bwd_args_v1* args, void* stream) { return zk::mnn_backward(args, stream); }
-extern "C" int zk_mnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks) { return zk::mnn_bwd_geometry(N, Dsel, rows_per_chunk, n_chunks); }
+extern "C" int zk_mnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks) {
+  return zk::mnn_bwd_geometry(N, Dsel, MNN_BWD_BLOCKS, rows_per_chunk, n_chunks);
+}
 extern "C" int zk_mnn_backward_floats(int S, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats) {
-  zk::MnnLayout L;
-  zk::MnnBwdLayout B;
-  if (!image_floats || !grad_floats || !zk::mnn_bwd_shape(S, n_hidden, width0, width1, width2, &L, &B)) return ZK_EINVAL;
-  *image_floats = B.total;
-  *grad_floats = B.g_total;
-  return 0;
+  return zk::mnn_bwd_floats<0>(S, n_hidden, width0, width1, width2, image_floats, grad_floats);
 }
 extern "C" int zk_mnn_backward_workspace_floats(int64_t N, int64_t Dsel, int S, int n_hidden, int width0, int width1, int width2, int64_t* floats) {
-  zk::MnnLayout L;
-  zk::MnnBwdLayout B;
-  if (!floats || !zk::mnn_bwd_shape(S, n_hidden, width0, width1, width2, &L, &B)) return ZK_EINVAL;
-  *floats = 0;
-  if (N == 0 && Dsel >= 1 && Dsel <= 65535) return 0;
-  int rows = 0, chunks = 0;
-  if (zk::mnn_bwd_geometry(N, Dsel, &rows, &chunks) != 0) return ZK_EINVAL;
-  *floats = (int64_t)chunks * Dsel * B.g_total;
-  return 0;
+  return zk::mnn_bwd_workspace_floats<0>(N, Dsel, S, n_hidden, width0, width1, width2, floats);
 }

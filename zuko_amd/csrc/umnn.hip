@@ -44,7 +44,6 @@ struct UmnnArgs {
   MnnLayout L;
 };
 
-__device__ __forceinline__ float umnn_elu(float p) { return p > 0.f ? p : expm1f(p); }
 // x / (1 + |x / 7|): the integrand's logarithm, within (-7, 7) (zuko/flows/neural.py:104)
 __device__ __forceinline__ float umnn_squash(float h) { return h / (1.f + fabsf(h / 7.f)); }
 
@@ -74,7 +73,7 @@ __device__ __forceinline__ void umnn_hidden(const float* W, const float* B, int 
   mnn_for<TM>([&](auto o) MNN_INLINE {
     if (o < tout) {
       mnn_for<NP>([&](auto p) MNN_INLINE {
-        mnn_for<4>([&](auto r) MNN_INLINE { v[p * TM + o][(int)r] = umnn_elu(ov[p * TM + o][(int)r]); });
+        mnn_for<4>([&](auto r) MNN_INLINE { v[p * TM + o][(int)r] = mnn_elu(ov[p * TM + o][(int)r]); });
       });
     }
   });
@@ -88,7 +87,7 @@ __device__ __forceinline__ void umnn_tail(const MnnLayout& L, const float* lds, 
     if (o < L.T[0]) {
       const mnn_f4 w = *reinterpret_cast<const mnn_f4*>(lds + L.o_w0x + o * 16 + q * 4);
       mnn_for<NP>([&](auto p) MNN_INLINE {
-        mnn_for<4>([&](auto r) MNN_INLINE { v[p * TM + o][(int)r] = umnn_elu(fmaf(w[(int)r], u[p], c0[o][(int)r])); });
+        mnn_for<4>([&](auto r) MNN_INLINE { v[p * TM + o][(int)r] = mnn_elu(fmaf(w[(int)r], u[p], c0[o][(int)r])); });
       });
     }
   });
@@ -152,7 +151,7 @@ template <int TM, bool INVERSE> __global__ __launch_bounds__(MNN_THREADS, 2) voi
     f = f < 0 ? 0 : (f >= a.n_features ? a.n_features - 1 : f);  // (a memory guard only: the caller checks the range, zuko_amd/ops.py: _mnn_feat)
     const float* img = a.image + (size_t)f * L.total;
     __syncthreads();  // the previous column's image is no longer read
-    for (int i = tid * 4; i < L.total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(umnn_lds + i) = *reinterpret_cast<const mnn_f4*>(img + i);
+    mnn_stage_image(umnn_lds, img, L.total, tid);
     __syncthreads();
     for (int tile = wave; tile * 16 < a.rows_per_block && row0 + tile * 16 < a.N; tile += MNN_THREADS / 64) {
       const long long row = row0 + tile * 16 + j;

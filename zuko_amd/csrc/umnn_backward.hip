@@ -58,31 +58,10 @@ template <int NP> __device__ __forceinline__ void ubw_act(const mnn_f4 (&p)[NP][
       v[n][o] = bwd_zero();
       if (o < T) {
         mnn_for<4>([&](auto r) MNN_INLINE {
-          const float pr = p[n][o][(int)r];
-          v[n][o][(int)r] = pr > 0.f ? pr : expm1f(pr);
+          v[n][o][(int)r] = mnn_elu(p[n][o][(int)r]);
         });
       }
     });
-  });
-}
-
-// p = W v + b of one hidden-to-hidden layer (forward tile order)
-template <int NP>
-__device__ __forceinline__ void ubw_pre(const float* W, const float* Bias, int tin, int tout, int lane, int q, const mnn_f4 (&v)[NP][MNN_BWD_TM], mnn_f4 (&p)[NP][MNN_BWD_TM]) {
-  mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-    mnn_for<NP>([&](auto n) MNN_INLINE { p[n][o] = bwd_zero(); });
-    if (o < tout) {
-      const mnn_f4 b = *reinterpret_cast<const mnn_f4*>(Bias + o * 16 + q * 4);
-      mnn_for<NP>([&](auto n) MNN_INLINE { p[n][o] = b; });
-      mnn_for<MNN_BWD_TM>([&](auto it) MNN_INLINE {
-        if (it < tin) {
-          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(W + (o * tin + it) * 256 + lane * 4);
-          mnn_for<4>([&](auto r) MNN_INLINE {
-            mnn_for<NP>([&](auto n) MNN_INLINE { p[n][o] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], v[n][it][(int)r], p[n][o], 0, 0, 0); });
-          });
-        }
-      });
-    }
   });
 }
 
@@ -93,53 +72,12 @@ template <int NP> __device__ __forceinline__ void ubw_local(const mnn_f4 (&p)[NP
       pb[n][o] = bwd_zero();
       if (o < T) {
         mnn_for<4>([&](auto r) MNN_INLINE {
-          const float pr = p[n][o][(int)r];
-          pb[n][o][(int)r] = ab[n][o][(int)r] * (pr > 0.f ? 1.f : expf(pr));
+          float unused, d;
+          mnn_elu(p[n][o][(int)r], unused, d);
+          pb[n][o][(int)r] = ab[n][o][(int)r] * d;
         });
       }
     });
-  });
-}
-
-// acc[o][i] += sum over the points, in order, of pb[o] v[i]^T, contracted over the wave's 16 elements
-template <int NP>
-__device__ __forceinline__ void ubw_outer(float* scr, int lane, int j, int q, int tout, int tin, const mnn_f4 (&pb)[NP][MNN_BWD_TM], const mnn_f4 (&v)[NP][MNN_BWD_TM],
-                                          mnn_f4 (&acc)[MNN_BWD_TM][MNN_BWD_TM]) {
-  float PA[NP][MNN_BWD_TM][4];
-  mnn_for<NP>([&](auto n) MNN_INLINE {
-    mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-      if (o < tout) bwd_transpose(scr, pb[n][o], lane, j, q, PA[n][o]);
-    });
-  });
-  mnn_for<MNN_BWD_TM>([&](auto i) MNN_INLINE {
-    if (i < tin) {
-      float VB[NP][4];
-      mnn_for<NP>([&](auto n) MNN_INLINE { bwd_transpose(scr + 256, v[n][i], lane, j, q, VB[n]); });
-      mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-        if (o < tout) {
-          mnn_for<NP>([&](auto n) MNN_INLINE {
-            mnn_for<4>([&](auto s) MNN_INLINE { acc[o][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(PA[n][o][s], VB[n][s], acc[o][i], 0, 0, 0); });
-          });
-        }
-      });
-    }
-  });
-}
-
-// ab = W^T pb through the transposed tiles WT [tin][tout][256] (tin: the tiles of the layer below, the product's rows)
-template <int NP> __device__ __forceinline__ void ubw_down(const float* WT, int tin, int tout, int lane, const mnn_f4 (&pb)[NP][MNN_BWD_TM], mnn_f4 (&ab)[NP][MNN_BWD_TM]) {
-  mnn_for<MNN_BWD_TM>([&](auto i) MNN_INLINE {
-    mnn_for<NP>([&](auto n) MNN_INLINE { ab[n][i] = bwd_zero(); });
-    if (i < tin) {
-      mnn_for<MNN_BWD_TM>([&](auto o) MNN_INLINE {
-        if (o < tout) {
-          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(WT + (i * tout + o) * 256 + lane * 4);
-          mnn_for<4>([&](auto r) MNN_INLINE {
-            mnn_for<NP>([&](auto n) MNN_INLINE { ab[n][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], pb[n][o][(int)r], ab[n][i], 0, 0, 0); });
-          });
-        }
-      });
-    }
   });
 }
 
@@ -208,11 +146,11 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void umnn
       });
       ubw_act<NP>(p0, T0, v0);
       if constexpr (NH > 1) {
-        ubw_pre<NP>(lds + L.o_w[1], lds + L.o_b[1], T0, T1, lane, q, v0, p1);
+        bwd_mv<NP, NP>(lds + L.o_w[1], lds + L.o_b[1], T0, T1, lane, q, v0, p1);
         ubw_act<NP>(p1, T1, v1);
       }
       if constexpr (NH > 2) {
-        ubw_pre<NP>(lds + L.o_w[2], lds + L.o_b[2], T1, T2, lane, q, v1, p2);
+        bwd_mv<NP, NP>(lds + L.o_w[2], lds + L.o_b[2], T1, T2, lane, q, v1, p2);
         ubw_act<NP>(p2, T2, v2);
       }
       const mnn_f4 (&vl)[NP][TM] = NH == 1 ? v0 : (NH == 2 ? v1 : v2);
@@ -250,14 +188,14 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void umnn
       if constexpr (NH > 2) {
         ubw_local<NP>(p2, T2, ab, pb);
         mnn_for<NP>([&](auto n) MNN_INLINE { bwd_add(aB2, pb[n], T2); });
-        ubw_outer<NP>(scr, lane, j, q, T2, T1, pb, v1, aW2);
-        ubw_down<NP>(lds + B.o_wT[2], T1, T2, lane, pb, ab);
+        bwd_outer<NP>(scr, lane, j, q, T2, T1, pb, v1, aW2);
+        bwd_mv<NP, 0>(lds + B.o_wT[2], nullptr, T2, T1, lane, q, pb, ab);  // ab = W_2^T pb
       }
       if constexpr (NH > 1) {
         ubw_local<NP>(p1, T1, ab, pb);
         mnn_for<NP>([&](auto n) MNN_INLINE { bwd_add(aB1, pb[n], T1); });
-        ubw_outer<NP>(scr, lane, j, q, T1, T0, pb, v0, aW1);
-        ubw_down<NP>(lds + B.o_wT[1], T0, T1, lane, pb, ab);
+        bwd_outer<NP>(scr, lane, j, q, T1, T0, pb, v0, aW1);
+        bwd_mv<NP, 0>(lds + B.o_wT[1], nullptr, T1, T0, lane, q, pb, ab);
       }
       ubw_local<NP>(p0, T0, ab, pb);
       mnn_for<NP>([&](auto n) MNN_INLINE {
@@ -347,22 +285,13 @@ template <int NH, int TS> __global__ __launch_bounds__(MNN_THREADS, 1) void umnn
         bwd_put_units(G + B.g_b[2], aB2, T2, j, q, set);
       }
       bwd_put_units(G + B.g_wl, aWl, TL, j, q, set);
-      const float sb = bwd_sum_j(aBl);
-      if (lane == 0) {
-        if (set) {
-          G[B.g_bl] = sb; G[B.g_bl + 1] = 0.f; G[B.g_bl + 2] = 0.f; G[B.g_bl + 3] = 0.f;
-        } else {
-          G[B.g_bl] += sb;
-        }
-      }
+      bwd_put_scalar(G + B.g_bl, aBl, lane, set);
     }
   }
   __syncthreads();
   float* out = a.work + ((size_t)blockIdx.x * a.Dsel + col) * B.g_total;
   for (int i = tid * 4; i < B.g_total; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(out + i) = *reinterpret_cast<const mnn_f4*>(G + i);
 }
-
-static bool umnn_bwd_shape(int S, int nh, int w0, int w1, int w2, MnnLayout* L, MnnBwdLayout* B) { return mnn_bwd_shape(S, nh, w0, w1, w2, L, B, 2 * UMNN_QUAD_MAX); }
 
 template <int NH> static const void* umnn_bwd_fn(int ts) {
   if (ts <= 1) return (const void*)umnn_bwd_kernel<NH, 1>;
@@ -373,7 +302,7 @@ template <int NH> static const void* umnn_bwd_fn(int ts) {
 static int umnn_backward(const zk_umnn_bwd_args_v1* p, void* stream) {
   if (!p || p->struct_size != sizeof(zk_umnn_bwd_args_v1) || p->version != 1) return ZK_EINVAL;
   UmnnBwdArgs a;
-  if (!umnn_bwd_shape(p->S, p->n_hidden, p->width0, p->width1, p->width2, &a.L, &a.B)) return ZK_EINVAL;
+  if (!mnn_bwd_shape(p->S, p->n_hidden, p->width0, p->width1, p->width2, &a.L, &a.B, 2 * UMNN_QUAD_MAX)) return ZK_EINVAL;
   if (p->image_floats != a.B.total || p->grad_floats != a.B.g_total || p->n_features < 1 || p->N < 0 || p->Dsel < 1 || p->Dsel > 65535) return ZK_EINVAL;
   if (p->n_quad < 1 || p->n_quad > UMNN_QUAD_MAX) return ZK_EINVAL;
   if (p->ldx < 1 || p->ld_col < p->S || p->ld_signal < (p->Dsel - 1) * p->ld_col + p->S) return ZK_EINVAL;
@@ -388,7 +317,7 @@ static int umnn_backward(const zk_umnn_bwd_args_v1* p, void* stream) {
   }
   if (!p->x || !p->signal || !p->image || !p->quad) return ZK_EINVAL;
   int chunks = 0;
-  if (mnn_bwd_geometry(p->N, p->Dsel, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
+  if (mnn_bwd_geometry(p->N, p->Dsel, MNN_BWD_BLOCKS, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
   a.x = (const float*)p->x; a.signal = (const float*)p->signal; a.image = (const float*)p->image; a.quad = (const float*)p->quad; a.feat = (const int*)p->feat;
   a.gy = (const float*)p->gy; a.gl = (const float*)p->gl; a.gx = (float*)p->gx; a.gsignal = (float*)p->gsignal;
   a.work = p->gparams ? (float*)p->work : nullptr;
@@ -407,23 +336,12 @@ static int umnn_backward(const zk_umnn_bwd_args_v1* p, void* stream) {
 }  // namespace zk
 
 extern "C" int zk_umnn_backward(const zk_umnn_bwd_args_v1* args, void* stream) { return zk::umnn_backward(args, stream); }
-extern "C" int zk_umnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks) { return zk::mnn_bwd_geometry(N, Dsel, rows_per_chunk, n_chunks); }
+extern "C" int zk_umnn_backward_geometry(int64_t N, int64_t Dsel, int* rows_per_chunk, int* n_chunks) {
+  return zk::mnn_bwd_geometry(N, Dsel, MNN_BWD_BLOCKS, rows_per_chunk, n_chunks);
+}
 extern "C" int zk_umnn_backward_floats(int S, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats) {
-  zk::MnnLayout L;
-  zk::MnnBwdLayout B;
-  if (!image_floats || !grad_floats || !zk::umnn_bwd_shape(S, n_hidden, width0, width1, width2, &L, &B)) return ZK_EINVAL;
-  *image_floats = B.total;
-  *grad_floats = B.g_total;
-  return 0;
+  return zk::mnn_bwd_floats<2 * UMNN_QUAD_MAX>(S, n_hidden, width0, width1, width2, image_floats, grad_floats);
 }
 extern "C" int zk_umnn_backward_workspace_floats(int64_t N, int64_t Dsel, int S, int n_hidden, int width0, int width1, int width2, int64_t* floats) {
-  zk::MnnLayout L;
-  zk::MnnBwdLayout B;
-  if (!floats || !zk::umnn_bwd_shape(S, n_hidden, width0, width1, width2, &L, &B)) return ZK_EINVAL;
-  *floats = 0;
-  if (N == 0 && Dsel >= 1 && Dsel <= 65535) return 0;
-  int rows = 0, chunks = 0;
-  if (zk::mnn_bwd_geometry(N, Dsel, &rows, &chunks) != 0) return ZK_EINVAL;
-  *floats = (int64_t)chunks * Dsel * B.g_total;
-  return 0;
+  return zk::mnn_bwd_workspace_floats<2 * UMNN_QUAD_MAX>(N, Dsel, S, n_hidden, width0, width1, width2, floats);
 }

@@ -1,5 +1,8 @@
 // zuko_amd — what the step kernel of the continuous flow (csrc/cnf.hip) and its adjoint (csrc/cnf_backward.hip) share: the layout of the field's
-// weight image, the Dormand-Prince tableau and the activation.  The two __global__ bodies and their sweeps are each file's own.
+// weight image, the Dormand-Prince tableau, the time embedding (cnf_embed), the first layer's pre-activation (cnf_first_layer) and the checks both
+// launchers make on t, dt, trace_scale and ld_pre (cnf_step_fields_ok).  The activation is mnn_elu of csrc/zk_mnn_common.h.  The last layer's product
+// stands in both files (sharing it cost the adjoint registers: profiles/small_net_frame/census.md); the two __global__ bodies and their sweeps are
+// each file's own.
 #pragma once
 #include "zk_mnn_common.h"
 #include <math.h>
@@ -56,11 +59,33 @@ static __constant__ float CNF_A[7][6] = {
 static __constant__ float CNF_E[7] = {(float)(35.0 / 384 - 5179.0 / 57600), 0.f, (float)(500.0 / 1113 - 7571.0 / 16695), (float)(125.0 / 192 - 393.0 / 640),
                                       (float)(92097.0 / 339200 - 2187.0 / 6784), (float)(11.0 / 84 - 187.0 / 2100), -(float)(1.0 / 40)};
 
-// ELU(alpha = 1) and its derivative
-__device__ __forceinline__ void cnf_act(float p, float& v, float& d) {
-  v = p > 0.f ? p : expm1f(p);
-  d = p > 0.f ? 1.f : expf(p);
+// element e of the time embedding (cos(fr ts), sin(fr ts)) of the image's Q frequencies; zero behind 2 Q
+__device__ __forceinline__ float cnf_embed(const CnfLayout& L, const float* lds, int e, float ts) {
+  const float arg = lds[L.o_fr + (e < L.Q ? e : (e < 2 * L.Q ? e - L.Q : 0))] * ts;
+  return e < L.Q ? cosf(arg) : (e < 2 * L.Q ? sinf(arg) : 0.f);
 }
-__device__ __forceinline__ float cnf_act(float p) { return p > 0.f ? p : expm1f(p); }
+
+// tile o of the first layer's pre-activation of the wave's rows: pre + W0t emb + W0x x
+__device__ __forceinline__ mnn_f4 cnf_first_layer(const CnfLayout& L, const float* lds, const float* __restrict__ prow, int lane, int q, int o, const float (&emb)[4],
+                                                  const float (&xin)[4]) {
+  const float* const pt = lds + L.o_w0t + lane;
+  const float* const px = lds + L.o_w0x + lane;
+  mnn_f4 c = *reinterpret_cast<const mnn_f4*>(prow + o * 16 + q * 4);
+  mnn_for<4>([&](auto s) MNN_INLINE {
+    if (s < L.kt) c = __builtin_amdgcn_mfma_f32_16x16x4f32(pt[(o * L.kt + s) * 64], emb[s], c, 0, 0, 0);
+  });
+  mnn_for<4>([&](auto s) MNN_INLINE {
+    if (s < L.kx) c = __builtin_amdgcn_mfma_f32_16x16x4f32(px[(o * L.kx + s) * 64], xin[s], c, 0, 0, 0);
+  });
+  return c;
+}
+
+// ---- host ----------------------------------------------------------------------------------------
+// what both launchers ask of the fields their argument blocks (zk_cnf_args_v1 / zk_cnf_adj_args_v1) name alike; `traced`: trace_scale is used
+template <class P> static inline bool cnf_step_fields_ok(const P* p, bool traced) {
+  if (p->ld_pre != 0 && (p->ld_pre < p->width0 || p->ld_pre % 4 != 0)) return false;
+  if (!std::isfinite(p->t) || !std::isfinite(p->dt)) return false;
+  return !traced || (p->trace_scale > 0 && std::isfinite(p->trace_scale));
+}
 
 }  // namespace zk

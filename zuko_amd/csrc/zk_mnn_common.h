@@ -1,6 +1,10 @@
 // zuko_amd — what the monotone-network kernels of NAF (csrc/mnn.hip) and UNAF (csrc/umnn.hip) share: the weight image's layout, the signal's share of
 // the first layer, the four-lane sum, the launch geometry, the checks on the fields their two argument blocks have in common, and the launch with
-// dynamic LDS.  The networks themselves (activations, tangent, quadrature) and the two __global__ bodies are each family's own.
+// dynamic LDS.  The networks themselves (tangent, quadrature) and the two __global__ bodies are each family's own.
+// For all six small-network kernels, the continuous flow's (csrc/cnf.hip) and the three adjoints included: ELU and its derivative (mnn_elu), the copy
+// of an image into LDS (mnn_stage_image) and the paired layer product of the forward kernels that run two wavefronts per SIMD (mnn_matvec: mnn_hidden
+// of NAF, the value and tangent products of CNF; umnn_hidden keeps its own unpaired one).  Where a kernel keeps a piece written out because the
+// shared one moved its instruction census: profiles/small_net_frame/census.md.
 #pragma once
 #include "../../include/zuko_amd.h"
 #include "zk_common.h"
@@ -73,6 +77,57 @@ __device__ __forceinline__ float mnn_sum_q(float p) {
   p += __shfl_xor(p, 16, 64);
   p += __shfl_xor(p, 32, 64);
   return p;
+}
+
+// ELU(alpha = 1), and with its derivative
+__device__ __forceinline__ float mnn_elu(float p) { return p > 0.f ? p : expm1f(p); }
+__device__ __forceinline__ void mnn_elu(float p, float& v, float& d) {
+  v = p > 0.f ? p : expm1f(p);
+  d = p > 0.f ? 1.f : expf(p);
+}
+
+// the block copies `floats` (a multiple of 4) of a 16-byte aligned image into LDS; the caller's barrier follows
+__device__ __forceinline__ void mnn_stage_image(float* lds, const float* __restrict__ image, int floats, int tid) {
+  for (int i = tid * 4; i < floats; i += MNN_THREADS * 4) *reinterpret_cast<mnn_f4*>(lds + i) = *reinterpret_cast<const mnn_f4*>(image + i);
+}
+
+// out[g] = W in[g] (+ b for the first NB members) for G right-hand sides at once, the form of the forward kernels that run two wavefronts per SIMD:
+// the A fragment of an (out tile, in tile) pair is read once and feeds 4 G products; out tiles go in pairs, so 2 G accumulator chains are independent
+// and the second tile's reads are immediate offsets of the first's.  tin / tout tiles; the tiles of one out tile are consecutive in the image.  in[g] /
+// out[g] are the tile arrays of member g: a [G][TM] array, an array of G pointers, or &tiles for a single member.
+template <int TM, int G, int NB, class In, class Out>
+__device__ __forceinline__ void mnn_matvec(const float* W, const float* B, int tin, int tout, int lane, int q, In in, Out out) {
+  const int rowstride = tin * 256;
+  mnn_for<TM / 2>([&](auto P) MNN_INLINE {
+    constexpr int o0 = 2 * P, o1 = o0 + 1;
+    if (o0 < tout) {
+      const bool two = o1 < tout;
+      const float* const p0 = W + o0 * rowstride + lane * 4;
+      const float* const p1 = p0 + rowstride;
+      mnn_for<G>([&](auto g) MNN_INLINE {
+        out[g][o0] = mnn_f4{0.f, 0.f, 0.f, 0.f};
+        out[g][o1] = mnn_f4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (g < NB) {
+          out[g][o0] = *reinterpret_cast<const mnn_f4*>(B + o0 * 16 + q * 4);
+          if (two) out[g][o1] = *reinterpret_cast<const mnn_f4*>(B + o1 * 16 + q * 4);
+        }
+      });
+      mnn_for<TM>([&](auto it) MNN_INLINE {
+        if (it < tin) {
+          const mnn_f4 a0 = *reinterpret_cast<const mnn_f4*>(p0 + it * 256);
+          mnn_for<4>([&](auto r) MNN_INLINE {
+            mnn_for<G>([&](auto g) MNN_INLINE { out[g][o0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[(int)r], in[g][it][(int)r], out[g][o0], 0, 0, 0); });
+          });
+          if (two) {
+            const mnn_f4 a1 = *reinterpret_cast<const mnn_f4*>(p1 + it * 256);
+            mnn_for<4>([&](auto r) MNN_INLINE {
+              mnn_for<G>([&](auto g) MNN_INLINE { out[g][o1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[(int)r], in[g][it][(int)r], out[g][o1], 0, 0, 0); });
+            });
+          }
+        }
+      });
+    }
+  });
 }
 
 // ---- host ----------------------------------------------------------------------------------------
