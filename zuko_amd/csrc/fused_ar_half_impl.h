@@ -43,6 +43,12 @@
 #ifndef ARH_PREFETCH
 #define ARH_PREFETCH 1  // probe builds: 0 = a tile's x rows and its log-derivative are requested where they are consumed
 #endif
+#ifndef ARH_BLOCK_ASM
+#define ARH_BLOCK_ASM 1  // probe builds: 0 = a block's counted wait as an asm statement that defines the images, its matrix instructions the compiler's (arh_settle, arh_block: one s_nop between them)
+#endif
+#ifndef ARH_EPI_TILE
+#define ARH_EPI_TILE 1  // probe builds: 0 = ReLU and the sample maximum of a hidden layer behind the whole layer (1: behind every out tile's descale, among the matrix instructions)
+#endif
 
 namespace zk {
 
@@ -82,17 +88,20 @@ __device__ __forceinline__ void arh_split(const f32x4& lo, const f32x4& hi, floa
   //   h = f16(fma(v, s, -0))   v s is exact (s is a power of two) and -0 keeps the sign of a zero: the bits of (_Float16)(v * s)
   //   l = f16(fma(v, s, -h))   v s - h is exact in f32: the bits of (_Float16)(v * s - (float)h)
   // (v s below the f32 normal range: |v s| < 2^-126 gives h = 0 and l = 0 either way.)  mixlo / mixhi write one half of the destination.
+  // ONE statement per call (sixteen single-instruction statements: the compiler pads a statement that reads what the one in front of it wrote).
   const float nz = -0.f;
-  arh_u32x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(h[e]) : "v"(e < 2 ? lo[2 * e] : hi[2 * e - 4]), "v"(s), "s"(nz));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) asm("v_fma_mixhi_f16 %0, %1, %2, %3" : "+v"(h[e]) : "v"(e < 2 ? lo[2 * e + 1] : hi[2 * e - 3]), "v"(s), "s"(nz));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l[e]) : "v"(e < 2 ? lo[2 * e] : hi[2 * e - 4]), "v"(s), "v"(h[e]));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l[e]) : "v"(e < 2 ? lo[2 * e + 1] : hi[2 * e - 3]), "v"(s), "v"(h[e]));
-  b.h = __builtin_bit_cast(f16x8, h); b.l = __builtin_bit_cast(f16x8, l);
+  unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+#define ARH_SPLIT_H(OP, H, V) "v_fma_mix" OP "_f16 %[" H "], %[" V "], %[s], %[nz]\n\t"
+#define ARH_SPLIT_L(OP, SEL, L, H, V) "v_fma_mix" OP "_f16 %[" L "], %[" V "], %[s], -%[" H "] op_sel:[0,0," SEL "] op_sel_hi:[0,0,1]\n\t"
+  asm(ARH_SPLIT_H("lo", "h0", "v0") ARH_SPLIT_H("lo", "h1", "v2") ARH_SPLIT_H("lo", "h2", "v4") ARH_SPLIT_H("lo", "h3", "v6")
+      ARH_SPLIT_H("hi", "h0", "v1") ARH_SPLIT_H("hi", "h1", "v3") ARH_SPLIT_H("hi", "h2", "v5") ARH_SPLIT_H("hi", "h3", "v7")
+      ARH_SPLIT_L("lo", "0", "l0", "h0", "v0") ARH_SPLIT_L("lo", "0", "l1", "h1", "v2") ARH_SPLIT_L("lo", "0", "l2", "h2", "v4") ARH_SPLIT_L("lo", "0", "l3", "h3", "v6")
+      ARH_SPLIT_L("hi", "1", "l0", "h0", "v1") ARH_SPLIT_L("hi", "1", "l1", "h1", "v3") ARH_SPLIT_L("hi", "1", "l2", "h2", "v5") ARH_SPLIT_L("hi", "1", "l3", "h3", "v7")
+      : [h0] "=&v"(h0), [h1] "=&v"(h1), [h2] "=&v"(h2), [h3] "=&v"(h3), [l0] "=&v"(l0), [l1] "=&v"(l1), [l2] "=&v"(l2), [l3] "=&v"(l3)
+      : [v0] "v"(lo[0]), [v1] "v"(lo[1]), [v2] "v"(lo[2]), [v3] "v"(lo[3]), [v4] "v"(hi[0]), [v5] "v"(hi[1]), [v6] "v"(hi[2]), [v7] "v"(hi[3]), [s] "v"(s), [nz] "s"(nz));
+#undef ARH_SPLIT_H
+#undef ARH_SPLIT_L
+  b.h = __builtin_bit_cast(f16x8, arh_u32x4{h0, h1, h2, h3}); b.l = __builtin_bit_cast(f16x8, arh_u32x4{l0, l1, l2, l3});
   return;
 #endif
 #pragma unroll
@@ -120,6 +129,67 @@ __device__ __forceinline__ void arh_block(const f32x4 (&a)[2], const ArhB& b, f3
 __device__ __forceinline__ void arh_touch(f32x4& v) { asm volatile("" : "+v"(v)); }  // a raw-read register becomes usable HERE (behind the counted wait that settled it)
 template <int N> __device__ __forceinline__ void arh_settle(f32x4& a0, f32x4& a1) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a0), "+v"(a1) : "n"(N)); }
 template <int N> __device__ __forceinline__ void arh_settle(f32x4& a0, f32x4& a1, f32x4& a2) { asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a0), "+v"(a1), "+v"(a2) : "n"(N)); }
+
+// A block without the compiler's pad: the counted wait that settles its weight images as the COMPILER's instruction (__builtin_amdgcn_s_waitcnt),
+// the three partial products (arh_block's, in its order) as ONE statement behind it.  The compiler's hazard recogniser pads any asm statement, and
+// any matrix instruction, that reads or writes a register an asm statement in front of it defined while nothing but asm statements stands between
+// the two (they count as no wait state).  The raw weight reads are asm statements, so a wait written as an asm statement draws one s_nop per block,
+// on whichever side of it the matrix instructions' statement begins; the builtin is an instruction of the compiler's own and is the one wait state
+// the rule asks for.  Inside the string nothing is padded, so the wait states are written here:
+//   FIRST  a tile's first block: the accumulator starts from the inline constant 0 (early-clobber: written before the last operand is read)
+//   PAD    a layer's first block: its B operands may have been written by the vector instruction in front of the wait (arh_split), and a matrix
+//          instruction reads a just-written operand two wait states later at the earliest: one more state in front of the wait
+//   TILE   a hidden tile's last block: the bias tile `bs` counts as settled behind the wait (a raw read, as the images), and the twelve wait states
+//          between the tile's last matrix instruction and the vector instruction that reads the accumulator (the descale) end the string
+// (the last layer's groups place their twelve states themselves: arh_acc_ready).  The images are inputs: what orders the matrix instructions behind
+// the wait is the statement order of a builtin with side effects and a volatile asm, and the scheduling fence between them.
+constexpr bool ARH_BLK = ARH_BLOCK_ASM && ARX_ABL != 2;
+#define ARH_BLK_ASM(C0, COUT, POST, BSOUT)                                                                  \
+  asm volatile("v_mfma_f32_16x16x32_f16 %[c], %[al], %[bh], " C0 "\n\t"                                     \
+               "v_mfma_f32_16x16x32_f16 %[c], %[ah], %[bl], %[c]\n\t"                                       \
+               "v_mfma_f32_16x16x32_f16 %[c], %[ah], %[bh], %[c]" POST                                      \
+               : [c] COUT(c) ARH_BLK_BS##BSOUT                                                              \
+               : [ah] "v"(a[0]), [al] "v"(a[1]), [bh] "v"(b.h), [bl] "v"(b.l))
+#define ARH_BLK_BS0
+#define ARH_BLK_BS1 , "+v"(bs)
+template <int N, bool FIRST, bool PAD, bool TILE> __device__ __forceinline__ void arh_wait_block(f32x4 (&a)[2], const ArhB& b, f32x4& c, f32x4& bs) {
+  static_assert(N >= 0 && N < 16, "lgkmcnt is a four-bit field");
+  if constexpr (PAD) asm volatile("s_nop 0");
+  __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));  // lgkmcnt(N); vmcnt and expcnt at their maxima: not waited for
+  if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+  if constexpr (FIRST && TILE) ARH_BLK_ASM("0", "=&v", "\n\ts_nop 11", 1);
+  else if constexpr (FIRST) ARH_BLK_ASM("0", "=&v", "", 0);
+  else if constexpr (TILE) ARH_BLK_ASM("%[c]", "+v", "\n\ts_nop 11", 1);
+  else ARH_BLK_ASM("%[c]", "+v", "", 0);
+  if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+}
+#undef ARH_BLK_ASM
+#undef ARH_BLK_BS0
+#undef ARH_BLK_BS1
+// the accumulators of a last-layer group become readable: twelve wait states behind the group's last matrix instruction (the other tiles' last
+// ones stand in front of it)
+template <int NT> __device__ __forceinline__ void arh_acc_ready(f32x4 (&acc)[NT]) {
+  asm volatile("s_nop 11" : "+v"(acc[NT - 1]));
+#pragma unroll
+  for (int t = 0; t + 1 < NT; ++t) arh_touch(acc[t]);
+}
+
+// ReLU of an out tile's four values and their entry into the sample maximum: ONE v_max_f32 per value, one v_max3_f32 per pair, a pair per statement.
+// The maximum is kept as FOUR partial maxima (pm: non-negative, joined by arh_join_max) so that no v_max3_f32 waits for the one in front of it;
+// max is exact, so the sample's maximum is the same bits in any order.  The max turns a NaN into 0, so no NaN may reach a hidden value: x, weights
+// and biases are finite (poison; zuko_amd/fused.py: half_scales), products and sums of the f16 parts stay far inside f32, and the descale fma of
+// finite operands gives a finite value or an infinity — which survives the max and is caught at the sample's maximum (arh_hidden_stack's poison:
+// the next layer would compute inf - inf from it).
+__device__ __forceinline__ void arh_relu_max(f32x4& o, float (&pm)[4], int t) {
+#pragma unroll
+  for (int r = 0; r < 4; r += 2)  // (pinned: behind a packed fma the compiler puts a canonicalising v_max in front of fmaxf)
+    asm("v_max_f32 %0, 0, %0\n\tv_max_f32 %1, 0, %1\n\tv_max3_f32 %2, %2, %0, %1" : "+v"(o[r]), "+v"(o[r + 1]), "+v"(pm[(2 * t + r / 2) % 4]));
+}
+__device__ __forceinline__ float arh_join_max(const float (&pm)[4]) {
+  float amax;
+  asm("v_max_f32 %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4" : "=&v"(amax) : "v"(pm[0]), "v"(pm[1]), "v"(pm[2]), "v"(pm[3]));
+  return amax;
+}
 
 // The ring of fused_ar_static_impl.h with a counted wait that knows about XV vector-memory loads YOUNGER than the chunk requested last (the
 // next tile's x rows: arh_kernel).  Loads return in order: with the two youngest groups (XV loads, PER copies) still in flight, the chunk
@@ -266,12 +336,18 @@ template <class S, int L, bool ALT> constexpr int arh_ip(int s) {  // the in pai
 }
 // (ALT, the flow kernel's first layer only: the blocks take the in pairs S::B_IP_ALT names — the pattern of the flow's OTHER feature order, which
 //  differs from this one in nothing else)
-template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d) {
+// (EPI — the pinned ReLU path with ARH_EPI_TILE: an out tile's ReLU and its entry into the sample's partial maxima pm stand behind the tile's descale,
+//  among the matrix instructions of the tiles that follow; nothing of them needs the whole layer)
+template <class S> constexpr bool ARH_EPI = S::ACT == 1 && ARH_EPI_PINNED && ARH_EPI_TILE;
+template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d, float (&pm)[4]) {
   typedef ArxPat<S> P;
   constexpr int NB = S::NB[L], BASE = S::BASE[L], HTL = S::HT[L];
   ars_for<HTL>([&](auto t_) ARS_ALWAYS_INLINE {
     constexpr int t = t_;
-    if constexpr (!P::tile_has_blocks(L, t)) out[t] = *reinterpret_cast<const f32x4*>(bias_q + t * 16);  // units that depend on nothing: bias only
+    if constexpr (!P::tile_has_blocks(L, t)) {
+      out[t] = *reinterpret_cast<const f32x4*>(bias_q + t * 16);  // units that depend on nothing: bias only
+      if constexpr (ARH_EPI<S>) arh_relu_max(out[t], pm, t);
+    }
   });
   if constexpr (NB > 0) {
     constexpr int LOOK = ARH_LOOK < NB ? ARH_LOOK : NB;
@@ -287,7 +363,7 @@ template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline
       constexpr int s = s_, ot = P::ot(L, s), cur = s % (LOOK + 1);
       constexpr int ip = arh_ip<S, L, ALT>(s);
       constexpr bool first_of_tile = (s == 0 || P::ot(L, s - 1) != ot), last_of_tile = (s + 1 == NB || P::ot(L, s + 1) != ot);
-      if constexpr (first_of_tile) acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (first_of_tile && !ARH_BLK) acc = f32x4{0.f, 0.f, 0.f, 0.f};
       if constexpr (last_of_tile) bs = arx_lds_raw<ot * 64>(bias_addr);
       if constexpr (s + LOOK < NB) {
         constexpr int nx = (s + LOOK) % (LOOK + 1);
@@ -295,11 +371,15 @@ template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline
       }
       constexpr int ahead = (s + LOOK < NB ? LOOK : NB - 1 - s);  // blocks behind this one whose images may still be outstanding
       // (a tile's last block: only THIS step's request is younger than the bias read — the wait that settles it also settles the blocks in between)
-      if constexpr (last_of_tile) arh_settle<(s + LOOK < NB ? 2 : 0)>(a[cur][0], a[cur][1], bs);
-      else arh_settle<2 * ahead>(a[cur][0], a[cur][1]);
-      if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
-      arh_block(a[cur], in[ip], acc);
-      if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+      if constexpr (ARH_BLK) {
+        arh_wait_block<(last_of_tile ? (s + LOOK < NB ? 2 : 0) : 2 * ahead), first_of_tile, s == 0, last_of_tile>(a[cur], in[ip], acc, bs);
+      } else {
+        if constexpr (last_of_tile) arh_settle<(s + LOOK < NB ? 2 : 0)>(a[cur][0], a[cur][1], bs);
+        else arh_settle<2 * ahead>(a[cur][0], a[cur][1]);
+        if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+        arh_block(a[cur], in[ip], acc);
+        if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+      }
       if constexpr (last_of_tile) {
         if (ARH_DESCALE_PK) {
 #pragma unroll
@@ -311,6 +391,7 @@ template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline
 #pragma unroll
           for (int r = 0; r < 4; ++r) out[ot][r] = __builtin_fmaf(acc[r], d, bs[r]);
         }
+        if constexpr (ARH_EPI<S>) arh_relu_max(out[ot], pm, ot);
       }
     });
   }
@@ -321,28 +402,23 @@ template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline
 template <class S, int L, class Ring, bool HAS_ALT = false> __device__ __forceinline__ void arh_hidden_stack(Ring& ring, const float* bias_lds, int q, ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], const float* wd,
                                                                                                          float& inv_s, float& poison, bool alt = false) {
   if constexpr (L < S::NH) {
+    float pm[4] = {0.f, 0.f, 0.f, 0.f};  // partial maxima of the layer's ReLU outputs (the pinned ReLU path: arh_relu_max)
     if constexpr (HAS_ALT && L == 0) {
       static_assert(S::BASE[0] == 0, "B_IP_ALT lists the first layer's blocks");
-      if (alt) arh_hidden<S, L, Ring, true>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s);
-      else arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s);
+      if (alt) arh_hidden<S, L, Ring, true>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm);
+      else arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm);
     } else {
-      arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s);
+      arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm);
     }
     constexpr int HTL = S::HT[L];
     float amax = 0.f;
     if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
-      // ReLU as ONE v_max_f32 per value, the sample's maximum as one v_max3_f32 per pair.  The max turns a NaN into 0, so no NaN may
-      // reach a hidden value: x, weights and biases are finite (poison below; zuko_amd/fused.py: half_scales), products and sums of the
-      // f16 parts stay far inside f32, and the descale fma of finite operands gives a finite value or an infinity — which survives the
-      // max and is caught at the sample's maximum (arh_hidden_stack's poison: the next layer would compute inf - inf from it).
+      // (arh_relu_max: with ARH_EPI_TILE every tile has been through it inside arh_hidden)
+      if constexpr (!ARH_EPI_TILE) {
 #pragma unroll
-      for (int t = 0; t < HTL; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          asm("v_max_f32 %0, 0, %0" : "+v"(out[t][r]));  // (pinned: behind a packed fma the compiler puts a canonicalising v_max in front of fmaxf)
-          asm("v_max_f32 %0, 0, %0" : "+v"(out[t][r + 1]));
-          asm("v_max3_f32 %0, %0, %1, %2" : "+v"(amax) : "v"(out[t][r]), "v"(out[t][r + 1]));
-        }
+        for (int t = 0; t < HTL; ++t) arh_relu_max(out[t], pm, t);
+      }
+      amax = arh_join_max(pm);
     } else if constexpr (S::ACT == 1) {
 #pragma unroll
       for (int t = 0; t < HTL; ++t)
@@ -512,7 +588,7 @@ __device__ __forceinline__ void arh_pass(const ArArgs& a, Ring& ring, XReq& x_re
       const float* bg = bias_last + (g * NT) * 16 + 4 * q;
       ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { bs[t] = *reinterpret_cast<const f32x4*>(bg + t * 16); });
     }
-    ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+    if constexpr (GN == 0 || !ARH_BLK) ars_for<NT>([&](auto t) ARS_ALWAYS_INLINE { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; });
     ars_for<GN>([&](auto i_) ARS_ALWAYS_INLINE {
       constexpr int st = ST0 + decltype(i_)::value, ip = S::G_IP[st];
       ars_for<NT>([&](auto t_) ARS_ALWAYS_INLINE {
@@ -526,15 +602,24 @@ __device__ __forceinline__ void arh_pass(const ArArgs& a, Ring& ring, XReq& x_re
           ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[nx][p] = ARH_READ_LAST(S::LAST_BASE + 2 * (blk + LOOKL) + decltype(p)::value); });
         }
         constexpr int ahead = (blk + LOOKL < NBL ? LOOKL : NBL - 1 - blk);
-        if constexpr (last_of_group) arh_settle<(blk + LOOKL < NBL ? 2 : 0)>(w[cur][0], w[cur][1]);
-        else arh_settle<2 * ahead>(w[cur][0], w[cur][1]);
-        if constexpr (last_of_group) {  // (the bias tiles are older than this step's request: the same wait has settled them)
+        if constexpr (ARH_BLK) {
+          arh_wait_block<(last_of_group ? (blk + LOOKL < NBL ? 2 : 0) : 2 * ahead), decltype(i_)::value == 0, blk == 0, false>(w[cur], in[ip], acc[t], bs[0]);
+          if constexpr (last_of_group) {  // (the bias tiles are older than this step's request: the block's wait has settled them)
 #pragma unroll
-          for (int u = 0; u < NT; ++u) arh_touch(bs[u]);
+            for (int u = 0; u < NT; ++u) arh_touch(bs[u]);
+            arh_acc_ready<NT>(acc);
+          }
+        } else {
+          if constexpr (last_of_group) arh_settle<(blk + LOOKL < NBL ? 2 : 0)>(w[cur][0], w[cur][1]);
+          else arh_settle<2 * ahead>(w[cur][0], w[cur][1]);
+          if constexpr (last_of_group) {  // (the bias tiles are older than this step's request: the same wait has settled them)
+#pragma unroll
+            for (int u = 0; u < NT; ++u) arh_touch(bs[u]);
+          }
+          if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+          arh_block(w[cur], in[ip], acc[t]);
+          if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
         }
-        if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
-        arh_block(w[cur], in[ip], acc[t]);
-        if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
       });
     });
     float p[4 * NT];
