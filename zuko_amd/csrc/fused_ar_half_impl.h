@@ -50,6 +50,10 @@
 #define ARH_EPI_TILE 1  // probe builds: 0 = ReLU and the sample maximum of a hidden layer behind the whole layer (1: behind every out tile's descale, among the matrix instructions)
 #endif
 
+#ifndef ARH_SPLIT_GAPS
+#define ARH_SPLIT_GAPS 1  // 0 = every in pair of a layer is split in front of the layer (1: pair p + 1 one instruction per gap among the matrix instructions of the blocks in front of its first reader: arh_gap_plan; profiles/half_gaps/README.md)
+#endif
+
 namespace zk {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -144,28 +148,175 @@ template <int N> __device__ __forceinline__ void arh_settle(f32x4& a0, f32x4& a1
 // (the last layer's groups place their twelve states themselves: arh_acc_ready).  The images are inputs: what orders the matrix instructions behind
 // the wait is the statement order of a builtin with side effects and a volatile asm, and the scheduling fence between them.
 constexpr bool ARH_BLK = ARH_BLOCK_ASM && ARX_ABL != 2;
-#define ARH_BLK_ASM(C0, COUT, POST, BSOUT)                                                                  \
-  asm volatile("v_mfma_f32_16x16x32_f16 %[c], %[al], %[bh], " C0 "\n\t"                                     \
-               "v_mfma_f32_16x16x32_f16 %[c], %[ah], %[bl], %[c]\n\t"                                       \
-               "v_mfma_f32_16x16x32_f16 %[c], %[ah], %[bh], %[c]" POST                                      \
-               : [c] COUT(c) ARH_BLK_BS##BSOUT                                                              \
-               : [ah] "v"(a[0]), [al] "v"(a[1]), [bh] "v"(b.h), [bl] "v"(b.l))
+// GAPS (ARH_SPLIT_GAPS): the block carries one form of an in pair's operand split, ONE v_fma_mix*_f16 behind each of its matrix instructions.  A
+// v_mfma_f32_16x16x32_f16 holds the SIMD's vector issue for half of its time; with both wavefronts of a SIMD issuing matrix instructions one
+// v_fma_mix*_f16 (or transcendental) or two v_fma_f32 / v_max_f32 / v_cndmask_b32 per gap cost 1.8 cycles per matrix instruction together, a
+// second v_fma_mix*_f16 6.5 more, one packed f32 instruction 13.6 (scripts/probes/gap_fill_probe.hip, profiles/half_gaps/gap_fill_probe.txt).
+// The sixteen instructions of arh_split, in its order, are the forms 1..6 (3, 3, 3, 3, 3, 1: the gap behind the last block of a split stays
+// empty, so the pair's first reader never follows its last write directly); they work on the pair's eight registers as scalars (ArhHL).
+constexpr bool ARH_GAPS = ARH_SPLIT_GAPS && ARH_BLK && ARH_EPI_PINNED && ARX_ABL != 6;
+struct ArhHL {  // the registers of an ArhB while its split is under way
+  unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+};
+#define ARH_GH(OP, H, V) "\n\tv_fma_mix" OP "_f16 %[" H "], %[" V "], %[s], %[nz]"
+#define ARH_GL(OP, SEL, L, H, V) "\n\tv_fma_mix" OP "_f16 %[" L "], %[" V "], %[s], -%[" H "] op_sel:[0,0," SEL "] op_sel_hi:[0,0,1]"
+#define ARH_G0 ARH_GH("lo", "h0", "v0")
+#define ARH_G1 ARH_GH("lo", "h1", "v2")
+#define ARH_G2 ARH_GH("lo", "h2", "v4")
+#define ARH_G3 ARH_GH("lo", "h3", "v6")
+#define ARH_G4 ARH_GH("hi", "h0", "v1")
+#define ARH_G5 ARH_GH("hi", "h1", "v3")
+#define ARH_G6 ARH_GH("hi", "h2", "v5")
+#define ARH_G7 ARH_GH("hi", "h3", "v7")
+#define ARH_G8 ARH_GL("lo", "0", "l0", "h0", "v0")
+#define ARH_G9 ARH_GL("lo", "0", "l1", "h1", "v2")
+#define ARH_G10 ARH_GL("lo", "0", "l2", "h2", "v4")
+#define ARH_G11 ARH_GL("lo", "0", "l3", "h3", "v6")
+#define ARH_G12 ARH_GL("hi", "1", "l0", "h0", "v1")
+#define ARH_G13 ARH_GL("hi", "1", "l1", "h1", "v3")
+#define ARH_G14 ARH_GL("hi", "1", "l2", "h2", "v5")
+#define ARH_G15 ARH_GL("hi", "1", "l3", "h3", "v7")
+// operands per form: a register's first write is early-clobber (the statement reads other inputs behind it), the later ones update it
+#define ARH_G_OUT0
+#define ARH_G_IN0
+#define ARH_G_SC [s] "v"(s), [nz] "s"(nz)
+#define ARH_G_OUT1 , [h0] "=&v"(x.h0), [l0] "=&v"(x.l0)
+#define ARH_G_IN1 , [v0] "v"(lo[0]), [v1] "v"(lo[1]), ARH_G_SC
+#define ARH_G_OUT2 , [l0] "+v"(x.l0), [h1] "=&v"(x.h1)
+#define ARH_G_IN2 , [v1] "v"(lo[1]), [h0] "v"(x.h0), [v2] "v"(lo[2]), [v3] "v"(lo[3]), ARH_G_SC
+#define ARH_G_OUT3 , [l1] "=&v"(x.l1), [h2] "=&v"(x.h2)
+#define ARH_G_IN3 , [v2] "v"(lo[2]), [v3] "v"(lo[3]), [h1] "v"(x.h1), [v4] "v"(hi[0]), ARH_G_SC
+#define ARH_G_OUT4 , [h2] "+v"(x.h2), [l2] "=&v"(x.l2)
+#define ARH_G_IN4 , [v5] "v"(hi[1]), [v4] "v"(hi[0]), ARH_G_SC
+#define ARH_G_OUT5 , [h3] "=&v"(x.h3), [l3] "=&v"(x.l3)
+#define ARH_G_IN5 , [v6] "v"(hi[2]), [v7] "v"(hi[3]), ARH_G_SC
+#define ARH_G_OUT6 , [l3] "+v"(x.l3)
+#define ARH_G_IN6 , [v7] "v"(hi[3]), [h3] "v"(x.h3), [s] "v"(s)
+// the forms F..6 as one statement (F >= 2): what the forms in front of F have defined is updated or read, the rest is defined here — early-clobber
+// as well: an update of a register nothing has defined yet may be given the register of an input the statement still reads
+#define ARH_T_OUT2 [l0] "+v"(x.l0), [h1] "=&v"(x.h1), [l1] "=&v"(x.l1), [h2] "=&v"(x.h2), [l2] "=&v"(x.l2), [h3] "=&v"(x.h3), [l3] "=&v"(x.l3)
+#define ARH_T_IN2 [v1] "v"(lo[1]), [v2] "v"(lo[2]), [v3] "v"(lo[3]), [v4] "v"(hi[0]), [v5] "v"(hi[1]), [v6] "v"(hi[2]), [v7] "v"(hi[3]), [h0] "v"(x.h0), ARH_G_SC
+#define ARH_T_OUT3 [l1] "=&v"(x.l1), [h2] "=&v"(x.h2), [l2] "=&v"(x.l2), [h3] "=&v"(x.h3), [l3] "=&v"(x.l3)
+#define ARH_T_IN3 [v2] "v"(lo[2]), [v3] "v"(lo[3]), [v4] "v"(hi[0]), [v5] "v"(hi[1]), [v6] "v"(hi[2]), [v7] "v"(hi[3]), [h1] "v"(x.h1), ARH_G_SC
+#define ARH_T_OUT4 [h2] "+v"(x.h2), [l2] "=&v"(x.l2), [h3] "=&v"(x.h3), [l3] "=&v"(x.l3)
+#define ARH_T_IN4 [v4] "v"(hi[0]), [v5] "v"(hi[1]), [v6] "v"(hi[2]), [v7] "v"(hi[3]), ARH_G_SC
+#define ARH_T_OUT5 [h3] "=&v"(x.h3), [l3] "=&v"(x.l3)
+#define ARH_T_IN5 [v6] "v"(hi[2]), [v7] "v"(hi[3]), ARH_G_SC
+#define ARH_T_OUT6 [l3] "+v"(x.l3)
+#define ARH_T_IN6 [v7] "v"(hi[3]), [h3] "v"(x.h3), [s] "v"(s)
+#define ARH_BLK_ASM(C0, COUT, POST, BSOUT, G1, G2, G3, G)                                                   \
+  asm volatile("v_mfma_f32_16x16x32_f16 %[c], %[al], %[bh], " C0 G1 "\n\t"                                  \
+               "v_mfma_f32_16x16x32_f16 %[c], %[ah], %[bl], %[c]" G2 "\n\t"                                 \
+               "v_mfma_f32_16x16x32_f16 %[c], %[ah], %[bh], %[c]" G3 POST                                   \
+               : [c] COUT(c) ARH_BLK_BS##BSOUT ARH_G_OUT##G                                                 \
+               : [ah] "v"(a[0]), [al] "v"(a[1]), [bh] "v"(b.h), [bl] "v"(b.l) ARH_G_IN##G)
 #define ARH_BLK_BS0
 #define ARH_BLK_BS1 , "+v"(bs)
+#define ARH_BLK_FORM(G1, G2, G3, G)                                                               \
+  if constexpr (FIRST && TILE) ARH_BLK_ASM("0", "=&v", "\n\ts_nop 11", 1, G1, G2, G3, G);          \
+  else if constexpr (FIRST) ARH_BLK_ASM("0", "=&v", "", 0, G1, G2, G3, G);                         \
+  else if constexpr (TILE) ARH_BLK_ASM("%[c]", "+v", "\n\ts_nop 11", 1, G1, G2, G3, G);            \
+  else ARH_BLK_ASM("%[c]", "+v", "", 0, G1, G2, G3, G)
 template <int N, bool FIRST, bool PAD, bool TILE> __device__ __forceinline__ void arh_wait_block(f32x4 (&a)[2], const ArhB& b, f32x4& c, f32x4& bs) {
   static_assert(N >= 0 && N < 16, "lgkmcnt is a four-bit field");
   if constexpr (PAD) asm volatile("s_nop 0");
   __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));  // lgkmcnt(N); vmcnt and expcnt at their maxima: not waited for
   if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
-  if constexpr (FIRST && TILE) ARH_BLK_ASM("0", "=&v", "\n\ts_nop 11", 1);
-  else if constexpr (FIRST) ARH_BLK_ASM("0", "=&v", "", 0);
-  else if constexpr (TILE) ARH_BLK_ASM("%[c]", "+v", "\n\ts_nop 11", 1);
-  else ARH_BLK_ASM("%[c]", "+v", "", 0);
+  ARH_BLK_FORM("", "", "", 0);
   if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
 }
+// the same block with form GF (1..6) of the split of (lo, hi) by the scale s in its gaps
+template <int N, bool FIRST, bool PAD, bool TILE, int GF>
+__device__ __forceinline__ void arh_wait_block(f32x4 (&a)[2], const ArhB& b, f32x4& c, f32x4& bs, ArhHL& x, const f32x4& lo, const f32x4& hi, float s) {
+  static_assert(N >= 0 && N < 16 && GF >= 1 && GF <= 6, "lgkmcnt is a four-bit field; six forms");
+  const float nz = -0.f;
+  if constexpr (PAD) asm volatile("s_nop 0");
+  __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
+  if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+  if constexpr (GF == 1) { ARH_BLK_FORM(ARH_G0, ARH_G4, ARH_G8, 1); }
+  else if constexpr (GF == 2) { ARH_BLK_FORM(ARH_G12, ARH_G1, ARH_G5, 2); }
+  else if constexpr (GF == 3) { ARH_BLK_FORM(ARH_G9, ARH_G13, ARH_G2, 3); }
+  else if constexpr (GF == 4) { ARH_BLK_FORM(ARH_G6, ARH_G10, ARH_G14, 4); }
+  else if constexpr (GF == 5) { ARH_BLK_FORM(ARH_G3, ARH_G7, ARH_G11, 5); }
+  else { ARH_BLK_FORM(ARH_G15, "", "", 6); }
+  if (ARX_FENCE) __builtin_amdgcn_sched_barrier(0);
+}
+// the forms F..6 of a split as one statement: what found no block in front of the pair's first reader (all of it: arh_split)
+template <int F> __device__ __forceinline__ void arh_split_tail(ArhHL& x, const f32x4& lo, const f32x4& hi, float s) {
+  static_assert(F >= 2 && F <= 6, "six forms");
+  const float nz = -0.f;
+#define ARH_T6 ARH_G15
+#define ARH_T5 ARH_G3 ARH_G7 ARH_G11 ARH_T6
+#define ARH_T4 ARH_G6 ARH_G10 ARH_G14 ARH_T5
+#define ARH_T3 ARH_G9 ARH_G13 ARH_G2 ARH_T4
+#define ARH_T2 ARH_G12 ARH_G1 ARH_G5 ARH_T3
+#define ARH_TAIL_ASM(T, F) asm("; the rest of a split" T : ARH_T_OUT##F : ARH_T_IN##F)
+  if constexpr (F == 2) ARH_TAIL_ASM(ARH_T2, 2);
+  else if constexpr (F == 3) ARH_TAIL_ASM(ARH_T3, 3);
+  else if constexpr (F == 4) ARH_TAIL_ASM(ARH_T4, 4);
+  else if constexpr (F == 5) ARH_TAIL_ASM(ARH_T5, 5);
+  else ARH_TAIL_ASM(ARH_T6, 6);
+#undef ARH_TAIL_ASM
+#undef ARH_T2
+#undef ARH_T3
+#undef ARH_T4
+#undef ARH_T5
+#undef ARH_T6
+}
+// The eight registers become the pair's two operands HERE: where the compiler could not make them two register quads from the start it copies, and
+// the copy has to stand in front of this statement — not in front of the block that reads the pair first, behind that block's wait, where the
+// matrix instruction (inside a string, unseen by the hazard recogniser) would read the register in the copy's shadow.
+__device__ __forceinline__ void arh_split_done(const ArhHL& x, ArhB& b) {
+  b.h = __builtin_bit_cast(f16x8, arh_u32x4{x.h0, x.h1, x.h2, x.h3}); b.l = __builtin_bit_cast(f16x8, arh_u32x4{x.l0, x.l1, x.l2, x.l3});
+  asm volatile("" : "+v"(b.h), "+v"(b.l));
+}
+#undef ARH_BLK_FORM
 #undef ARH_BLK_ASM
 #undef ARH_BLK_BS0
 #undef ARH_BLK_BS1
+#undef ARH_G_OUT0
+#undef ARH_G_IN0
+#undef ARH_G_OUT1
+#undef ARH_G_IN1
+#undef ARH_G_OUT2
+#undef ARH_G_IN2
+#undef ARH_G_OUT3
+#undef ARH_G_IN3
+#undef ARH_G_OUT4
+#undef ARH_G_IN4
+#undef ARH_G_OUT5
+#undef ARH_G_IN5
+#undef ARH_G_OUT6
+#undef ARH_G_IN6
+#undef ARH_G_SC
+#undef ARH_T_OUT2
+#undef ARH_T_IN2
+#undef ARH_T_OUT3
+#undef ARH_T_IN3
+#undef ARH_T_OUT4
+#undef ARH_T_IN4
+#undef ARH_T_OUT5
+#undef ARH_T_IN5
+#undef ARH_T_OUT6
+#undef ARH_T_IN6
+#undef ARH_GH
+#undef ARH_GL
+#undef ARH_G0
+#undef ARH_G1
+#undef ARH_G2
+#undef ARH_G3
+#undef ARH_G4
+#undef ARH_G5
+#undef ARH_G6
+#undef ARH_G7
+#undef ARH_G8
+#undef ARH_G9
+#undef ARH_G10
+#undef ARH_G11
+#undef ARH_G12
+#undef ARH_G13
+#undef ARH_G14
+#undef ARH_G15
 // the accumulators of a last-layer group become readable: twelve wait states behind the group's last matrix instruction (the other tiles' last
 // ones stand in front of it)
 template <int NT> __device__ __forceinline__ void arh_acc_ready(f32x4 (&acc)[NT]) {
@@ -339,9 +490,110 @@ template <class S, int L, bool ALT> constexpr int arh_ip(int s) {  // the in pai
 // (EPI — the pinned ReLU path with ARH_EPI_TILE: an out tile's ReLU and its entry into the sample's partial maxima pm stand behind the tile's descale,
 //  among the matrix instructions of the tiles that follow; nothing of them needs the whole layer)
 template <class S> constexpr bool ARH_EPI = S::ACT == 1 && ARH_EPI_PINNED && ARH_EPI_TILE;
-template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, const ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d, float (&pm)[4]) {
+
+// Where the splits of a consuming layer's in pairs stand (ARH_SPLIT_GAPS).  L: a hidden layer 1..NH-1, or NH, the last layer (NT blocks per (group,
+// in pair) step).  Its input is the layer before's output, still in `out`; the units are sorted by degree, so the layer's first blocks read the first
+// in pairs only.  Pair 0 is split in front of the layer.  Pair p >= 1 takes the blocks from where pair p - 1 ended, one form per block, up to
+// lim(p): the first block that reads the pair, or (hidden layers) the last block of the first out tile that overwrites out[2p] or out[2p + 1] —
+// an out tile without blocks is written in front of the first block: lim 0.  The forms front(p)..6 found no block and stand in front of block lim(p).
+template <int NBLK> struct ArhGapPlan {
+  signed char pair[NBLK > 0 ? NBLK : 1], form[NBLK > 0 ? NBLK : 1];  // per block: the pair whose split it carries and the form (0: none)
+  short lim[9];                                                      // per in pair
+  signed char front[9];                                              // per in pair: 7 = nothing left over
+};
+template <class S, int L, int NT> constexpr int arh_gap_blocks() {
+  if constexpr (L == S::NH) return S::GOFF[S::NG] * NT;
+  else return S::NB[L];
+}
+template <class S, int L, int NT> constexpr int arh_gap_reader(int b) {  // the in pair block b reads
+  if constexpr (L == S::NH) return S::G_IP[b / NT];
+  else return ArxPat<S>::ip(L, b);
+}
+template <class S, int L> constexpr int arh_gap_last_block(int t) {  // the last block of out tile t of a hidden layer; -1: none, its bias is its value; NB: no such tile
+  if (t >= S::HT[L]) return S::NB[L];
+  int last = -1;
+  for (int b = 0; b < S::NB[L]; ++b)
+    if (ArxPat<S>::ot(L, b) == t) last = b;
+  return last;
+}
+template <class S, int L, int NT> constexpr ArhGapPlan<arh_gap_blocks<S, L, NT>()> arh_gap_plan() {
+  static_assert(L >= 1 && L <= S::NH && S::TMAX / 2 <= 8, "a consuming layer; eight in pairs at most");
+  constexpr int NBLK = arh_gap_blocks<S, L, NT>(), NP = (S::HT[L - 1] + 1) / 2;
+  ArhGapPlan<NBLK> g{};
+  for (int p = 0; p < 9; ++p) { g.lim[p] = 0; g.front[p] = 7; }
+  int cursor = 0;
+  for (int p = 1; p < NP; ++p) {
+    int lim = NBLK;
+    for (int b = NBLK - 1; b >= 0; --b)
+      if (arh_gap_reader<S, L, NT>(b) == p) lim = b;
+    if constexpr (L != S::NH) {
+      for (int t = 2 * p; t <= 2 * p + 1; ++t) {
+        const int last = arh_gap_last_block<S, L>(t);
+        lim = last < 0 ? 0 : (last < lim ? last : lim);
+      }
+    }
+    int f = 1;
+    for (; f <= 6 && cursor < lim; ++f, ++cursor) { g.pair[cursor] = (signed char)p; g.form[cursor] = (signed char)f; }
+    g.lim[p] = (short)lim;
+    g.front[p] = (signed char)f;
+  }
+  return g;
+}
+template <class S, int L, int NT, bool ON> struct ArhGapsOf {
+  static constexpr int NP = 0, NBLK = 0;
+  static constexpr int form(int) { return 0; }
+  static constexpr int pair(int) { return 0; }
+  static constexpr bool tail_at(int, int) { return false; }
+  static constexpr bool any_tail_at(int) { return false; }
+  static constexpr int front(int) { return 7; }
+};
+template <class S, int L, int NT> struct ArhGapsOf<S, L, NT, true> {
+  static constexpr int NP = (S::HT[L - 1] + 1) / 2, NBLK = arh_gap_blocks<S, L, NT>();
+  static constexpr ArhGapPlan<NBLK> plan = arh_gap_plan<S, L, NT>();
+  static constexpr int form(int b) { return plan.form[b]; }
+  static constexpr int pair(int b) { return plan.pair[b]; }
+  static constexpr bool tail_at(int p, int b) { return p >= 1 && plan.front[p] <= 6 && plan.lim[p] == b; }  // pair p's leftover forms stand in front of block b (NBLK: behind the last block)
+  static constexpr int front(int p) { return plan.front[p]; }
+  static constexpr bool any_tail_at(int b) {
+    for (int p = 1; p < NP; ++p)
+      if (tail_at(p, b)) return true;
+    return false;
+  }
+};
+// the splits in front of the layer (pair 0, and every pair no block can carry), and those in front of block B (B >= 1; NBLK: behind the last block)
+template <class GP, int HTI, int NPR> __device__ __forceinline__ void arh_gap_front(const f32x4 (&out)[2 * NPR], float s, ArhB (&in)[NPR]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  arh_split(out[0], 1 < HTI ? out[1] : zero, s, in[0]);
+  ars_for<GP::NP>([&](auto p_) ARS_ALWAYS_INLINE {
+    constexpr int p = p_;
+    if constexpr (GP::tail_at(p, 0)) arh_split(out[2 * p], 2 * p + 1 < HTI ? out[2 * p + 1] : zero, s, in[p]);
+  });
+}
+template <class GP, int HTI, int B, int NPR> __device__ __forceinline__ void arh_gap_tails(ArhHL (&x)[NPR], const f32x4 (&out)[2 * NPR], float s, ArhB (&in)[NPR]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  ars_for<GP::NP>([&](auto p_) ARS_ALWAYS_INLINE {
+    constexpr int p = p_;
+    if constexpr (B >= 1 && GP::tail_at(p, B)) {
+      if constexpr (GP::front(p) == 1) {
+        arh_split(out[2 * p], 2 * p + 1 < HTI ? out[2 * p + 1] : zero, s, in[p]);
+      } else {
+        arh_split_tail<GP::front(p)>(x[p], out[2 * p], 2 * p + 1 < HTI ? out[2 * p + 1] : zero, s);
+        arh_split_done(x[p], in[p]);
+      }
+    }
+  });
+}
+
+// GAPS (hidden layers 1..NH-1 with ARH_SPLIT_GAPS): `out` holds the layer's INPUT, to be split by the scale s_in into `in` as the blocks go
+// (arh_gap_plan), and receives the layer's output tile by tile
+template <class S, int L, class Ring, bool ALT = false, bool GAPS = false>
+__device__ __forceinline__ void arh_hidden(Ring& ring, const float* bias_q, ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], float d, float (&pm)[4], float s_in = 0.f) {
   typedef ArxPat<S> P;
-  constexpr int NB = S::NB[L], BASE = S::BASE[L], HTL = S::HT[L];
+  typedef ArhGapsOf<S, L, 0, GAPS> GP;
+  constexpr int NB = S::NB[L], BASE = S::BASE[L], HTL = S::HT[L], HTI = S::HT[L > 0 ? L - 1 : 0];
+  ArhHL x[S::TMAX / 2];
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (GAPS) arh_gap_front<GP, HTI>(out, s_in, in);
   ars_for<HTL>([&](auto t_) ARS_ALWAYS_INLINE {
     constexpr int t = t_;
     if constexpr (!P::tile_has_blocks(L, t)) {
@@ -371,8 +623,15 @@ template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline
       }
       constexpr int ahead = (s + LOOK < NB ? LOOK : NB - 1 - s);  // blocks behind this one whose images may still be outstanding
       // (a tile's last block: only THIS step's request is younger than the bias read — the wait that settles it also settles the blocks in between)
-      if constexpr (ARH_BLK) {
-        arh_wait_block<(last_of_tile ? (s + LOOK < NB ? 2 : 0) : 2 * ahead), first_of_tile, s == 0, last_of_tile>(a[cur], in[ip], acc, bs);
+      if constexpr (GAPS) arh_gap_tails<GP, HTI, s>(x, out, s_in, in);  // (what found no block in front of this one, its first reader or the last of an out tile that overwrites the pair)
+      constexpr int WAIT = last_of_tile ? (s + LOOK < NB ? 2 : 0) : 2 * ahead;
+      constexpr bool pad = s == 0 || (GAPS && s >= 1 && GP::any_tail_at(s));
+      if constexpr (GP::form(s) != 0) {
+        constexpr int gp = GP::pair(s);
+        arh_wait_block<WAIT, first_of_tile, pad, last_of_tile, GP::form(s)>(a[cur], in[ip], acc, bs, x[gp], out[2 * gp], 2 * gp + 1 < HTI ? out[2 * gp + 1] : zero, s_in);
+        if constexpr (GP::form(s) == 6) arh_split_done(x[gp], in[gp]);
+      } else if constexpr (ARH_BLK) {
+        arh_wait_block<WAIT, first_of_tile, pad, last_of_tile>(a[cur], in[ip], acc, bs);
       } else {
         if constexpr (last_of_tile) arh_settle<(s + LOOK < NB ? 2 : 0)>(a[cur][0], a[cur][1], bs);
         else arh_settle<2 * ahead>(a[cur][0], a[cur][1]);
@@ -394,13 +653,16 @@ template <class S, int L, class Ring, bool ALT = false> __device__ __forceinline
         if constexpr (ARH_EPI<S>) arh_relu_max(out[ot], pm, ot);
       }
     });
+    if constexpr (GAPS) arh_gap_tails<GP, HTI, NB>(x, out, s_in, in);
   }
 }
 
 // (wd: the per-layer descale factors 2^-ew_l of the stream being read — ArArgs::wdescale, or the transform's row of the flow kernel's table)
 // HAS_ALT / alt (flow kernel): this pass's first layer follows S::B_IP_ALT
+// s (ARH_SPLIT_GAPS): the scale by which the CONSUMER of a layer's output splits it — the next hidden layer (arh_hidden's GAPS) or, behind the last
+// hidden layer, arh_pass; without the switch every layer's output is split here, behind the layer
 template <class S, int L, class Ring, bool HAS_ALT = false> __device__ __forceinline__ void arh_hidden_stack(Ring& ring, const float* bias_lds, int q, ArhB (&in)[S::TMAX / 2], f32x4 (&out)[S::TMAX], const float* wd,
-                                                                                                         float& inv_s, float& poison, bool alt = false) {
+                                                                                                         float& inv_s, float& poison, float& s, bool alt = false) {
   if constexpr (L < S::NH) {
     float pm[4] = {0.f, 0.f, 0.f, 0.f};  // partial maxima of the layer's ReLU outputs (the pinned ReLU path: arh_relu_max)
     if constexpr (HAS_ALT && L == 0) {
@@ -408,7 +670,7 @@ template <class S, int L, class Ring, bool HAS_ALT = false> __device__ __forcein
       if (alt) arh_hidden<S, L, Ring, true>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm);
       else arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm);
     } else {
-      arh_hidden<S, L, Ring>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm);
+      arh_hidden<S, L, Ring, false, ARH_GAPS && L >= 1>(ring, bias_lds + L * S::BIAS_STRIDE + 4 * q, in, out, wd[L] * inv_s, pm, s);
     }
     constexpr int HTL = S::HT[L];
     float amax = 0.f;
@@ -435,15 +697,16 @@ template <class S, int L, class Ring, bool HAS_ALT = false> __device__ __forcein
 #pragma unroll
         for (int r = 0; r < 4; ++r) amax = fmaxf(amax, fabsf(out[t][r]));
     }
-    float s;
     arh_scale(amax, s, inv_s);
     if constexpr (S::ACT == 1 && ARH_EPI_PINNED) {
       if (!(amax < ARH_AMAX_OVERFLOW)) poison = __builtin_nanf("");  // a hidden value overflowed f32 (or f16 after the scaling): NaN for its sample
     }
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (!ARH_GAPS) {
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int p = 0; p < (HTL + 1) / 2; ++p) arh_split(out[2 * p], 2 * p + 1 < HTL ? out[2 * p + 1] : zero, s, in[p]);
-    arh_hidden_stack<S, L + 1, Ring, HAS_ALT>(ring, bias_lds, q, in, out, wd, inv_s, poison, alt);
+      for (int p = 0; p < (HTL + 1) / 2; ++p) arh_split(out[2 * p], 2 * p + 1 < HTL ? out[2 * p + 1] : zero, s, in[p]);
+    }
+    arh_hidden_stack<S, L + 1, Ring, HAS_ALT>(ring, bias_lds, q, in, out, wd, inv_s, poison, s, alt);
   }
 }
 
@@ -537,8 +800,14 @@ __device__ __forceinline__ void arh_pass(const ArArgs& a, Ring& ring, XReq& x_re
   }
 
   // ---- hidden layers ---------------------------------------------------------------------------------------------
-  if constexpr (FLOW) arh_hidden_stack<S, 0, Ring, S::FLOW_ALT>(ring, bias_lds, q, in, out, wd, inv_s, poison, alt);
-  else arh_hidden_stack<S, 0, Ring>(ring, bias_lds, q, in, out, wd, inv_s, poison);
+  float s_last = 0.f;  // (ARH_SPLIT_GAPS: the scale of the last hidden layer's output, split under the last layer's blocks)
+  if constexpr (FLOW) arh_hidden_stack<S, 0, Ring, S::FLOW_ALT>(ring, bias_lds, q, in, out, wd, inv_s, poison, s_last, alt);
+  else arh_hidden_stack<S, 0, Ring>(ring, bias_lds, q, in, out, wd, inv_s, poison, s_last);
+  typedef ArhGapsOf<S, S::NH, Uni::NT, (ARH_GAPS && S::NH >= 1)> GP;
+  constexpr int HTI = S::HT[S::NH >= 1 ? S::NH - 1 : 0];
+  ArhHL hl[S::TMAX / 2];
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (ARH_GAPS && S::NH >= 1) arh_gap_front<GP, HTI>(out, s_last, in);
 
   // ---- last layer + univariate transform, one group of 4 * FPL features at a time --------------------------------
   const float dl = wd[S::NH] * inv_s;
@@ -602,8 +871,17 @@ __device__ __forceinline__ void arh_pass(const ArArgs& a, Ring& ring, XReq& x_re
           ars_for<2>([&](auto p) ARS_ALWAYS_INLINE { w[nx][p] = ARH_READ_LAST(S::LAST_BASE + 2 * (blk + LOOKL) + decltype(p)::value); });
         }
         constexpr int ahead = (blk + LOOKL < NBL ? LOOKL : NBL - 1 - blk);
+        if constexpr (ARH_GAPS && S::NH >= 1) arh_gap_tails<GP, HTI, blk>(hl, out, s_last, in);  // (what found no block in front of this one, the pair's first reader)
+        constexpr int WAIT = last_of_group ? (blk + LOOKL < NBL ? 2 : 0) : 2 * ahead;
+        constexpr bool pad = blk == 0 || (ARH_GAPS && S::NH >= 1 && blk >= 1 && GP::any_tail_at(blk));
         if constexpr (ARH_BLK) {
-          arh_wait_block<(last_of_group ? (blk + LOOKL < NBL ? 2 : 0) : 2 * ahead), decltype(i_)::value == 0, blk == 0, false>(w[cur], in[ip], acc[t], bs[0]);
+          if constexpr (GP::form(blk) != 0) {
+            constexpr int gp = GP::pair(blk);
+            arh_wait_block<WAIT, decltype(i_)::value == 0, pad, false, GP::form(blk)>(w[cur], in[ip], acc[t], bs[0], hl[gp], out[2 * gp], 2 * gp + 1 < HTI ? out[2 * gp + 1] : zero, s_last);
+            if constexpr (GP::form(blk) == 6) arh_split_done(hl[gp], in[gp]);
+          } else {
+            arh_wait_block<WAIT, decltype(i_)::value == 0, pad, false>(w[cur], in[ip], acc[t], bs[0]);
+          }
           if constexpr (last_of_group) {  // (the bias tiles are older than this step's request: the block's wait has settled them)
 #pragma unroll
             for (int u = 0; u < NT; ++u) arh_touch(bs[u]);
@@ -636,6 +914,7 @@ __device__ __forceinline__ void arh_pass(const ArArgs& a, Ring& ring, XReq& x_re
     else ar_uni_epilogue<Uni, DIAG, XLDS, true, TERM>(p, a, fid, xin, poison, xr, n, live, S::D, lacc, bv);
   });
 #undef ARH_READ_LAST
+  if constexpr (ARH_GAPS && S::NH >= 1) arh_gap_tails<GP, HTI, NBL>(hl, out, s_last, in);  // (pairs no block reads)
   if constexpr (FLOW) {
     // the transform's log-derivative joins the running sum as a launch of its own would add it to the buffer: summed over the sample's four lanes first
     lacc += __shfl_xor(lacc, 16, 64);

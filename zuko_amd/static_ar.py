@@ -101,11 +101,12 @@ def hipcc_flags() -> list:
     return ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={_arch()}", "-Wno-unused-result", "-Wno-uninitialized", "-ffp-contract=off", f"-I{CSRC}"]
 
 
-def _build_so(stem: str, source, meta: dict | None, verbose: bool, out_dir: str | None = None) -> str | None:
+def _build_so(stem: str, source, meta: dict | None, verbose: bool, out_dir: str | None = None, only_dir: bool = False, cxxflags: list | None = None) -> str | None:
     """Compile the one-kernel translation unit `source()` into <dir>/<stem>.so (+ <stem>.json when `meta` is given); a no-op when it
     is there.  Returns the .so path, or None when there is no hipcc, the compile fails, or the directory cannot be written (read-only
     install, full disk): the caller then stays on the generic / layer-wise kernels — a failed JIT must never fail the user's call."""
-    have = _find(stem + ".so")
+    # (only_dir: a variant build — a kernel of the same name elsewhere, such as the prebuilt one, does not count; cxxflags: in place of ZUKO_AMD_STATIC_CXXFLAGS)
+    have = (os.path.join(out_dir, stem + ".so") if os.path.exists(os.path.join(out_dir, stem + ".so")) else None) if only_dir else _find(stem + ".so")
     if have is not None and (meta is None or os.path.exists(have[: -len(".so")] + ".json")):
         return have
     hipcc = _hipcc()
@@ -128,7 +129,7 @@ def _build_so(stem: str, source, meta: dict | None, verbose: bool, out_dir: str 
                 f.write(source())
             tmp = os.path.join(d, f".{stem}.so.{os.getpid()}")
             cmd = [hipcc, *hipcc_flags(), "-shared", "-no-hip-rt",
-                   *os.environ.get("ZUKO_AMD_STATIC_CXXFLAGS", "").split(),  # (probe / ablation builds into a ZUKO_AMD_CACHE_DIR of their own: NOT part of the kernel's signature)
+                   *(os.environ.get("ZUKO_AMD_STATIC_CXXFLAGS", "").split() if cxxflags is None else cxxflags),  # (probe / ablation builds into a ZUKO_AMD_CACHE_DIR of their own: NOT part of the kernel's signature)
                    src, f"-L{_torch_lib_dir()}", "-l:libamdhip64.so", "-o", tmp]
             if verbose:
                 print("[zuko_amd static_ar]", " ".join(cmd), flush=True)
@@ -766,6 +767,51 @@ def find_or_compile(fam: Family, t: dict, allow: bool, l0: list | None = None, v
     with _LOCK:
         k = _load(found[0], fam.entry)
     return None if k is None else (k, found[1])
+
+
+def build_half_variant(configs: list, out_dir: str, cxxflags: list | None = None, jobs: int = 4) -> list:
+    """Compile the two-part kernels (both feature orders' units and the flow unit) of every (kind, features, context, hidden, bins) in `configs` into
+    <out_dir>/ars with the extra compiler flags `cxxflags`, whether or not kernels of the same names exist elsewhere; returns the .so paths.  A process
+    started with ZUKO_AMD_CACHE_DIR=<out_dir> finds them before the prebuilt ones (probe and ablation builds: scripts/build_half_variant.py)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    ars = os.path.join(os.path.abspath(out_dir), "ars")
+    work = []
+    for cfg in configs:
+        tabs = [half_tables(plan, layout.kind, 1) for plan, layout, _ in _plans_for(*cfg)]
+        if any(t is None for t in tabs):
+            raise ValueError(f"no two-part kernel for {cfg}")
+        for t, _ in tabs:
+            if (ARH, t) not in work:
+                work.append((ARH, t))
+        tf = flow_tables([t for t, _ in tabs])
+        if tf is not None:
+            work.append((ARHF, tf[0]))
+
+    def one(w):
+        fam, t = w
+        stem, meta = _identity(fam, t)
+        return _build_so(stem, lambda: emit(fam, t), dict(meta, flags=list(cxxflags or [])), False, ars, only_dir=True, cxxflags=list(cxxflags or []))
+
+    with ThreadPoolExecutor(max_workers=jobs) as ex:
+        sos = list(ex.map(one, work))
+    if any(so is None for so in sos):
+        raise RuntimeError("zuko_amd.static_ar: a variant kernel failed to compile")
+    rescan()
+    return sos
+
+
+def rescan() -> None:
+    """Forget which kernels were found on disk: the next lookup reads the directories (ZUKO_AMD_CACHE_DIR, lib/ars) again."""
+    global _INDEX
+    with _LOCK:
+        _INDEX = None
+
+
+def loaded_kernels() -> dict:
+    """{file name: path} of the generated kernels this process has loaded."""
+    with _LOCK:
+        return {name: k.so for name, k in _LOADED.items()}
 
 
 def _enabled() -> bool:
