@@ -970,6 +970,46 @@ typedef struct zk_cnf_args_v1 {
   void* err_rows;          /* or NULL */
 } zk_cnf_args_v1;
 int zk_cnf_step(const zk_cnf_args_v1* args, void* stream);
+/* zk_cnf_step_v2 is zk_cnf_step with Hutchinson's estimator of the trace (FreeFormJacobianTransform(exact=False), FFJORD): the block is
+ * zk_cnf_args_v1's fields followed by the probe.  With eps != NULL every stage carries ONE tangent in the row's direction eps instead of one per
+ * feature, and the log-determinant component integrates (eps^T (df/dx) eps) * trace_scale; everything else — y, the sums, the error ratio with l,
+ * err, err_rows — is the v1 call's, and y has the exact call's bits.  The probe is an input: constant over an integration, drawn by the caller.
+ *
+ *   eps      [N, features], row stride ld_eps >= features, or NULL: the v1 call (ld_eps is not examined)
+ *   requires n_tangents = features (l and l_next given); eps with n_tangents = 0 is refused.
+ * A row's outputs depend on its own x, l, pre row and eps row only. */
+typedef struct zk_cnf_args_v2 {
+  uint32_t struct_size;    /* sizeof(zk_cnf_args_v2) */
+  uint32_t version;        /* 2 */
+  int32_t features;
+  int32_t freqs;
+  int32_t n_hidden;
+  int32_t width0;
+  int32_t width1;
+  int32_t width2;
+  int32_t image_floats;
+  int32_t n_tangents;
+  int64_t N;
+  int64_t ldx;
+  int64_t ldy;
+  int64_t ld_pre;
+  double t;
+  double dt;
+  double atol;
+  double rtol;
+  double trace_scale;
+  const void* x;
+  const void* l;
+  const void* pre;
+  const void* image;
+  void* y;
+  void* l_next;
+  void* err;
+  void* err_rows;
+  const void* eps;         /* the probe, or NULL: exactly zk_cnf_step */
+  int64_t ld_eps;          /* with eps */
+} zk_cnf_args_v2;
+int zk_cnf_step_v2(const zk_cnf_args_v2* args, void* stream);
 /* Floats of the weight image, or -1 outside the limits (host only). */
 int zk_cnf_image_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2);
 
@@ -1029,6 +1069,50 @@ typedef struct zk_cnf_adj_args_v1 {
   void* work;
 } zk_cnf_adj_args_v1;
 int zk_cnf_adjoint_step(const zk_cnf_adj_args_v1* args, void* stream);
+/* zk_cnf_adjoint_step_v2 is zk_cnf_adjoint_step for a forward that ran zk_cnf_step_v2 with a probe: the block is zk_cnf_adj_args_v1's fields
+ * followed by the probe.  With eps != NULL and al != NULL the trace term of every stage is that of eps^T (df/dx) eps — ONE tangent in the row's
+ * direction eps forward and back instead of one per feature:
+ *     ka_s = dt (a_s^T df/dx + beta d(eps^T (df/dx) eps)/dx),   and likewise for every parameter gradient.
+ * The value term, the partials, the reduction, gpre and `work` are the v1 call's.  There is no gradient for eps.
+ *
+ *   eps      [N, features], row stride ld_eps >= features: the probe of the forward steps, or NULL: the v1 call (ld_eps is not examined)
+ *   al       NULL: the probe is not read; the result has the v1 call's bits.
+ * A row's ax_next and gpre depend on its own x, ax, al, pre row and eps row only. */
+typedef struct zk_cnf_adj_args_v2 {
+  uint32_t struct_size;    /* sizeof(zk_cnf_adj_args_v2) */
+  uint32_t version;        /* 2 */
+  int32_t features;
+  int32_t freqs;
+  int32_t n_hidden;
+  int32_t width0;
+  int32_t width1;
+  int32_t width2;
+  int32_t image_floats;
+  int32_t grad_floats;
+  int64_t N;
+  int64_t ldx;
+  int64_t ld_ax;
+  int64_t ld_ax_next;
+  int64_t ld_pre;
+  int64_t ld_gpre;
+  int64_t flat_total;
+  double t;
+  double dt;
+  double trace_scale;
+  const void* x;
+  const void* ax;
+  const void* al;
+  const void* pre;
+  const void* image;
+  const int32_t* grad_table;
+  void* ax_next;
+  void* gpre;
+  void* gparams;
+  void* work;
+  const void* eps;           /* the probe, or NULL: exactly zk_cnf_adjoint_step */
+  int64_t ld_eps;            /* with eps */
+} zk_cnf_adj_args_v2;
+int zk_cnf_adjoint_step_v2(const zk_cnf_adj_args_v2* args, void* stream);
 /* Host only.  Floats of the backward image and of one partial; hipErrorInvalidValue outside the limits. */
 int zk_cnf_adjoint_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats);
 /* Host only.  Rows per chunk (a multiple of 64) and the number of chunks of an N-row call: a pure function of N. */

@@ -7,6 +7,12 @@ field evaluations per attempted step, each with a batched autograd Jacobian for 
     rocprofv3 --kernel-trace --stats -- python scripts/bench_cnf.py --trace     # per-launch kernel times (kernel path only, few calls)
     python scripts/bench_cnf.py --train         # one JSON line: an Adam step at batch 2^14 and 2^16 with ops.CNF_ADJOINT on and off
     rocprofv3 --kernel-trace --stats -- python scripts/bench_cnf.py --train --trace   # per-launch times of the adjoint kernel (kernel path only)
+    python scripts/bench_cnf.py --exact-false [--train] [--trace]     # Hutchinson's estimator (exact=False): see below
+
+`--exact-false`: CNF(5, 3) and the 16-feature CNF(16, 3, hidden (64, 64)) with exact=False, `log_prob` at batch 2^16 (with `--train`: an Adam step at
+batch 2^14 and 2^16), three ways in one process: ops.CNF_HUTCHINSON on (with `--train` ops.CNF_ADJOINT too: the probe variant of the kernels), both
+switches off (the torch-op path an exact=False flow takes by default, and took before the switch existed), and the exact=True flow of the same shape on
+the exact kernels.  ZUKO_AMD_BENCH_ROOT=<another checkout> measures that checkout's package instead; one without the switch reports the two rows it has.
 
 `--train`: the loss is -log_prob(x).mean(); a step is zero_grad, forward, backward, Adam.  With the switch on the forward runs on zk_cnf_step and the
 backward makes one zk_cnf_adjoint_step per accepted step; with it off (the default) both run in torch ops — the code path of the parent commit.
@@ -22,7 +28,7 @@ import json
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.environ.get("ZUKO_AMD_BENCH_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
@@ -129,7 +135,87 @@ def train_main() -> None:
     print(json.dumps(out))
 
 
+def hutch_main() -> None:
+    """exact=False on the probe kernels, on the torch-op path, and exact=True on the exact kernels, at two shapes."""
+    dev = torch.device("cuda:0")
+    train, trace = "--train" in sys.argv, "--trace" in sys.argv
+    has_switch = hasattr(ops, "CNF_HUTCHINSON")
+    g = torch.Generator().manual_seed(1)
+    out = {"workload": ("Adam step, loss -log_prob.mean()" if train else "log_prob") + " of CNF(F, 3), freqs 3, hidden (64, 64), weights as initialised (seed 0)",
+           "version": zuko_amd.__version__, "has_switch": has_switch}
+    for F in (5, 16):
+        X, Cx = torch.randn(2**16, F, generator=g).to(dev), torch.randn(2**16, 3, generator=g).to(dev)
+
+        def runner(exact: bool, on: bool, n: int):
+            torch.manual_seed(0)
+            flow = CNF(F, 3, exact=exact).to(dev)
+            flow = flow.train() if train else flow.eval().requires_grad_(False)
+            opt = torch.optim.Adam(flow.parameters(), lr=1e-3) if train else None
+            x, c = X[:n], Cx[:n]
+            stats = {}
+
+            def run():
+                keep = ops.CNF_ADJOINT, getattr(ops, "CNF_HUTCHINSON", False)
+                ops.CNF_ADJOINT = on and train
+                if has_switch:
+                    ops.CNF_HUTCHINSON = on
+                try:
+                    if not train:
+                        with torch.no_grad():
+                            lp = flow(c).log_prob(x)
+                        stats.update(ops.CNF_STATS)
+                        return lp
+                    opt.zero_grad(set_to_none=True)
+                    loss = -flow(c).log_prob(x).mean()
+                    stats.update(ops.CNF_STATS)
+                    loss.backward()
+                    stats.update(ops.CNF_STATS)
+                    opt.step()
+                    return loss
+                finally:
+                    ops.CNF_ADJOINT = keep[0]
+                    if has_switch:
+                        ops.CNF_HUTCHINSON = keep[1]
+
+            return run, stats
+
+        for n in ((2**14, 2**16) if train else (2**16,)):
+            rows = {"exact_kernels": (True, True), "hutchinson_off": (False, False)} | ({"hutchinson_on": (False, True)} if has_switch else {})
+            if trace:  # the probe kernels alone, a few calls
+                run, _ = runner(False, True, n)
+                for _ in range(3):
+                    run()
+                torch.cuda.synchronize()
+                continue
+            runs = {name: runner(exact, on, n) for name, (exact, on) in rows.items()}
+            res = {}
+            for rnd in range(2):  # alternate the paths: none sees a systematically warmer or cooler device
+                for name, (run, _) in runs.items():
+                    res.setdefault(name, []).append(timed(run, min_seconds=0.5, warmup=2))
+            key = f"features_{F}_batch_{n}"
+            for name, (run, st) in runs.items():
+                best = min(res[name], key=lambda r: r["median_ms"])
+                out[f"{key}_{name}"] = best | {"medians_ms": [round(r["median_ms"], 3) for r in res[name]],
+                                               "last_call": {k: st[k] for k in ("path", "trace", "attempts", "accepted", "adjoint_steps") if k in st}}
+            if has_switch:
+                on = out[f"{key}_hutchinson_on"]["median_ms"]
+                out[f"{key}_off_over_on"] = out[f"{key}_hutchinson_off"]["median_ms"] / on
+                out[f"{key}_exact_over_on"] = out[f"{key}_exact_kernels"]["median_ms"] / on
+                _C.PROFILE = {}
+                runs["hutchinson_on"][0]()
+                torch.cuda.synchronize()
+                prof, _C.PROFILE = _C.PROFILE, None
+                for sym in ("zk_cnf_step_v2", "zk_cnf_adjoint_step_v2"):
+                    ts = [a.elapsed_time(b) for a, b, _ in prof.get(sym, [])]
+                    if ts:
+                        out[f"{key}_{sym}_launch_ms"] = {"launches": len(ts), "mean": sum(ts) / len(ts), "min": min(ts), "max": max(ts)}
+    if not trace:
+        print(json.dumps(out))
+
+
 def main() -> None:
+    if "--exact-false" in sys.argv:
+        return hutch_main()
     if "--train" in sys.argv:
         return train_main()
     dev = torch.device("cuda:0")

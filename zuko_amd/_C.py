@@ -50,7 +50,8 @@ def _parse_structs(path: str) -> dict:
 
 
 STRUCTS = _parse_structs(_HEADER)
-_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_umnn_bwd_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1, "zk_cnf_adj_args_v1": 1}
+_VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_umnn_bwd_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1, "zk_cnf_adj_args_v1": 1,
+            "zk_cnf_args_v2": 2, "zk_cnf_adj_args_v2": 2}
 
 
 def args(struct: str, **fields):
@@ -103,6 +104,8 @@ _UMNN_BWD = POINTER(STRUCTS["zk_umnn_bwd_args_v1"])
 _GMM = POINTER(STRUCTS["zk_gmm_args_v1"])
 _CNF = POINTER(STRUCTS["zk_cnf_args_v1"])
 _CNF_ADJ = POINTER(STRUCTS["zk_cnf_adj_args_v1"])
+_CNF2 = POINTER(STRUCTS["zk_cnf_args_v2"])
+_CNF_ADJ2 = POINTER(STRUCTS["zk_cnf_adj_args_v2"])
 
 # symbol -> argument types (return type is always int = hipError_t)
 SIGNATURES = {
@@ -183,8 +186,10 @@ SIGNATURES = {
     "zk_gmm_workspace_floats": [I, L, I, I, I, I],
     "zk_gmm_launch_geometry": [I, I, I, I, I, POINTER(c_int)],
     "zk_cnf_step": [_CNF, P],
+    "zk_cnf_step_v2": [_CNF2, P],
     "zk_cnf_image_floats": [I, I, I, I, I, I],
     "zk_cnf_adjoint_step": [_CNF_ADJ, P],
+    "zk_cnf_adjoint_step_v2": [_CNF_ADJ2, P],
     "zk_cnf_adjoint_floats": [I, I, I, I, I, I, POINTER(c_int), POINTER(c_int)],
     "zk_cnf_adjoint_geometry": [L, POINTER(c_int), POINTER(c_int)],
     "zk_cnf_adjoint_workspace_floats": [L, I, I, I, I, I, I, POINTER(c_int64)],

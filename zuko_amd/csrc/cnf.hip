@@ -37,11 +37,12 @@ struct CnfArgs {
   const float* l;
   const float* pre;
   const float* image;
+  const float* eps;
   float* y;
   float* l_next;
   unsigned* err;
   float* err_rows;
-  long long N, ldx, ldy, ld_pre;
+  long long N, ldx, ldy, ld_pre, ld_eps;
   float t, dt, atol, rtol, tscale;
   CnfLayout L;
 };
@@ -107,9 +108,51 @@ __device__ __forceinline__ float cnf_tangents(const CnfLayout& L, const float* l
   return tr;
 }
 
-// f(ts, xin) of the wave's 16 rows: fo[r] = component 4 r + q of the field, tr = the trace of its Jacobian (TAN)
-template <int TM, bool TAN>
-__device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, const float* __restrict__ prow, int lane, int q, float ts, const float (&xin)[4], float (&fo)[4], float& tr) {
+// Hutchinson's estimate of the trace, ep^T (df/dx) ep, of the wave's rows: ONE tangent in direction ep (held as the state is: lane (j, q), features
+// 4 s + q, zero behind F).  Z_1 = W0x ep is the x part of cnf_first_layer, the hidden layers are those of one member of cnf_tangents, and the last
+// layer's product is the field's with a zero accumulator: u = W_last T_L comes out in the state's distribution and meets ep in four per-lane products.
+template <int TM>
+__device__ __forceinline__ float cnf_probe(const CnfLayout& L, const float* lds, int lane, int q, const float (&ep)[4], const mnn_f4 (&D)[3][TM]) {
+  mnn_f4 a[TM], b[TM];
+  const float* const px = lds + L.o_w0x + lane;
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < L.T[0]) {
+      mnn_f4 z = {0.f, 0.f, 0.f, 0.f};
+      mnn_for<4>([&](auto s) MNN_INLINE {
+        if (s < L.kx) z = __builtin_amdgcn_mfma_f32_16x16x4f32(px[(o * L.kx + s) * 64], ep[s], z, 0, 0, 0);
+      });
+      mnn_for<4>([&](auto r) MNN_INLINE { a[o][(int)r] = D[0][o][(int)r] * z[(int)r]; });
+    }
+  });
+  if (L.nh > 1) {
+    mnn_matvec<TM, 1, 0>(lds + L.o_w[1], nullptr, L.T[0], L.T[1], lane, q, &a, &b);
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < L.T[1]) mnn_for<4>([&](auto r) MNN_INLINE { a[o][(int)r] = D[1][o][(int)r] * b[o][(int)r]; });
+    });
+  }
+  if (L.nh > 2) {
+    mnn_matvec<TM, 1, 0>(lds + L.o_w[2], nullptr, L.T[1], L.T[2], lane, q, &a, &b);
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < L.T[2]) mnn_for<4>([&](auto r) MNN_INLINE { a[o][(int)r] = D[2][o][(int)r] * b[o][(int)r]; });
+    });
+  }
+  const int tl = L.T[L.nh - 1];
+  mnn_f4 u = {0.f, 0.f, 0.f, 0.f};
+  mnn_for<TM>([&](auto it) MNN_INLINE {
+    if (it < tl) {
+      const mnn_f4 w = *reinterpret_cast<const mnn_f4*>(lds + L.o_wo + it * 256 + lane * 4);
+      mnn_for<4>([&](auto r) MNN_INLINE { u = __builtin_amdgcn_mfma_f32_16x16x4f32(w[(int)r], a[it][(int)r], u, 0, 0, 0); });
+    }
+  });
+  float p = 0.f;
+  mnn_for<4>([&](auto s) MNN_INLINE { p = fmaf(ep[s], u[(int)s], p); });
+  return mnn_sum_q(p);
+}
+
+// f(ts, xin) of the wave's 16 rows: fo[r] = component 4 r + q of the field, tr = the trace of its Jacobian (TAN), or its estimate along ep (PROBE)
+template <int TM, bool TAN, bool PROBE>
+__device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, const float* __restrict__ prow, int lane, int q, float ts, const float (&xin)[4],
+                                          const float (&ep)[4], float (&fo)[4], float& tr) {
   mnn_f4 v[TM], w[TM], D[3][TM];
   float emb[4];
   mnn_for<4>([&](auto s) MNN_INLINE {
@@ -141,7 +184,9 @@ __device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, 
     }
   });
   mnn_for<4>([&](auto r) MNN_INLINE { fo[r] = c[(int)r]; });
-  if constexpr (TAN) {
+  if constexpr (PROBE) {
+    tr = cnf_probe<TM>(L, lds, lane, q, ep, D);
+  } else if constexpr (TAN) {
     tr = 0.f;
     int i = 0;
     if constexpr (TM <= 4) {
@@ -153,7 +198,9 @@ __device__ __forceinline__ void cnf_field(const CnfLayout& L, const float* lds, 
 
 extern __shared__ __attribute__((aligned(16))) float cnf_lds[];
 
-template <int TM, bool TAN> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 2 : 1) void cnf_step_kernel(CnfArgs a) {
+// TAN: the state carries l; its trace is exact (one tangent per feature) or, with PROBE (which implies TAN), Hutchinson's estimate along the row's eps
+template <int TM, bool TAN, bool PROBE = false> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 2 : 1) void cnf_step_kernel(CnfArgs a) {
+  static_assert(TAN || !PROBE);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
   const CnfLayout& L = a.L;
   mnn_stage_image(cnf_lds, a.image, L.total, tid);
@@ -165,8 +212,9 @@ template <int TM, bool TAN> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 
   const float* const prow = a.pre + rc * a.ld_pre;
   float x[4], xs[4], xn[4], k[7][4], kl[7];
   mnn_for<4>([&](auto s) MNN_INLINE { x[s] = 4 * s + q < L.F ? a.x[rc * a.ldx + 4 * s + q] : 0.f; });
-  float l0 = 0.f, ln = 0.f;
+  float l0 = 0.f, ln = 0.f, ep[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (TAN) l0 = a.l[rc];
+  if constexpr (PROBE) mnn_for<4>([&](auto s) MNN_INLINE { ep[s] = 4 * s + q < L.F ? a.eps[rc * a.ld_eps + 4 * s + q] : 0.f; });
   mnn_for<7>([&](auto m) MNN_INLINE {
     kl[m] = 0.f;
     mnn_for<4>([&](auto s) MNN_INLINE { k[m][s] = 0.f; });
@@ -189,7 +237,7 @@ template <int TM, bool TAN> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 
     }
     const float ts = a.t + CNF_C[s] * a.dt;
     float fo[4], tr = 0.f;
-    cnf_field<TM, TAN>(L, cnf_lds, prow, lane, q, ts, xs, fo, tr);
+    cnf_field<TM, TAN, PROBE>(L, cnf_lds, prow, lane, q, ts, xs, ep, fo, tr);
     mnn_for<7>([&](auto m) MNN_INLINE {
       if (s == m) {
         mnn_for<4>([&](auto c) MNN_INLINE { k[m][c] = a.dt * fo[c]; });
@@ -235,8 +283,9 @@ template <int TM, bool TAN> __global__ __launch_bounds__(MNN_THREADS, TM <= 4 ? 
   if (lane == 0) atomicMax(a.err, bits);
 }
 
-static int cnf_step(const zk_cnf_args_v1* p, void* stream) {
-  if (!p || p->struct_size != sizeof(zk_cnf_args_v1) || p->version != 1) return ZK_EINVAL;
+// the launcher of both argument blocks: P is zk_cnf_args_v1 (eps = NULL) or zk_cnf_args_v2, whose first fields are v1's
+template <class P> static int cnf_step(const P* p, uint32_t version, const void* eps, long long ld_eps, void* stream) {
+  if (!p || p->struct_size != sizeof(P) || p->version != version) return ZK_EINVAL;
   CnfArgs a;
   const int widths[3] = {p->width0, p->width1, p->width2};
   if (!cnf_layout(p->features, p->freqs, p->n_hidden, widths, &a.L)) return ZK_EINVAL;
@@ -247,23 +296,28 @@ static int cnf_step(const zk_cnf_args_v1* p, void* stream) {
   if (p->N == 0) return 0;
   if (!p->x || !p->pre || !p->image || !p->y || !p->err) return ZK_EINVAL;
   if (p->n_tangents != 0 && (!p->l || !p->l_next)) return ZK_EINVAL;
+  if (eps && (p->n_tangents == 0 || ld_eps < p->features)) return ZK_EINVAL;  // the estimator belongs to a traced call
   if (((uintptr_t)p->pre | (uintptr_t)p->image) % 16 != 0) return ZK_EINVAL;
   const long long gx = (p->N + CNF_ROWS - 1) / CNF_ROWS;
   if (gx > 0x7fffffffLL) return ZK_EINVAL;
-  a.x = (const float*)p->x; a.l = (const float*)p->l; a.pre = (const float*)p->pre; a.image = (const float*)p->image;
+  a.x = (const float*)p->x; a.l = (const float*)p->l; a.pre = (const float*)p->pre; a.image = (const float*)p->image; a.eps = (const float*)eps;
   a.y = (float*)p->y; a.l_next = (float*)p->l_next; a.err = (unsigned*)p->err; a.err_rows = (float*)p->err_rows;
-  a.N = p->N; a.ldx = p->ldx; a.ldy = p->ldy; a.ld_pre = p->ld_pre;
+  a.N = p->N; a.ldx = p->ldx; a.ldy = p->ldy; a.ld_pre = p->ld_pre; a.ld_eps = ld_eps;
   a.t = (float)p->t; a.dt = (float)p->dt; a.atol = (float)p->atol; a.rtol = (float)p->rtol; a.tscale = (float)p->trace_scale;
   const bool small = a.L.T[0] <= 4 && a.L.T[1] <= 4 && a.L.T[2] <= 4;
   const bool tan = p->n_tangents != 0;
-  const void* fn = small ? (tan ? (const void*)cnf_step_kernel<4, true> : (const void*)cnf_step_kernel<4, false>)
+  const void* fn = eps ? (small ? (const void*)cnf_step_kernel<4, true, true> : (const void*)cnf_step_kernel<8, true, true>)
+                 : small ? (tan ? (const void*)cnf_step_kernel<4, true> : (const void*)cnf_step_kernel<4, false>)
                          : (tan ? (const void*)cnf_step_kernel<8, true> : (const void*)cnf_step_kernel<8, false>);
   return mnn_launch_dyn_lds(fn, dim3((unsigned)gx), a.L.total * 4, &a, (hipStream_t)stream);
 }
 
 }  // namespace zk
 
-extern "C" int zk_cnf_step(const zk_cnf_args_v1* args, void* stream) { return zk::cnf_step(args, stream); }
+extern "C" int zk_cnf_step(const zk_cnf_args_v1* args, void* stream) { return zk::cnf_step(args, 1, nullptr, 0, stream); }
+extern "C" int zk_cnf_step_v2(const zk_cnf_args_v2* args, void* stream) {
+  return zk::cnf_step(args, 2, args ? args->eps : nullptr, args ? (long long)args->ld_eps : 0, stream);
+}
 extern "C" int zk_cnf_image_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2) {
   zk::CnfLayout L;
   const int widths[3] = {width0, width1, width2};

@@ -93,11 +93,12 @@ struct CnfAdjArgs {
   const float* al;
   const float* pre;
   const float* image;
+  const float* eps;
   float* ax_next;
   float* gpre;
   float* work;
   float* kbuf;
-  long long N, ldx, ldax, ldan, ld_pre, ld_gpre;
+  long long N, ldx, ldax, ldan, ld_pre, ld_gpre, ld_eps;
   int rows_per_chunk, lds_main;
   float t, dt, tscale;
   CnfLayout L;
@@ -266,9 +267,92 @@ __device__ __forceinline__ void adj_tangent(const CnfLayout& L, const CnfAdjLayo
   adj_put_feature(aW0x, Tt, T0, j, i);
 }
 
+// Hutchinson's estimate eps^T (df/dx) eps in place of the trace: ONE tangent, in the row's direction ep (held as a state: features 4 s + q, zero
+// behind F), forward and back.  Z_1 = W0x ep is a matrix product here (the x part of cnf_first_layer) and is formed again where Db_1 needs it,
+// as adj_tangent reads its column again; the seed Tb_L = W_last^T (beta ep) is the product that forms hb from `as`; the two gradients that are a
+// weight's column per feature in adj_tangent are outer products over the wave's rows here, those of the value reverse with ep for `as` and for x.
+// There is no gradient for ep.
+template <int NH>
+__device__ __forceinline__ void adj_probe(const CnfLayout& L, const CnfAdjLayout& B, const float* lds, float* scr, int lane, int j, int q, const float (&ep)[4], float beta,
+                                          float sigma, const mnn_f4 (&D)[3][MNN_BWD_TM], mnn_f4 (&Db)[3][MNN_BWD_TM], mnn_f4 (&aW1)[MNN_BWD_TM][MNN_BWD_TM],
+                                          mnn_f4 (&aW2)[MNN_BWD_TM][MNN_BWD_TM], bwd_tiles aWo, bwd_tiles aW0x) {
+  constexpr int TM = MNN_BWD_TM;
+  const int T0 = L.T[0], T1 = L.T[1], T2 = L.T[2], TL = L.T[NH - 1];
+  const float* const px = lds + L.o_w0x + lane;
+  mnn_f4 Z2[TM], Z3[TM], Tt[TM], Tb[TM], Zb[TM];
+  auto z1 = [&](auto o) MNN_INLINE {  // tile o of Z_1 = W0x ep
+    mnn_f4 z = bwd_zero();
+    mnn_for<4>([&](auto s) MNN_INLINE {
+      if (s < L.kx) z = __builtin_amdgcn_mfma_f32_16x16x4f32(px[(o * L.kx + s) * 64], ep[s], z, 0, 0, 0);
+    });
+    return z;
+  };
+  auto first = [&](bwd_tiles out) MNN_INLINE {  // T_1 = D_1 o Z_1
+    mnn_for<TM>([&](auto o) MNN_INLINE { out[o] = o < T0 ? D[0][o] * z1(o) : bwd_zero(); });
+  };
+  first(Tt);
+  if constexpr (NH > 1) adj_mv(lds + L.o_w[1], nullptr, T0, T1, lane, q, Tt, Z2);
+  if constexpr (NH > 2) {
+    adj_mul(D[1], Z2, T1, Tt);
+    adj_mv(lds + L.o_w[2], nullptr, T1, T2, lane, q, Tt, Z3);
+  }
+  // the last layer: Tb_L = W_last^T (beta ep), g W_last += sigma beta ep T_L^T
+  if constexpr (NH == 2) adj_mul(D[1], Z2, T1, Tt);
+  if constexpr (NH == 3) adj_mul(D[2], Z3, T2, Tt);
+  float EB[4];
+  adj_state_transpose(scr + 256, ep, lane, j, q, EB);
+  {
+    const float sb = sigma * beta;
+    const float* const pw = lds + B.o_woT + lane;
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      Tb[o] = bwd_zero();
+      if (o < TL) {
+        mnn_for<4>([&](auto k) MNN_INLINE {
+          if (k < L.kx) Tb[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(pw[(o * L.kx + k) * 64], beta * ep[k], Tb[o], 0, 0, 0);
+        });
+        float PA[4];
+        const mnn_f4 sc = Tt[o] * sb;
+        bwd_transpose(scr, sc, lane, j, q, PA);
+        mnn_for<4>([&](auto k) MNN_INLINE { aWo[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(PA[k], EB[k], aWo[o], 0, 0, 0); });
+      }
+    });
+  }
+  if constexpr (NH > 2) {
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < T2) Db[2][o] += Tb[o] * Z3[o];
+    });
+    adj_mul(Tb, D[2], T2, Zb);
+    adj_mul(D[1], Z2, T1, Tt);
+    bwd_outer<1, true>(scr, lane, j, q, T2, T1, &Zb, &Tt, aW2, sigma);
+    adj_mv(lds + B.o_wT[2], nullptr, T2, T1, lane, q, Zb, Tb);
+  }
+  if constexpr (NH > 1) {
+    mnn_for<TM>([&](auto o) MNN_INLINE {
+      if (o < T1) Db[1][o] += Tb[o] * Z2[o];
+    });
+    adj_mul(Tb, D[1], T1, Zb);
+    first(Tt);
+    bwd_outer<1, true>(scr, lane, j, q, T1, T0, &Zb, &Tt, aW1, sigma);
+    adj_mv(lds + B.o_wT[1], nullptr, T1, T0, lane, q, Zb, Tb);
+  }
+  // the first layer: Db_1 += Tb_1 o Z_1, g W0x += sigma (Tb_1 o D_1) ep^T (ep transposed again: four registers less across the hidden layers)
+  if constexpr (NH > 1) adj_state_transpose(scr + 256, ep, lane, j, q, EB);
+  mnn_for<TM>([&](auto o) MNN_INLINE {
+    if (o < T0) {
+      Db[0][o] += Tb[o] * z1(o);
+      float PA[4];
+      const mnn_f4 sc = Tb[o] * D[0][o] * sigma;
+      bwd_transpose(scr, sc, lane, j, q, PA);
+      mnn_for<4>([&](auto k) MNN_INLINE { aW0x[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(PA[k], EB[k], aW0x[o], 0, 0, 0); });
+    }
+  });
+}
+
 extern __shared__ __attribute__((aligned(16))) float cnf_adj_lds[];
 
-template <int NH, bool TAN> __global__ __launch_bounds__(MNN_THREADS, 1) void cnf_adj_kernel(CnfAdjArgs a) {
+// TAN: the trace term (al given); with PROBE (which implies TAN) Hutchinson's estimate along the row's eps instead of the exact trace
+template <int NH, bool TAN, bool PROBE = false> __global__ __launch_bounds__(MNN_THREADS, 1) void cnf_adj_kernel(CnfAdjArgs a) {
+  static_assert(TAN || !PROBE);
   constexpr int TM = MNN_BWD_TM;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
   const CnfLayout& L = a.L;
@@ -337,7 +421,11 @@ template <int NH, bool TAN> __global__ __launch_bounds__(MNN_THREADS, 1) void cn
       mnn_for<3>([&](auto l) MNN_INLINE {
         mnn_for<TM>([&](auto o) MNN_INLINE { Db[l][o] = bwd_zero(); });
       });
-      if constexpr (TAN) {
+      if constexpr (PROBE) {
+        float ep[4];  // (read per stage, as x and ax are: nothing of it is held across the value passes)
+        mnn_for<4>([&](auto c) MNN_INLINE { ep[c] = 4 * c + q < L.F ? a.eps[rc * a.ld_eps + 4 * c + q] : 0.f; });
+        adj_probe<NH>(L, B, lds, scr, lane, j, q, ep, beta, sigma, D, Db, aW1, aW2, aWo, aW0x);
+      } else if constexpr (TAN) {
 #pragma unroll 1
         for (int i = 0; i < L.F; ++i) adj_tangent<NH>(L, B, lds, scr, lane, j, q, i, beta, sigma, D, Db, aW1, aW2, aWo, aW0x);
       }
@@ -493,8 +581,9 @@ __global__ __launch_bounds__(256) void cnf_adj_reduce_kernel(const float* __rest
   gparams[dst] += s;
 }
 
-static int cnf_adjoint_step(const zk_cnf_adj_args_v1* p, void* stream) {
-  if (!p || p->struct_size != sizeof(zk_cnf_adj_args_v1) || p->version != 1) return ZK_EINVAL;
+// the launcher of both argument blocks: P is zk_cnf_adj_args_v1 (eps = NULL) or zk_cnf_adj_args_v2, whose first fields are v1's
+template <class P> static int cnf_adjoint_step(const P* p, uint32_t version, const void* eps, long long ld_eps, void* stream) {
+  if (!p || p->struct_size != sizeof(P) || p->version != version) return ZK_EINVAL;
   CnfAdjArgs a;
   if (!cnf_adj_shape(p->features, p->freqs, p->n_hidden, p->width0, p->width1, p->width2, &a.L, &a.B)) return ZK_EINVAL;
   if (p->image_floats != a.B.total || p->grad_floats != a.B.g_total || p->N < 0) return ZK_EINVAL;
@@ -505,17 +594,21 @@ static int cnf_adjoint_step(const zk_cnf_adj_args_v1* p, void* stream) {
   if (p->N == 0) return 0;
   if (!p->x || !p->pre || !p->image || !p->gpre || !p->work) return ZK_EINVAL;
   if (p->gparams && !p->grad_table) return ZK_EINVAL;
+  if (eps && ld_eps < p->features) return ZK_EINVAL;
+  if (!p->al) eps = nullptr;  // the estimator belongs to the trace term: without al the probe is not read
   if (((uintptr_t)p->pre | (uintptr_t)p->image | (uintptr_t)p->gpre | (uintptr_t)p->work) % 16 != 0) return ZK_EINVAL;
   int chunks = 0;
   if (mnn_bwd_geometry(p->N, 1, CNF_ADJ_BLOCKS, &a.rows_per_chunk, &chunks) != 0) return ZK_EINVAL;
   a.x = (const float*)p->x; a.ax = (const float*)p->ax; a.al = (const float*)p->al; a.pre = (const float*)p->pre; a.image = (const float*)p->image;
+  a.eps = (const float*)eps; a.ld_eps = ld_eps;
   a.ax_next = (float*)p->ax_next; a.gpre = (float*)p->gpre; a.work = p->gparams ? (float*)p->work : nullptr;
   a.kbuf = (float*)p->work + (size_t)chunks * a.B.g_total;  // (behind the partials: the stages' k vectors, written and read by the lane that owns them)
   a.N = p->N; a.ldx = p->ldx; a.ldax = p->ld_ax; a.ldan = p->ld_ax_next; a.ld_pre = p->ld_pre; a.ld_gpre = p->ld_gpre;
   a.t = (float)p->t; a.dt = (float)p->dt; a.tscale = (float)p->trace_scale;
   a.lds_main = a.B.total > a.B.g_total ? a.B.total : a.B.g_total;
   const bool tan = p->al != nullptr;
-  const void* fn = a.L.nh == 1 ? (tan ? (const void*)cnf_adj_kernel<1, true> : (const void*)cnf_adj_kernel<1, false>)
+  const void* fn = eps ? (a.L.nh == 1 ? (const void*)cnf_adj_kernel<1, true, true> : a.L.nh == 2 ? (const void*)cnf_adj_kernel<2, true, true> : (const void*)cnf_adj_kernel<3, true, true>)
+                 : a.L.nh == 1 ? (tan ? (const void*)cnf_adj_kernel<1, true> : (const void*)cnf_adj_kernel<1, false>)
                  : a.L.nh == 2 ? (tan ? (const void*)cnf_adj_kernel<2, true> : (const void*)cnf_adj_kernel<2, false>)
                                : (tan ? (const void*)cnf_adj_kernel<3, true> : (const void*)cnf_adj_kernel<3, false>);
   hipStream_t st = (hipStream_t)stream;
@@ -528,7 +621,10 @@ static int cnf_adjoint_step(const zk_cnf_adj_args_v1* p, void* stream) {
 
 }  // namespace zk
 
-extern "C" int zk_cnf_adjoint_step(const zk_cnf_adj_args_v1* args, void* stream) { return zk::cnf_adjoint_step(args, stream); }
+extern "C" int zk_cnf_adjoint_step(const zk_cnf_adj_args_v1* args, void* stream) { return zk::cnf_adjoint_step(args, 1, nullptr, 0, stream); }
+extern "C" int zk_cnf_adjoint_step_v2(const zk_cnf_adj_args_v2* args, void* stream) {
+  return zk::cnf_adjoint_step(args, 2, args ? args->eps : nullptr, args ? (long long)args->ld_eps : 0, stream);
+}
 extern "C" int zk_cnf_adjoint_floats(int features, int freqs, int n_hidden, int width0, int width1, int width2, int* image_floats, int* grad_floats) {
   zk::CnfLayout L;
   zk::CnfAdjLayout B;

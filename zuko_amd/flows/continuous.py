@@ -29,7 +29,9 @@ class FFJTransform(LazyTransform):
 
     Without gradients, in float32 and with `exact=True`, a field inside the envelope of `zuko_amd.ops.cnf_supported` is integrated by the fused
     step kernel (csrc/cnf.hip); everything else — training, float64, exact=False, other activations or shapes — runs in torch ops.  With
-    `zuko_amd.ops.CNF_ADJOINT = True` (off by default) training on a field of widths up to 64 runs on the kernels too (csrc/cnf_backward.hip)."""
+    `zuko_amd.ops.CNF_ADJOINT = True` (off by default) training on a field of widths up to 64 runs on the kernels too (csrc/cnf_backward.hip), and
+    with `zuko_amd.ops.CNF_HUTCHINSON = True` (off by default) so does `exact=False`, forward and — with both switches — training: one tangent
+    along the probe per stage instead of `features`."""
 
     def __init__(self, features: int, context: int = 0, freqs: int = 3, atol: float = 1e-6, rtol: float = 1e-5, exact: bool = True, **kwargs) -> None:
         super().__init__()

@@ -6,8 +6,8 @@ otherwise — there is no CPU or eager-PyTorch fallback.  One documented excepti
 flow (mnn_forward / mnn_inverse) run as torch ops ON THE DEVICE for network shapes their kernels do not serve, for float64, for the gradient of the
 bisection inverse and, under autograd, for layers wider than 64 (the adjoint kernel's envelope: mnn_backward_supported).  Likewise the Gaussian mixture density (gmm_log_prob) runs the reference's expressions as torch ops
 ON THE DEVICE outside its kernels' envelope (features or components above 64, sample dimensions broadcast over a batch of mixtures).  And the
-continuous flow (cnf_integrate) hands every call its step kernel does not serve — gradients, float64, Hutchinson's estimator, other activations or
-shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.  The Gaussianization map (gauss_forward / gauss_inverse) runs the
+continuous flow (cnf_integrate) hands every call its step kernel does not serve — gradients (CNF_ADJOINT off), float64, Hutchinson's estimator (CNF_HUTCHINSON
+off), other activations or shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.  The Gaussianization map (gauss_forward / gauss_inverse) runs the
 reference's expressions as torch ops ON THE DEVICE for more than 64 components (32 with gradients), for float64 calls that need gradients and under
 GAUSS_KERNEL = False.
 """
@@ -1363,7 +1363,8 @@ def gmm_log_prob(x: Tensor, phi: Tensor, components: int, covariance_type: str =
 # ------------------------------------------------------------------------------------------------
 
 CNF_KERNEL = True  # False: every call takes the torch-op path (scripts/bench_cnf.py measures the kernel against it)
-CNF_STATS: dict = {}  # the last integration: path ("kernel" | "torch"); on the kernel path also attempts, accepted and t_end (the time reached)
+CNF_STATS: dict = {}  # the last integration: path ("kernel" | "torch"); on the kernel path also attempts, accepted, t_end (the time reached) and trace ("exact" | "hutchinson")
+CNF_HUTCHINSON = False  # True: call_and_ladj of an exact=False transform integrates on the kernels too (the probe variant of zk_cnf_step_v2 / zk_cnf_adjoint_step_v2)
 
 
 def cnf_supported(features: int, context: int = 0, hidden_features=(64, 64), freqs: int = 3, activation=None) -> bool:
@@ -1400,23 +1401,30 @@ def _cnf_kernel_serves(module, c, x: Tensor):
     return cnf_plan.image_of(module, x.device)
 
 
-def cnf_step(img, x: Tensor, l, pre: Tensor, t: float, dt: float, atol: float, rtol: float, trace_scale: float, y: Tensor, l_next, err: Tensor, err_rows=None) -> None:
+def cnf_step(img, x: Tensor, l, pre: Tensor, t: float, dt: float, atol: float, rtol: float, trace_scale: float, y: Tensor, l_next, err: Tensor, err_rows=None, *,
+             eps=None) -> None:
     """One attempted Dormand-Prince step on zk_cnf_step: x [N, F] (unit column stride), l [N] | None (None: the value alone, no trace), pre
-    [N, H1] or [H1] (one row for every x row) -> y, l_next, and the largest error ratio in `err` (one float, zeroed by the caller)."""
+    [N, H1] or [H1] (one row for every x row) -> y, l_next, and the largest error ratio in `err` (one float, zeroed by the caller).  With `eps`
+    [N, F] (unit column stride; needs l) the trace is Hutchinson's estimate eps^T (df/dx) eps, on zk_cnf_step_v2."""
     lay = img.layout
     w = list(lay.widths) + [0, 0]
     N, F = x.shape
-    a = _C.args("zk_cnf_args_v1", features=F, freqs=lay.Q, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], image_floats=lay.total,
+    probe = {} if eps is None else dict(eps=eps.data_ptr(), ld_eps=eps.stride(0) if N > 1 else F)
+    a = _C.args("zk_cnf_args_v1" if eps is None else "zk_cnf_args_v2", **probe, features=F, freqs=lay.Q, n_hidden=len(lay.widths), width0=w[0], width1=w[1], width2=w[2], image_floats=lay.total,
                 n_tangents=0 if l is None else F, N=N, ldx=x.stride(0) if N > 1 else F, ldy=y.stride(0) if N > 1 else F,
                 ld_pre=0 if pre.dim() == 1 else (pre.stride(0) if N > 1 else lay.widths[0]), t=t, dt=dt, atol=atol, rtol=rtol, trace_scale=trace_scale,
                 x=x.data_ptr(), l=None if l is None else l.data_ptr(), pre=pre.data_ptr(), image=img.data.data_ptr(), y=y.data_ptr(),
                 l_next=None if l_next is None else l_next.data_ptr(), err=err.data_ptr(), err_rows=None if err_rows is None else err_rows.data_ptr())
-    _C.check(_C.lib().zk_cnf_step(a, _stream()), "zk_cnf_step")
+    if eps is None:
+        _C.check(_C.lib().zk_cnf_step(a, _stream()), "zk_cnf_step")
+    else:
+        _C.check(_C.lib().zk_cnf_step_v2(a, _stream()), "zk_cnf_step_v2")
 
 
-def _cnf_run(module, img, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool, keep: bool):
+def _cnf_run(module, img, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool, keep: bool, eps=None):
     """The controller's loop on zk_cnf_step: (x(t1) [N, F], l(t1) [N] | None, the broadcast shape, pre, the accepted steps, the statistics).  With
-    `keep` every accepted step leaves (a clone of the state after it, the time after it, its size) for the adjoint: N F floats per step."""
+    `keep` every accepted step leaves (a clone of the state after it, the time after it, its size) for the adjoint: N F floats per step.  `eps`
+    [N, F]: the probe of Hutchinson's estimator, the same for every attempt."""
     from .utils import step_factor
 
     if torch.cuda.is_current_stream_capturing():
@@ -1457,7 +1465,7 @@ def _cnf_run(module, img, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
         dt = f32(sign * min(abs(dt), abs(rest)))
         while True:
             err.zero_()
-            cnf_step(img, cur, l_cur, pre, float(t), float(dt), atol, rtol, trace_scale, spare, l_spare, err)
+            cnf_step(img, cur, l_cur, pre, float(t), float(dt), atol, rtol, trace_scale, spare, l_spare, err, eps=eps)
             ratio = float(err.item())
             attempts += 1
             if not math.isfinite(ratio):
@@ -1474,10 +1482,20 @@ def _cnf_run(module, img, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
             if ok:
                 break
     del data
-    return cur, l_cur, shape, pre, steps, dict(path="kernel", attempts=attempts, accepted=accepted, t_end=float(t))
+    stats = dict(path="kernel", attempts=attempts, accepted=accepted, t_end=float(t))
+    if with_ladj:
+        stats["trace"] = "exact" if eps is None else "hutchinson"
+    return cur, l_cur, shape, pre, steps, stats
 
 
-def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool, phi=()):
+def _cnf_probe_ok(c, x: Tensor, eps) -> bool:
+    """The estimator's call is served when x already has the broadcast batch shape (the probe is drawn like x) and a given probe is x's like."""
+    if c is not None and torch.broadcast_shapes(x.shape[:-1], c.shape[:-1]) != x.shape[:-1]:
+        return False
+    return eps is None or (eps.shape == x.shape and eps.dtype == x.dtype and eps.device == x.device and not (torch.is_grad_enabled() and eps.requires_grad))
+
+
+def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol: float, trace_scale: float, with_ladj: bool, phi=(), hutchinson: bool = False, eps=None):
     """(x(t1), l(t1) | None) of the free-form Jacobian ODE of `module` (a zuko_amd.flows.FFJTransform) from x(t0) = x, l(t0) = 0, on the step kernel —
     or None when the kernel does not serve the call (the caller then integrates in torch ops).  l is the log-determinant times `trace_scale`.
 
@@ -1488,16 +1506,23 @@ def cnf_integrate(module, c, x: Tensor, t0: float, t1: float, atol: float, rtol:
 
     A call that asks for gradients is served only with CNF_ADJOINT on and a field zk_cnf_adjoint_step serves (cnf_backward_supported): it goes
     through CnfIntegrateFn, which gives gradients to x and to the tensors of `phi` (the transform's: the context and, in train() mode, the
-    parameters), as the reference's adjoint does."""
+    parameters), as the reference's adjoint does.
+
+    `hutchinson` (with_ladj, CNF_HUTCHINSON on): l integrates Hutchinson's estimate eps^T (df/dx) eps of the trace on the probe variant of the
+    kernels.  The probe is `eps` [like x] or ONE torch.randn_like(x), drawn here once the call is known to be served — where the torch-op path
+    draws its own — and constant over the integration; it has no gradient."""
+    if hutchinson and not (CNF_HUTCHINSON and with_ladj and _cnf_probe_ok(c, x, eps)):
+        return None
     img = _cnf_kernel_serves(module, c, x)
     if img is None:
         img = _cnf_adjoint_serves(module, c, x, phi)
         if img is None:
             return None
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in phi)):
-            out = CnfIntegrateFn.apply((module, c, t0, t1, atol, rtol, trace_scale, with_ladj), x, *phi)
-            return (out[0], out[1]) if with_ladj else (out, None)
-    cur, l_cur, shape, _, _, stats = _cnf_run(module, img, c, x, t0, t1, atol, rtol, trace_scale, with_ladj, False)
+    eps = (torch.randn_like(x) if eps is None else eps.detach()).reshape(-1, x.shape[-1]).contiguous() if hutchinson else None
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in phi)):
+        out = CnfIntegrateFn.apply((module, c, t0, t1, atol, rtol, trace_scale, with_ladj, eps), x, *phi)
+        return (out[0], out[1]) if with_ladj else (out, None)
+    cur, l_cur, shape, _, _, stats = _cnf_run(module, img, c, x, t0, t1, atol, rtol, trace_scale, with_ladj, False, eps)
     CNF_STATS.clear()
     CNF_STATS.update(stats)
     return cur.reshape(shape), (l_cur.reshape(shape[:-1]) if with_ladj else None)
@@ -1538,19 +1563,25 @@ def _cnf_adjoint_serves(module, c, x: Tensor, phi):
     return cnf_plan.image_of(module, x.device)
 
 
-def cnf_adjoint_step(bimg, x: Tensor, ax: Tensor, al, pre: Tensor, t: float, dt: float, trace_scale: float, ax_next: Tensor, gpre: Tensor, gparams, work: Tensor) -> None:
+def cnf_adjoint_step(bimg, x: Tensor, ax: Tensor, al, pre: Tensor, t: float, dt: float, trace_scale: float, ax_next: Tensor, gpre: Tensor, gparams, work: Tensor, *,
+                     eps=None) -> None:
     """One reverse step on zk_cnf_adjoint_step: x [N, F] the checkpoint after the forward step (t, dt), ax [N, F], al [N] | None -> ax_next; gpre
-    [N, H1] and gparams [flat] | None are added to.  `work`: cnf_adjoint_workspace(bimg, N) floats."""
+    [N, H1] and gparams [flat] | None are added to.  `work`: cnf_adjoint_workspace(bimg, N) floats.  With `eps` [N, F] (unit column stride), the
+    probe of the forward steps, the trace term is that of Hutchinson's estimate, on zk_cnf_adjoint_step_v2 (al = None: the probe is not read)."""
     lay = bimg.layout
     w = list(lay.fwd.widths) + [0, 0]
     N, F = x.shape
-    a = _C.args("zk_cnf_adj_args_v1", features=F, freqs=lay.fwd.Q, n_hidden=len(lay.fwd.widths), width0=w[0], width1=w[1], width2=w[2], image_floats=lay.total,
+    probe = {} if eps is None else dict(eps=eps.data_ptr(), ld_eps=eps.stride(0) if N > 1 else F)
+    a = _C.args("zk_cnf_adj_args_v1" if eps is None else "zk_cnf_adj_args_v2", **probe, features=F, freqs=lay.fwd.Q, n_hidden=len(lay.fwd.widths), width0=w[0], width1=w[1], width2=w[2], image_floats=lay.total,
                 grad_floats=lay.g_total, N=N, ldx=x.stride(0) if N > 1 else F, ld_ax=ax.stride(0) if N > 1 else F, ld_ax_next=ax_next.stride(0) if N > 1 else F,
                 ld_pre=0 if pre.dim() == 1 else (pre.stride(0) if N > 1 else w[0]), ld_gpre=gpre.stride(0) if N > 1 else w[0],
                 flat_total=0 if gparams is None else gparams.numel(), t=t, dt=dt, trace_scale=trace_scale, x=x.data_ptr(), ax=ax.data_ptr(),
                 al=None if al is None else al.data_ptr(), pre=pre.data_ptr(), image=bimg.data.data_ptr(), grad_table=bimg.table.data_ptr(), ax_next=ax_next.data_ptr(),
                 gpre=gpre.data_ptr(), gparams=None if gparams is None else gparams.data_ptr(), work=work.data_ptr())
-    _C.check(_C.lib().zk_cnf_adjoint_step(a, _stream()), "zk_cnf_adjoint_step")
+    if eps is None:
+        _C.check(_C.lib().zk_cnf_adjoint_step(a, _stream()), "zk_cnf_adjoint_step")
+    else:
+        _C.check(_C.lib().zk_cnf_adjoint_step_v2(a, _stream()), "zk_cnf_adjoint_step_v2")
 
 
 def cnf_adjoint_workspace(bimg, N: int) -> int:
@@ -1564,15 +1595,16 @@ def cnf_adjoint_workspace(bimg, N: int) -> int:
 class CnfIntegrateFn(torch.autograd.Function):
     """x(t1) (and l(t1)) on zk_cnf_step, keeping every accepted step; backward makes one zk_cnf_adjoint_step per kept step in reverse — no host
     synchronisation — and turns gpre into the gradients of b0, the context's columns of W0 and the context.  Inputs: the settings, x, and the
-    transform's phi; gradients go to x and to exactly those tensors."""
+    transform's phi; gradients go to x and to exactly those tensors.  The settings end with the probe of Hutchinson's estimator ([N, F] | None):
+    the node keeps it (N F floats) and gives it to every reverse step."""
 
     @staticmethod
     def forward(ctx, cfg, x, *phi):
         from . import cnf_plan
 
-        module, c, t0, t1, atol, rtol, trace_scale, with_ladj = cfg
+        module, c, t0, t1, atol, rtol, trace_scale, with_ladj, eps = cfg
         img = cnf_plan.image_of(module, x.device)
-        cur, l_cur, shape, pre, steps, stats = _cnf_run(module, img, c, x, t0, t1, atol, rtol, trace_scale, with_ladj, True)
+        cur, l_cur, shape, pre, steps, stats = _cnf_run(module, img, c, x, t0, t1, atol, rtol, trace_scale, with_ladj, True, eps)
         ctx.set_materialize_grads(False)
         ctx.cfg, ctx.steps, ctx.pre, ctx.shape, ctx.x_shape, ctx.phi = cfg, steps, pre, shape, x.shape, phi
         CNF_STATS.clear()
@@ -1585,7 +1617,7 @@ class CnfIntegrateFn(torch.autograd.Function):
     def backward(ctx, gy, gl=None):
         from . import cnf_plan
 
-        module, c, _, _, _, _, trace_scale, with_ladj = ctx.cfg
+        module, c, _, _, _, _, trace_scale, with_ladj, eps = ctx.cfg
         shape, pre, phi = ctx.shape, ctx.pre, ctx.phi
         F = shape[-1]
         dev = pre.device
@@ -1601,7 +1633,7 @@ class CnfIntegrateFn(torch.autograd.Function):
         gparams = torch.zeros(bimg.flat_total, dtype=torch.float32, device=dev) if want_params else None
         work = torch.empty(max(cnf_adjoint_workspace(bimg, N), 4), dtype=torch.float32, device=dev)
         for xs, t, dt in reversed(ctx.steps):
-            cnf_adjoint_step(bimg, xs, ax, al, pre, t, dt, trace_scale, spare, gpre, gparams, work)
+            cnf_adjoint_step(bimg, xs, ax, al, pre, t, dt, trace_scale, spare, gpre, gparams, work, eps=eps)
             ax, spare = spare, ax
         del data
         CNF_STATS["adjoint_steps"] = len(ctx.steps)

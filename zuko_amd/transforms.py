@@ -595,8 +595,11 @@ class FreeFormJacobianTransform(Transform):
     `kernel` = (module, c), given by `zuko_amd.flows.FFJTransform`: the field's module and the context.  A call without gradients in float32 on
     the device, `exact=True`, on a field csrc/cnf.hip serves (ops.cnf_supported) is integrated by ops.cnf_integrate — one launch per attempted
     step.  With `ops.CNF_ADJOINT` on, a call that asks for gradients on a field csrc/cnf_backward.hip serves (ops.cnf_backward_supported) goes
-    through ops.CnfIntegrateFn: the same forward, and one zk_cnf_adjoint_step per accepted step backwards.  Every other call integrates `f` in torch
-    ops (zuko_amd.utils.odeint), with the reference's adjoint for the gradients."""
+    through ops.CnfIntegrateFn: the same forward, and one zk_cnf_adjoint_step per accepted step backwards.  With `ops.CNF_HUTCHINSON` on (off by
+    default), `call_and_ladj` of an `exact=False` transform is served under the same conditions by the probe variant of both kernels
+    (zk_cnf_step_v2 / zk_cnf_adjoint_step_v2: one tangent along the probe instead of one per feature) when `x` already has the batch shape of
+    the result; the probe is `eps` or one `torch.randn_like(x)` drawn before the integration, as on the torch-op path, and constant over it.
+    Every other call integrates `f` in torch ops (zuko_amd.utils.odeint), with the reference's adjoint for the gradients."""
 
     domain = constraints.real_vector
     codomain = constraints.real_vector
@@ -615,13 +618,14 @@ class FreeFormJacobianTransform(Transform):
         self.kernel = kernel
         self.trace_scale = 1e-2  # (the log-determinant enters the error estimate at a hundredth of its size)
 
-    def _integrate(self, x: Tensor, t0, t1, with_ladj: bool):
-        """The kernel path's result, or None when the call belongs to the torch-op path."""
+    def _integrate(self, x: Tensor, t0, t1, with_ladj: bool, eps: Tensor | None = None):
+        """The kernel path's result, or None when the call belongs to the torch-op path.  `eps`: the probe call_and_ladj was given (exact=False)."""
         ops._require_device(x)
-        if self.kernel is None or (with_ladj and not self.exact):
+        hutchinson = with_ladj and not self.exact
+        if self.kernel is None or (hutchinson and not ops.CNF_HUTCHINSON):
             return None
         module, c = self.kernel
-        return ops.cnf_integrate(module, c, x, float(t0), float(t1), self.atol, self.rtol, self.trace_scale, with_ladj, self.phi)
+        return ops.cnf_integrate(module, c, x, float(t0), float(t1), self.atol, self.rtol, self.trace_scale, with_ladj, self.phi, hutchinson, eps)
 
     def _call(self, x: Tensor) -> Tensor:
         out = self._integrate(x, self.t0, self.t1, False)
@@ -667,7 +671,7 @@ class FreeFormJacobianTransform(Transform):
 
     def call_and_ladj(self, x: Tensor, eps: Tensor | None = None):
         """(y, log|det dy/dx|).  `eps` fixes the probe of Hutchinson's estimator (exact=False; default: a standard-normal draw)."""
-        out = self._integrate(x, self.t0, self.t1, True)
+        out = self._integrate(x, self.t0, self.t1, True, eps)
         if out is not None:
             return out[0], out[1] * (1 / self.trace_scale)
         from .utils import odeint
