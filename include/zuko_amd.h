@@ -505,6 +505,19 @@ int zk_bernstein_backward(int64_t N, int64_t D, int M, int bounded, double bound
  * gl ([N] if gl_reduced else [N, D]) may be NULL; outputs gx [N, D], gphi [N, D, 2K].  No atomics. */
 int zk_gauss_backward(int64_t N, int64_t D, int K, const void* x, const void* phi, const void* gy, const void* gl, int gl_reduced,
                       void* gx, void* gphi, void* stream);
+/* The same adjoint for ONE parameter table shared by all rows (the unconditional GF; fp32): phi [D, 2K] = [shift(K) | scale(K)],
+ * gx [N, D] as zk_gauss_backward gives it for the same element, gphi [D, 2K] = the per-element parameter gradients summed over
+ * the N rows inside the kernel.  1 <= K <= 32 (another K returns hipErrorInvalidValue before anything is launched); phi and gphi
+ * contiguous and 16-byte aligned (else hipErrorInvalidValue); gy [N, D] / gl ([N] if gl_reduced else [N, D]) may be NULL;
+ * N <= 0 or D <= 0 returns 0 and launches nothing.  The library allocates nothing: `work` holds
+ * zk_gauss_backward_shared_floats(N, D, K) floats (a 64-bit count, spelled `long long int`; <= 0 for a shape the kernel does not
+ * serve), one [D, 2K] partial per row chunk.  Two launches on `stream`: the first writes gx and the chunks' partials, the second
+ * adds the partials in chunk order.  The partition is a function of (N, D, K) alone: a pass is 4 * (64 / min(64, D)) rows, a
+ * chunk has eight passes until there are max(1, 1024 / ceil(D / 64)) chunks, beyond that the passes are split evenly over that
+ * many.  No atomics, no block waits for another: the same inputs give the same bits on every run. */
+long long int zk_gauss_backward_shared_floats(int64_t N, int64_t D, int K);
+int zk_gauss_backward_shared(int64_t N, int64_t D, int K, const void* x, const void* phi, const void* gy, const void* gl, int gl_reduced,
+                             void* gx, void* work, void* gphi, void* stream);
 /* Adjoint seeds of an INVERSE univariate map x = f^{-1}(y) (gradients through rsample; inverse function theorem):
  * gy[e] = gx[e] * exp(-ladj[e]) with ladj = log f'(x), seed[e] = -gy[e] (zk_univariate_backward(x, phi, gy = seed) then
  * yields dL/dphi). */

@@ -6,6 +6,8 @@ alternating in one process.  Device events over >= 0.5 s of work per measurement
     python scripts/bench_gf.py                 # prints one JSON line
     rocprofv3 --kernel-trace --stats -- python scripts/bench_gf.py --trace     # per-launch kernel times (kernel path, few calls, a sample() for the inverse)
     python scripts/bench_gf.py --rows DIR      # the Gaussianization kernels' dispatches in the *_kernel_trace.csv under DIR, grouped (no GPU needed)
+    python scripts/bench_gf.py --shared-adjoint   # the same line, plus the unconditional training step with ops.GAUSS_SHARED_ADJOINT on and off
+                                                  # (step time, peak memory, zk_gauss_backward_shared per launch); with --trace: three such steps more
 
 Rooflines.  Conditional forward: 4 + 8 K + 4 bytes per element (x, the packed parameters, y; ladj is one float per row) against 8 TB/s
 of HBM.  Shared parameters: 2 K floats per feature stay in cache, the kernel is bound by its arithmetic: per element and component one exp (the scale), one
@@ -30,7 +32,7 @@ from zuko_amd.flows import GF
 PEAK_HBM = 8.0e12
 D, C, T, K = 64, 16, 3, 8
 N_LOG_PROB, N_TRAIN = 2**18, 2**16
-KERNELS = ("GaussOp", "gauss_backward")
+KERNELS = ("GaussOp", "gauss_backward", "gauss_shared_reduce")
 
 
 def timed(fn, min_seconds: float = 0.5, warmup: int = 3):
@@ -89,6 +91,50 @@ def workload(context: int, dev):
     return flow, log_prob, step, sample
 
 
+def with_shared(on, fn):
+    def run():
+        ops.GAUSS_SHARED_ADJOINT = on
+        try:
+            return fn()
+        finally:
+            ops.GAUSS_SHARED_ADJOINT = False
+
+    return run
+
+
+def shared_adjoint(dev) -> dict:
+    """--shared-adjoint: the unconditional training step with ops.GAUSS_SHARED_ADJOINT on and off, alternating (two rounds each); one step's peak of
+    allocated memory over the level before it; the adjoint launches by events around the entry points."""
+    _, _, step, _ = workload(0, dev)
+    names = {True: "shared_on", False: "shared_off"}
+    runs = {True: [], False: []}
+    for rnd in range(2):
+        for on in (True, False):
+            runs[on].append(timed(with_shared(on, step)))
+    res = {}
+    for on, rs in runs.items():
+        res[f"train_step_{names[on]}"] = min(rs, key=lambda r: r["median_ms"]) | {"medians_ms": [round(r["median_ms"], 3) for r in rs]}
+    res["train_step_shared_speedup"] = res["train_step_shared_off"]["median_ms"] / res["train_step_shared_on"]["median_ms"]
+    for on in (True, False):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        with_shared(on, step)()
+        torch.cuda.synchronize()
+        res[f"train_step_{names[on]}_peak_bytes"] = torch.cuda.max_memory_allocated()
+        res[f"train_step_{names[on]}_peak_bytes_over_start"] = torch.cuda.max_memory_allocated() - before
+        _C.PROFILE = {}
+        with_shared(on, step)()
+        torch.cuda.synchronize()
+        prof, _C.PROFILE = _C.PROFILE, None
+        for sym in ("zk_gauss_backward_shared", "zk_gauss_backward"):
+            ts = [a.elapsed_time(b) * 1e-3 for a, b, _ in prof.get(sym, [])]
+            if ts:
+                res[f"{sym}_event_ms"] = round(1e3 * min(ts), 4)
+                res[f"{sym}_component_evaluations_per_s"] = N_TRAIN * D * K * 2 / min(ts)
+    return res
+
+
 def kernel_rows(stats_dir: str) -> list:
     """The Gaussianization kernels' dispatches in a rocprofv3 --kernel-trace output directory, grouped by (kernel, grid): the grid tells the 2^18-row
     inference call from the 2^16-row training step; `us` keeps the dispatch order (--trace runs the unconditional flow first)."""
@@ -118,6 +164,8 @@ def main() -> None:
                 log_prob()
                 step()
                 sample()
+                if "--shared-adjoint" in sys.argv and not context:
+                    with_shared(True, step)()
         torch.cuda.synchronize()
         return
     out = {"workload": f"GF(features={D}, transforms={T}, components={K})", "log_prob_batch": N_LOG_PROB, "train_batch": N_TRAIN}
@@ -158,6 +206,8 @@ def main() -> None:
         out["conditional" if context else "unconditional"] = res
         del flow
         torch.cuda.empty_cache()
+    if "--shared-adjoint" in sys.argv:
+        out["unconditional"]["shared_adjoint"] = shared_adjoint(dev)
     out["version"] = zuko_amd.__version__
     print(json.dumps(out))
 

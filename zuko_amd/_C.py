@@ -107,7 +107,7 @@ _CNF_ADJ = POINTER(STRUCTS["zk_cnf_adj_args_v1"])
 _CNF2 = POINTER(STRUCTS["zk_cnf_args_v2"])
 _CNF_ADJ2 = POINTER(STRUCTS["zk_cnf_adj_args_v2"])
 
-# symbol -> argument types (return type is always int = hipError_t)
+# symbol -> argument types (the return type is int = hipError_t unless RESTYPES below names another)
 SIGNATURES = {
     "zk_rqs_forward": [I, L, L, I, F, F, P, P, L, L, P, L, L, P, L, L, P, P, I, P, P],
     "zk_rqs_inverse": [I, L, L, I, F, F, P, P, L, L, P, L, L, P, L, L, P, P, P],
@@ -122,6 +122,8 @@ SIGNATURES = {
     "zk_gauss_forward": [I, L, L, I, P, P, L, L, P, L, L, P, P, I, P],
     "zk_gauss_inverse": [I, L, L, I, F, I, P, P, L, L, P, L, L, P, P],
     "zk_gauss_backward": [L, L, I, P, P, P, P, I, P, P, P],
+    "zk_gauss_backward_shared_floats": [L, L, I],
+    "zk_gauss_backward_shared": [L, L, I, P, P, P, P, I, P, P, P, P],
     "zk_linear": [I, L, I, I, P, L, P, P, P, I, P, L, P],
     "zk_linear_bf16": [L, I, I, P, L, P, P, P, I, P, L, P],
     "zk_linear_bf16_rqs": [L, I, I, P, L, P, P, P, I, I, F, F, P, L, P, L, P, P, P],
@@ -196,6 +198,9 @@ SIGNATURES = {
 }
 
 
+RESTYPES = {"zk_gauss_backward_shared_floats": c_int64}  # the size queries that return a 64-bit count instead of a hipError_t
+
+
 class _Lib:
     def __init__(self, path: str) -> None:
         if not os.path.exists(path):
@@ -208,7 +213,7 @@ class _Lib:
         for name, argtypes in SIGNATURES.items():
             fn = getattr(self.cdll, name)  # AttributeError -> loud failure on a stale library
             fn.argtypes = argtypes
-            fn.restype = c_int
+            fn.restype = RESTYPES.get(name, c_int)
             setattr(self, name, _timed(name, fn))
 
 

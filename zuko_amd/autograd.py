@@ -291,6 +291,96 @@ class UnivariateInverseFn(torch.autograd.Function):
         return (None, None, None, None, _sum_to(gy, ctx.yshape), *grads)
 
 
+def _gauss_shared_adjoint(x: Tensor, phi: Tensor, gy, gl, reduce: bool):
+    """(gx [*, D], gphi [D, 2K]) of the Gaussianization map with ONE parameter table for all rows: zk_gauss_backward_shared, the sum over the rows
+    taken inside the kernel (its workspace: one [D, 2K] partial per row chunk)."""
+    D, K = x.shape[-1], phi.shape[-1] // 2
+    N = x.numel() // max(D, 1)
+    gx = torch.empty_like(x)
+    if N == 0 or D == 0:
+        return gx, torch.zeros_like(phi)
+    lib = _C.lib()
+    floats = lib.zk_gauss_backward_shared_floats(N, D, K)
+    if floats <= 0:
+        raise NotImplementedError("zuko_amd: the shared-parameter Gaussianization adjoint is built for 1 to 32 components")
+    work = torch.empty(floats, dtype=torch.float32, device=x.device)
+    gphi = torch.empty_like(phi)
+    err = lib.zk_gauss_backward_shared(N, D, K, _ptr(x), _ptr(phi), _ptr(gy), _ptr(gl), int(reduce), _ptr(gx), _ptr(work), _ptr(gphi), _stream())
+    _C.check(err, "zk_gauss_backward_shared")
+    return gx, gphi
+
+
+def _gauss_shared_phi(shift: Tensor, scale: Tensor) -> Tensor:
+    return torch.cat([shift.detach(), scale.detach()], dim=-1).contiguous()  # [D, 2K] = [shift | scale]
+
+
+class GaussSharedFn(torch.autograd.Function):
+    """(y, ladj) of the Gaussianization map for parameters [D, K] shared by all rows (ops.gauss_shared_supported): the forward reads them in place
+    (row stride 0, the inference path), the backward is one zk_gauss_backward_shared call.  Nothing of N * D * K elements is created: saved are x and
+    the packed [D, 2K] table."""
+
+    @staticmethod
+    def forward(ctx, reduce: bool, x: Tensor, shift: Tensor, scale: Tensor):
+        from . import ops
+
+        _require_f32(x, shift, scale)
+        K = shift.shape[-1]
+        xe = x.detach().contiguous()
+        phi = _gauss_shared_phi(shift, scale)
+        with torch.no_grad():
+            y, ladj = ops.gauss_forward(xe, phi[:, :K], phi[:, K:], reduce)
+        ctx.reduce = reduce
+        ctx.set_materialize_grads(False)  # an unused output's weight stays None: the kernel takes NULL for it
+        ctx.save_for_backward(xe, phi)
+        return y, ladj
+
+    @staticmethod
+    @once_differentiable  # raw-pointer HIP kernels on detached data: double backward (create_graph=True) must raise, not return graph-less grads
+    def backward(ctx, gy, gl):
+        xe, phi = ctx.saved_tensors
+        K = phi.shape[-1] // 2
+        gy_c = None if gy is None else gy.expand(xe.shape).contiguous()
+        gl_c = None if gl is None else (gl.expand(xe.shape[:-1]) if ctx.reduce else gl.expand(xe.shape)).contiguous()
+        gx, gphi = _gauss_shared_adjoint(xe, phi, gy_c, gl_c, ctx.reduce)
+        need = ctx.needs_input_grad
+        return (None, gx if need[1] else None, gphi[:, :K] if need[2] else None, gphi[:, K:] if need[3] else None)
+
+
+class GaussSharedInverseFn(torch.autograd.Function):
+    """x = f^{-1}(y) for parameters [D, K] shared by all rows: UnivariateInverseFn's inverse function theorem (seed -g_x / f'(x) into the forward
+    map's adjoint at the solution) on zk_gauss_inverse / zk_gauss_forward with row stride 0 and zk_gauss_backward_shared."""
+
+    @staticmethod
+    def forward(ctx, bound: float, eps: float, y: Tensor, shift: Tensor, scale: Tensor):
+        from . import ops
+
+        _require_f32(y, shift, scale)
+        K = shift.shape[-1]
+        phi = _gauss_shared_phi(shift, scale)
+        with torch.no_grad():
+            x = ops.gauss_inverse(y.detach().contiguous(), phi[:, :K], phi[:, K:], bound, eps)
+        ctx.save_for_backward(x, phi)
+        return x
+
+    @staticmethod
+    @once_differentiable  # raw-pointer HIP kernels on detached data: double backward (create_graph=True) must raise, not return graph-less grads
+    def backward(ctx, gx):
+        from . import ops
+
+        x, phi = ctx.saved_tensors
+        K = phi.shape[-1] // 2
+        with torch.no_grad():
+            _, ladj = ops.gauss_forward(x, phi[:, :K], phi[:, K:], False)
+        gxc = gx.expand(x.shape).contiguous()
+        gy, seed = torch.empty_like(x), torch.empty_like(x)
+        _C.check(_C.lib().zk_inverse_seed(x.numel(), _ptr(gxc), _ptr(ladj.contiguous()), _ptr(gy), _ptr(seed), _stream()), "zk_inverse_seed")
+        need = ctx.needs_input_grad
+        if not (need[3] or need[4]):
+            return (None, None, gy, None, None)
+        _, gphi = _gauss_shared_adjoint(x, phi, seed, None, False)
+        return (None, None, gy if need[2] else None, gphi[:, :K] if need[3] else None, gphi[:, K:] if need[4] else None)
+
+
 BACKWARD_ACTS = (0, 1, 2, 3, 6, 7)  # activations whose derivative is a function of their output
 
 

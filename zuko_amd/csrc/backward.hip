@@ -89,6 +89,94 @@ __global__ __launch_bounds__(256) void gauss_backward_kernel(BwdArgs a, int K) {
   uni_backward_frame(a, Dyn<2 * ZK_GAUSS_KMAX_BWD>{2 * K}, [&](float* slot, float x, float gyv, float glv) { return gauss_backward_element(K, slot, x, gyv, glv); });
 }
 
+// Gaussianization with ONE [D, 2K] parameter table shared by all rows (the unconditional GF): gx as above, and the table's gradient summed over the
+// rows inside the kernel instead of written per row.  Geometry: block (c, t) covers the rows of chunk c and the features d0 = 64 t ..
+// d0 + dw - 1, dw = min(64, D - d0); lane l of a wave stays on feature d0 + l % dw and walks the rows r + l / dw (64 / dw rows per wave and pass,
+// lanes beyond (64 / dw) dw idle), so x / gy / gx are read and written along the feature axis and a lane's [2K] running sums are its own LDS words.
+// LDS: acc[2K][256] (component-major: the 64 lanes of a wave touch 64 consecutive banks) | par[2K][64] (the tile's parameters transposed: lanes of
+// consecutive features read consecutive banks, lanes of one feature the same word).  At the end of the chunk the lanes of one feature are added in
+// the fixed order (wave, row slot) and the tile's [dw, 2K] partial goes to work[c]; gauss_shared_reduce_kernel adds the chunks.  No atomics.
+struct GaussSharedArgs {
+  int64_t N, D;
+  const float *x, *phi, *gy, *gl;
+  int gl_reduced, K;
+  float *gx, *work;
+  int64_t passes;  // of pass_rows rows each, split evenly over gridDim.x chunks
+  int pass_rows;
+};
+
+// the partition, a function of (N, D, K) alone: a pass is what one block covers of a full feature tile in one step (4 waves x 64 / min(64, D) rows); a
+// chunk has eight passes until there are GAUSS_SHARED_BLOCKS / tiles chunks, then the passes are split evenly over that many
+#define GAUSS_SHARED_BLOCKS 1024
+#define GAUSS_SHARED_MIN_PASSES 8
+static bool gauss_shared_geometry(int64_t N, int64_t D, int K, int* pass_rows, int64_t* passes, int64_t* chunks, int64_t* tiles) {
+  if (K < 1 || K > ZK_GAUSS_KMAX_BWD || N <= 0 || D <= 0) return false;
+  *tiles = (D + 63) / 64;
+  if (*tiles > 65535) return false;  // gridDim.y
+  *pass_rows = 4 * (64 / (int)(D < 64 ? D : 64));
+  *passes = (N + *pass_rows - 1) / *pass_rows;
+  const int64_t cap = GAUSS_SHARED_BLOCKS / *tiles > 1 ? GAUSS_SHARED_BLOCKS / *tiles : 1;
+  const int64_t want = (*passes + GAUSS_SHARED_MIN_PASSES - 1) / GAUSS_SHARED_MIN_PASSES;
+  *chunks = want < cap ? want : cap;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void gauss_backward_shared_kernel(GaussSharedArgs a) {
+  const int K = a.K, K2 = 2 * K;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t d0 = (int64_t)blockIdx.y * 64;
+  const int dw = (int)((a.D - d0) < 64 ? (a.D - d0) : 64);
+  const int rpw = 64 / dw;
+  float* acc = bw_lds;             // [2K][256]
+  float* par = bw_lds + K2 * 256;  // [2K][64]
+  const float* src = a.phi + d0 * K2;
+  for (int o = tid; o < dw * K2; o += 256) par[(o % K2) * 64 + o / K2] = src[o];
+  for (int k = 0; k < K2; ++k) acc[k * 256 + tid] = 0.f;
+  __syncthreads();
+  const int f = lane % dw, j = lane / dw;
+  const int64_t p0 = (int64_t)blockIdx.x * a.passes / gridDim.x, p1 = ((int64_t)blockIdx.x + 1) * a.passes / gridDim.x;
+  const int64_t r0 = p0 * a.pass_rows, rr = p1 * a.pass_rows, r1 = rr < a.N ? rr : a.N;
+  if (j < rpw) {
+    for (int64_t r = r0 + (tid >> 6) * rpw + j; r < r1; r += 4 * rpw) {
+      const int64_t e = r * a.D + d0 + f;
+      const float glv = a.gl ? (a.gl_reduced ? a.gl[r] : a.gl[e]) : 0.f;
+      const float gyv = a.gy ? a.gy[e] : 0.f;
+      a.gx[e] = gauss_backward_sweeps(K, [&](int k) { return par[k * 64 + f]; }, [&](int k) { return par[(K + k) * 64 + f]; },
+                                      [&](int k, float gb, float ga) { acc[k * 256 + tid] += gb; acc[(K + k) * 256 + tid] += ga; }, a.x[e], gyv, glv);
+    }
+  }
+  __syncthreads();
+  // the lanes of one feature in the order (wave, row slot); the sums replace the parameters, which nobody reads any more
+  for (int o = tid; o < dw * K2; o += 256) {
+    const int k = o / dw, ff = o % dw;
+    float s = 0.f;
+    for (int w = 0; w < 4; ++w)
+      for (int jj = 0; jj < rpw; ++jj) s += acc[k * 256 + w * 64 + jj * dw + ff];
+    par[k * 64 + ff] = s;
+  }
+  __syncthreads();
+  float* out = a.work + ((int64_t)blockIdx.x * a.D + d0) * K2;
+  for (int o = tid; o < dw * K2; o += 256) out[o] = par[(o % K2) * 64 + o / K2];
+}
+
+// gphi[pos] = the chunks' partials of pos: sixteen lanes share a position, lane g adds the chunks [g chunks / 16, (g + 1) chunks / 16) in order, the
+// sixteen sums are added in order (one writer per position)
+__global__ __launch_bounds__(256) void gauss_shared_reduce_kernel(const float* __restrict__ work, float* __restrict__ gphi, int chunks, int64_t total) {
+  __shared__ float part[16][16];
+  const int p = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int64_t pos = (int64_t)blockIdx.x * 16 + p;
+  float s = 0.f;
+  if (pos < total)
+    for (int c = (int)((int64_t)g * chunks / 16), c1 = (int)((int64_t)(g + 1) * chunks / 16); c < c1; ++c) s += work[(int64_t)c * total + pos];
+  part[g][p] = s;
+  __syncthreads();
+  if (g == 0 && pos < total) {
+    float t = part[0][p];
+    for (int i = 1; i < 16; ++i) t += part[i][p];
+    gphi[pos] = t;
+  }
+}
+
 // Any bin count up to 64 (zuko/transforms.py:469-477 accepts any `bins`): one lane per element, knots and softmax probabilities
 // in run-time indexed local arrays, parameters read from / gradients written to global memory directly.  A slow path next to the
 // K = 4 / 8 / 16 instantiations above, with the same arithmetic (max-subtracted softmax, strict-count bin search, the same
@@ -234,6 +322,40 @@ int zk_gauss_backward(int64_t N, int64_t D, int K, const void* x, const void* ph
   const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
   a.iters = (tiles + (int64_t)grid * 4 - 1) / ((int64_t)grid * 4);
   hipLaunchKernelGGL(gauss_backward_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a, K);
+  return ZK_LAUNCH_CHECK();
+}
+
+// Floats of `work` for zk_gauss_backward_shared: one [D, 2K] partial per row chunk; <= 0 for a shape the kernel does not serve.
+long long int zk_gauss_backward_shared_floats(int64_t N, int64_t D, int K) {
+  int pass_rows;
+  int64_t passes, chunks, tiles;
+  if (!gauss_shared_geometry(N, D, K, &pass_rows, &passes, &chunks, &tiles)) return 0;
+  return chunks * D * 2 * K;
+}
+
+// Gaussianization with parameters shared by all rows (phi [D, 2K] = [shift(K) | log-scale(K)], 1 <= K <= 32): gx [N, D] and gphi [D, 2K] summed over the rows.
+int zk_gauss_backward_shared(int64_t N, int64_t D, int K, const void* x, const void* phi, const void* gy, const void* gl, int gl_reduced, void* gx, void* work,
+                             void* gphi, void* stream) {
+  if (K < 1 || K > ZK_GAUSS_KMAX_BWD) return ZK_EINVAL;
+  if ((((uintptr_t)phi | (uintptr_t)gphi) % 16) != 0) return ZK_EINVAL;
+  if (N <= 0 || D <= 0) return 0;
+  GaussSharedArgs a{};
+  int64_t chunks, tiles;
+  if (!gauss_shared_geometry(N, D, K, &a.pass_rows, &a.passes, &chunks, &tiles)) return ZK_EINVAL;
+  if (!x || !phi || !gx || !work || !gphi) return ZK_EINVAL;
+  a.N = N; a.D = D; a.K = K; a.x = (const float*)x; a.phi = (const float*)phi; a.gy = (const float*)gy; a.gl = (const float*)gl; a.gl_reduced = gl_reduced;
+  a.gx = (float*)gx; a.work = (float*)work;
+  const size_t lds = (size_t)(256 + 64) * 2 * K * sizeof(float);
+  if (lds > 64 * 1024) {  // K >= 26; 80 KiB at K = 32
+    const hipError_t e = hipFuncSetAttribute((const void*)gauss_backward_shared_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(gauss_backward_shared_kernel, dim3((unsigned)chunks, (unsigned)tiles), dim3(256), lds, st, a);
+  const int rc = ZK_LAUNCH_CHECK();
+  if (rc != 0) return rc;
+  const int64_t total = D * 2 * K;
+  hipLaunchKernelGGL(gauss_shared_reduce_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, (const float*)work, (float*)gphi, (int)chunks, total);
   return ZK_LAUNCH_CHECK();
 }
 

@@ -136,27 +136,35 @@ __device__ __forceinline__ void affine_backward_element(const float* p, float x,
 //   S = sum_k s_k exp(-u_k^2/2),  f' = dy/dx = exp(ladj),  w_k = c exp((y^2 - u_k^2)/2) / K,  r_k = s_k exp(-u_k^2/2) / S:
 //   dy/db_k = w_k,                      dy/da_k = w_k x s_k,
 //   dladj/dx = y f' - sum_k r_k u_k s_k,  dladj/db_k = y w_k - r_k u_k,  dladj/da_k = x s_k dladj/db_k + r_k.
-// `slot`: the element's [b(K) | a(K)] in the wave's LDS image.  Two sweeps over it, no array sized by K: the first recomputes the forward and the
-// two sums, the second overwrites every parameter by its gradient (a lane's own words; a wave's DS operations execute in order).  Returns gx.
-__device__ __forceinline__ float gauss_backward_element(int K, float* slot, float x, float gyv, float glv) {
+// Two sweeps over the components, no array sized by K: the first recomputes the forward and the two sums, the second hands every component's
+// pair of gradients to `out(k, gb, ga)`.  `ldb(k)` / `lda(k)` read shift and log-scale k (twice each).  Returns gx.  The one statement of this
+// arithmetic: the per-row kernel stores the pair, the shared-parameter kernel adds it to the lane's running sums.
+template <typename LdB, typename LdA, typename Out>
+__device__ __forceinline__ float gauss_backward_sweeps(int K, LdB ldb, LdA lda, Out out, float x, float gyv, float glv) {
   float m, S, R;
-  const float y = gauss_sweep<float, 2>(K, [&](int k) { return slot[k]; }, [&](int k) { return slot[K + k]; }, x, m, S, R);
+  const float y = gauss_sweep<float, 2>(K, ldb, lda, x, m, S, R);
   const float fp = expf(gauss_ladj<float>(K, y, m, S));
   const float iS = S > 0.f ? 1.f / S : 0.f;
   const float gw = gyv + glv * y;  // what multiplies w_k (and f')
   const float cK = (1.f - 1e-6f) / (float)K;
   for (int k = 0; k < K; ++k) {
-    const float b = slot[k], a = slot[K + k];
+    const float b = ldb(k), a = lda(k);
     const float s = expf(a);
     const float u = x * s + b;
     const float w = cK * expf(0.5f * ((y - u) * (y + u)));
     const float t = a - 0.5f * (u * u);
     const float r = (t > -INFINITY) ? expf(t - m) * iS : 0.f;
     const float gb = gw * w - glv * (r * u);
-    slot[k] = gb;
-    slot[K + k] = (x * s) * gb + glv * r;
+    out(k, gb, (x * s) * gb + glv * r);
   }
   return gw * fp - glv * (R * iS);
+}
+
+// `slot`: the element's [b(K) | a(K)] in the wave's LDS image; the second sweep overwrites every parameter by its gradient (a lane's own words; a
+// wave's DS operations execute in order).  Returns gx.
+__device__ __forceinline__ float gauss_backward_element(int K, float* slot, float x, float gyv, float glv) {
+  return gauss_backward_sweeps(K, [&](int k) { return slot[k]; }, [&](int k) { return slot[K + k]; },
+                               [&](int k, float gb, float ga) { slot[k] = gb; slot[K + k] = ga; }, x, gyv, glv);
 }
 
 }  // namespace zk

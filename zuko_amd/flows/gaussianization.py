@@ -3,8 +3,10 @@ Mirrors zuko/flows/gaussianization.py:97-155 (same module tree, state_dict keys 
 
 Each element-wise layer is one launch of csrc/elementwise.hip's Gaussianization kernel (zuko_amd.transforms.GaussianizationTransform); the
 rotations and the base density run on torch ops (zuko_amd.transforms.RotationTransform).  Without a context the parameters are [features,
-components] tensors shared by all rows: training expands them to one packed copy per row (zuko_amd/autograd.py: UnivariateFn) and sums the
-gradient over the rows."""
+components] tensors shared by all rows.  By default training expands them to one packed copy per row (zuko_amd/autograd.py: UnivariateFn) and
+sums the [N, features, 2 components] gradient over the rows.  With zuko_amd.ops.GAUSS_SHARED_ADJOINT = True (off by default) it reads them in
+place and sums the gradient inside the adjoint kernel (GaussSharedFn / GaussSharedInverseFn on zk_gauss_backward_shared; the calls it serves:
+ops.gauss_shared_supported): no tensor of batch x features x components elements is created."""
 
 from __future__ import annotations
 

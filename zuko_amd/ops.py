@@ -848,6 +848,40 @@ def gauss_supported(K: int, dtype=torch.float32, needs_grad: bool = False) -> bo
     return dtype in (torch.float32, torch.float64) and 1 <= K <= GAUSS_K_MAX
 
 
+GAUSS_SHARED_ADJOINT = False  # True: [D, K] parameters shared by all rows train on zk_gauss_backward_shared (autograd.GaussSharedFn) instead of an expanded [N, D, 2K] copy
+
+
+def _gauss_shared_shapes(x: Tensor, shift: Tensor, scale: Tensor) -> bool:
+    """The dtype and shape clauses of gauss_shared_supported (no device needed)."""
+    return (x.dtype in (torch.float32, torch.bfloat16) and shift.dtype == x.dtype and scale.dtype == x.dtype and x.dim() >= 1 and shift.dim() == 2
+            and tuple(scale.shape) == tuple(shift.shape) and shift.shape[0] == x.shape[-1] and 1 <= shift.shape[1] <= GAUSS_K_MAX_BWD)
+
+
+def gauss_shared_supported(x: Tensor, shift: Tensor, scale: Tensor) -> bool:
+    """Does zk_gauss_backward_shared serve this call?  Device tensors, float32 (bfloat16 trains on float32 copies), x [..., D] with at least one
+    dimension, shift and scale exactly [D, K] (two-dimensional, no other broadcast), 1 <= K <= 32."""
+    return x.is_cuda and shift.is_cuda and scale.is_cuda and _gauss_shared_shapes(x, shift, scale)
+
+
+def gauss_shared_chunks(N: int, D: int, K: int) -> int:
+    """Row chunks of zk_gauss_backward_shared's partition (one [D, 2K] partial each in its workspace); 0 for a shape it does not serve."""
+    floats = _C.lib().zk_gauss_backward_shared_floats(int(N), int(D), int(K))
+    return floats // (D * 2 * K) if floats > 0 else 0
+
+
+def _gauss_route(x: Tensor, shift: Tensor, scale: Tensor, grad: bool, packed: Tensor | None = None) -> str:
+    """The path of gauss_forward / gauss_inverse: "torch" (torch ops), "kernel" (no gradients), and under autograd "packed" (UnivariatePackedFn, forward
+    only), "shared" (GaussSharedFn / GaussSharedInverseFn) or "rows" (UnivariateFn / UnivariateInverseFn on parameters expanded to every row)."""
+    K = shift.shape[-1]
+    if not (GAUSS_KERNEL and gauss_supported(K, x.dtype, grad)):
+        return "torch"
+    if not grad:
+        return "kernel"
+    if _packed_ok(x, packed, 2 * K):
+        return "packed"
+    return "shared" if GAUSS_SHARED_ADJOINT and gauss_shared_supported(x, shift, scale) else "rows"
+
+
 def _gauss_torch_f(x: Tensor, shift: Tensor, scale: Tensor) -> Tensor:
     """The reference's expression tree (zuko/transforms.py:869-875)."""
     u = x[..., None] * torch.exp(scale) + shift
@@ -870,7 +904,8 @@ def gauss_forward(x: Tensor, shift: Tensor, scale: Tensor, reduce: bool = False,
 
     K = _gauss_check(x, shift, scale)
     grad = AG.needs_grad(x, shift, scale)
-    if not (GAUSS_KERNEL and gauss_supported(K, x.dtype, grad)):
+    route = _gauss_route(x, shift, scale, grad, packed)
+    if route == "torch":
         with torch.enable_grad():
             xg = x.expand(torch.broadcast_shapes(x.shape, shift.shape[:-1], scale.shape[:-1])).clone().requires_grad_()
             y = _gauss_torch_f(xg, shift, scale)
@@ -879,9 +914,11 @@ def gauss_forward(x: Tensor, shift: Tensor, scale: Tensor, reduce: bool = False,
             y = y.detach()
         ladj = jac.log()
         return y, (ladj.sum(dim=-1) if reduce else ladj)
-    if grad:
-        if _packed_ok(x, packed, 2 * K):
-            return AG.UnivariatePackedFn.apply((4, GAUSS_BOUND, 0.0, (K, K), ()), reduce, x, packed)
+    if route == "packed":
+        return AG.UnivariatePackedFn.apply((4, GAUSS_BOUND, 0.0, (K, K), ()), reduce, x, packed)
+    if route == "shared":
+        return AG.GaussSharedFn.apply(reduce, x, shift, scale)
+    if route == "rows":
         return AG.UnivariateFn.apply(4, GAUSS_BOUND, 0.0, reduce, x, shift, scale)
     pr = _Prepared(x, [(shift, 1), (scale, 1)])
     if reduce and len(pr.shape) == 0:
@@ -902,10 +939,13 @@ def gauss_inverse(y: Tensor, shift: Tensor, scale: Tensor, bound: float = GAUSS_
     K = _gauss_check(y, shift, scale)
     grad = AG.needs_grad(y, shift, scale)
     n = math.ceil(math.log2(2 * bound / eps))
-    if not (GAUSS_KERNEL and gauss_supported(K, y.dtype, grad)):
+    route = _gauss_route(y, shift, scale, grad)
+    if route == "torch":
         phi = [p for p in (shift, scale) if p.requires_grad] if torch.is_grad_enabled() else []
         ye = y.expand(torch.broadcast_shapes(y.shape, shift.shape[:-1], scale.shape[:-1]))
         return _MnnBisection.apply(lambda v: _gauss_torch_f(v, shift, scale), ye, float(bound), n, *phi)
+    if route == "shared":
+        return AG.GaussSharedInverseFn.apply(float(bound), float(eps), y, shift, scale)
     if grad:
         return AG.UnivariateInverseFn.apply(4, float(bound), 0.0, (float(eps),), y, shift, scale)
     pr = _Prepared(y, [(shift, 1), (scale, 1)])

@@ -190,7 +190,7 @@ class GaussianizationTransform(_Univariate):
     r"""y = \Phi^{-1}(c mean_k \Phi(exp(a_k) x + b_k)), c = 1 - 1e-6, with shift b[*, K] and unconstrained scale a[*, K]: the univariate map of the
     Gaussianization flow.  Mirrors zuko/transforms.py:834-875 + MonotonicTransform (:570-637): value and log-derivative in one launch
     (zk_gauss_forward; the derivative in closed form instead of torch.autograd.grad), the inverse by the reference's bisection on [-bound, bound]
-    to `eps` (zk_gauss_inverse), gradients by zk_gauss_backward.  More than 64 components (32 with gradients) and float64 calls that need
+    to `eps` (zk_gauss_inverse), gradients by zk_gauss_backward (zk_gauss_backward_shared for [D, K] parameters under ops.GAUSS_SHARED_ADJOINT).  More than 64 components (32 with gradients) and float64 calls that need
     gradients run the reference's expressions as torch ops on the device (zuko_amd/ops.py: gauss_forward)."""
 
     def __init__(self, shift: Tensor, scale: Tensor, bound: float = 10.0, eps: float = 1e-6, **kwargs) -> None:
@@ -217,7 +217,9 @@ class RotationTransform(Transform):
 
     def __init__(self, A: Tensor, **kwargs) -> None:
         super().__init__(**kwargs)
-        self.R = torch.linalg.matrix_exp(A - A.mT)
+        S = A - A.mT
+        # (matrix_exp of a bfloat16 matrix comes back NaN on the device: a bfloat16 module takes it in float32 and rounds the result)
+        self.R = torch.linalg.matrix_exp(S.float()).to(S.dtype) if S.dtype == torch.bfloat16 else torch.linalg.matrix_exp(S)
 
     def _call(self, x: Tensor) -> Tensor:
         return torch.einsum("...ij,...j->...i", self.R, x)
