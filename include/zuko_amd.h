@@ -371,6 +371,58 @@ int zk_coupling_forward(const zk_coupling_args_v1* args, void* stream);
  * back by x_b = (y_b - shift) exp(-softclip(scale)).  ladj (optional) = log|det dy/dx| of the FORWARD map at the solution (negate it
  * for the inverse transform), the convention of zk_ar_inverse_incremental. */
 int zk_coupling_inverse(const zk_coupling_args_v1* args, void* stream);
+/* zk_coupling_forward_v2 / zk_coupling_inverse_v2: the same launches with the UNIVARIATE MAP in the block, which is zk_coupling_args_v1's fields
+ * followed by bound, uni_kind and bins.  struct_size and version = 2 are checked exactly; every argument is validated before the first HIP call.
+ *   uni_kind = 0: the affine map — exactly the v1 launch (bins and bound are not examined).
+ *   uni_kind = 1: the monotonic rational-quadratic spline with `bins` = K in {4, 8, 16} bins on [-bound, bound] (zuko/transforms.py:449-548,
+ *     MonotonicRQSTransform over packed (K, K, K - 1) parameters; slope is its `slope`): the coupling form of neural spline flows, i.e.
+ *     GeneralCouplingTransform(univariate=MonotonicRQSTransform, shapes=[(K,), (K,), (K - 1,)]).  The conditioner's last layer has 3 K - 1 rows per
+ *     moved feature.  n_groups counts groups of FOUR slots and fmap has 4 n_groups entries; the last layer's stream is, group by group and in-tile
+ *     by in-tile, NT = ceil((3 K - 1) / 4) out-tiles whose row 4 q + r of out-tile t is parameter 4 t + r of slot 4 g + q, and the last bias image is
+ *     n_groups x NT x 16 floats (zuko_amd/coupling_plan.py: build_coupling_plan(total = 3 K - 1)).  wstream is the f32 stream: static_ok must be 0.
+ *     The matrix instruction is v_mfma_f32_16x16x4_f32 (exact f32 products) for every shape.  The inverse launch returns log|det dy/dx| of the
+ *     FORWARD map at the solution, as the v1 one.  A NaN / inf among the conditioner's inputs makes every parameter of the row NaN, which the
+ *     spline turns into the reference's output: NaN right of -bound, the value itself elsewhere, ladj NaN.
+ *   Any other uni_kind, bins, a non-zero static_ok with a spline, bound <= 0 or slope outside (0, 1): hipErrorInvalidValue. */
+typedef struct zk_coupling_args_v2 {
+  uint32_t struct_size;    /* sizeof(zk_coupling_args_v2) */
+  uint32_t version;        /* 2 */
+  int32_t D;
+  int32_t C;
+  int32_t nit;
+  int32_t n_groups;        /* uni_kind 0: groups of 8 transformed slots; 1: groups of 4 */
+  int32_t n_layers;
+  int32_t n_chunks;
+  int32_t act;
+  int32_t bias_floats;
+  int32_t accumulate;
+  int32_t static_ok;       /* uni_kind 1: must be 0 */
+  int64_t N;
+  int64_t ldx;
+  int64_t ldc;
+  int64_t ldy;
+  double slope;
+  const void* in;
+  const void* ctx;
+  void* out;
+  void* ladj;
+  const void* wstream;
+  const void* bias;
+  const int32_t* bias_off;
+  const int32_t* amap;
+  const int32_t* fmap;     /* DEVICE [n_groups * 8] (uni_kind 0) or [n_groups * 4] (uni_kind 1) */
+  const int32_t* tiles;
+  const int32_t* widths;
+  double wdescale0;
+  double wdescale1;
+  double wdescale2;
+  double wdescale3;
+  double bound;            /* uni_kind 1: the spline's domain is [-bound, bound] */
+  int32_t uni_kind;        /* 0 affine, 1 rational-quadratic spline */
+  int32_t bins;            /* uni_kind 1: K, one of 4, 8, 16 */
+} zk_coupling_args_v2;
+int zk_coupling_forward_v2(const zk_coupling_args_v2* args, void* stream);
+int zk_coupling_inverse_v2(const zk_coupling_args_v2* args, void* stream);
 /* INCREMENTAL inverse: the whole loop of AutoregressiveTransform._inverse (zuko/transforms.py:994-1000) in one launch whose
  * multiply-add count is ~1.5x ONE density evaluation (every off-diagonal weight tile is multiplied once per sample; only the
  * diagonal tiles of a 4-feature group are iterated).  Needs the aligned-tile plan of zuko_amd/incremental.py

@@ -51,7 +51,7 @@ def _parse_structs(path: str) -> dict:
 
 STRUCTS = _parse_structs(_HEADER)
 _VERSION = {"zk_ar_args_v1": 1, "zk_coupling_args_v1": 1, "zk_ar_inc_args_v1": 1, "zk_mnn_args_v1": 1, "zk_mnn_bwd_args_v1": 1, "zk_umnn_args_v1": 1, "zk_umnn_bwd_args_v1": 1, "zk_gmm_args_v1": 1, "zk_cnf_args_v1": 1, "zk_cnf_adj_args_v1": 1,
-            "zk_cnf_args_v2": 2, "zk_cnf_adj_args_v2": 2}
+            "zk_cnf_args_v2": 2, "zk_cnf_adj_args_v2": 2, "zk_coupling_args_v2": 2}
 
 
 def args(struct: str, **fields):
@@ -97,6 +97,7 @@ def gather_multi(items, stream) -> None:
 
 
 _AR, _CP, _INC = POINTER(STRUCTS["zk_ar_args_v1"]), POINTER(STRUCTS["zk_coupling_args_v1"]), POINTER(STRUCTS["zk_ar_inc_args_v1"])
+_CP2 = POINTER(STRUCTS["zk_coupling_args_v2"])
 _MNN = POINTER(STRUCTS["zk_mnn_args_v1"])
 _MNN_BWD = POINTER(STRUCTS["zk_mnn_bwd_args_v1"])
 _UMNN = POINTER(STRUCTS["zk_umnn_args_v1"])
@@ -164,6 +165,8 @@ SIGNATURES = {
     "zk_ar_inverse_sweep": [_AR, P],
     "zk_coupling_forward": [_CP, P],
     "zk_coupling_inverse": [_CP, P],
+    "zk_coupling_forward_v2": [_CP2, P],
+    "zk_coupling_inverse_v2": [_CP2, P],
     "zk_ar_inverse_incremental": [_INC, P],
     "zk_ar_inc_lds_bytes": [I, I],
     "zk_ar_inverse_partial": [_AR, P],

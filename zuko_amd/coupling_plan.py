@@ -43,18 +43,37 @@ class CouplingPlan:
     split_gather: np.ndarray = None  # int32 [split_blocks * 512] (lane-major, 8 per lane) into the concatenated weights (-1 -> 0)
     split_chunks: int = 0
     split_layer_blocks: list = None  # blocks of every linear layer inside split_gather (the two-part stream scales each layer by its own power of two)
+    total: int = 2   # parameters per moved feature: 2 = the affine map, 3 K - 1 = the K-bin spline (coupling_rqs_kernel)
+    nt: int = 1      # out-tiles of a group of the last layer: 1 (8 slots x 2 parameters) or ceil(total / 4) (4 slots x total parameters, padded to 4 nt)
 
 
-def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk: int = CHUNK):
-    """shapes: [(out, in)] of the MLP's linear layers; idx_a / idx_b: columns of x that pass through / are transformed.
-    Returns None when the network does not fit the kernel (widths > 512, inputs > 256, fewer than two layers)."""
+SPLINE_BINS = (4, 8, 16)      # K of the spline kernel's instantiations (csrc/fused_coupling.hip: coupling_rqs_kernel)
+SPLINE_TOTALS = tuple(3 * k - 1 for k in SPLINE_BINS)
+LDS_LIMIT = 160 * 1024        # bytes of LDS a workgroup of the coupling kernels may take (csrc/fused_coupling.hip: cp_launch)
+
+
+def lds_bytes(bias_floats: int, n_groups: int, features: int, context: int, chunk: int = CHUNK) -> int:
+    """CpLds::bytes of csrc/fused_coupling.hip: ring, bias image, the two index maps, the layer words and four row images."""
+    xs = (features + context + 3) // 4 * 4 + 4
+    return (RING * chunk * 256 + bias_floats + MAX_IT * TILE + n_groups * 8 + 3 * 8 + 4 * 16 * xs) * 4
+
+
+def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk: int = CHUNK, total: int = 2):
+    """shapes: [(out, in)] of the MLP's linear layers; idx_a / idx_b: columns of x that pass through / are transformed; total: parameters per
+    moved feature (2: the affine map; 3 K - 1 with K = 4, 8, 16: the spline, whose last layer runs in groups of 4 slots with all parameters of
+    a slot in one lane, see last_rows).  Returns None when the network does not fit the kernel (widths > 512, inputs > 256, fewer than two
+    layers, a spline plan whose tables exceed the kernel's LDS)."""
+    spline = total != 2
+    if spline and total not in SPLINE_TOTALS:
+        return None
+    nt = -(-total // 4) if spline else 1
     L = len(shapes)
     idx_a, idx_b = np.asarray(idx_a, dtype=np.int64), np.asarray(idx_b, dtype=np.int64)
     if L < 2 or L > 8:
         return None
     din = shapes[0][1]
     moved = len(idx_b)
-    if din != len(idx_a) + context or shapes[-1][0] != 2 * moved:
+    if din != len(idx_a) + context or shapes[-1][0] != total * moved:
         return None
     widths = [s[0] for s in shapes[:-1]]
     if din > MAX_IT * TILE or any(w > MAX_T * TILE for w in widths) or any(shapes[l + 1][1] != widths[l] for l in range(L - 1)):
@@ -63,7 +82,7 @@ def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk
         return None
     nit = -(-din // TILE)
     tiles = [-(-w // TILE) for w in widths]
-    n_groups = -(-moved // 8)
+    n_groups = -(-moved // (4 if spline else 8))
     w_off, b_off = [], []
     acc = 0
     for o, i in shapes:
@@ -88,8 +107,14 @@ def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk
         v[v >= limit] = -1
         return v
 
-    def last_rows(g):
+    def last_rows(g, t=0):
         rows = -np.ones(TILE, dtype=np.int64)
+        if spline:  # row i of out-tile t: parameter 4 t + (i & 3) of slot 4 g + (i >> 2) — lane (j, q) of the kernel accumulates slot 4 g + q
+            for i in range(TILE):
+                slot, p = 4 * g + (i >> 2), 4 * t + (i & 3)
+                if slot < moved and p < total:
+                    rows[i] = slot * total + p
+            return rows
         for i in range(TILE):
             fi, p = divmod(i & 3, 2)
             slot = g * 8 + (i >> 2) * 2 + fi
@@ -112,7 +137,8 @@ def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk
         pad()
     for g in range(n_groups):
         for it in range(tiles[-1]):
-            blocks.append(image(L - 1, last_rows(g), span(it, widths[-1])))
+            for t in range(nt):  # (spline: the nt out-tiles of one in-tile side by side — independent accumulators)
+                blocks.append(image(L - 1, last_rows(g, t), span(it, widths[-1])))
     pad()
     gather = np.concatenate(blocks).astype(np.int32)
 
@@ -126,14 +152,17 @@ def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk
     bias_off.append(cur)
     lastb = []
     for g in range(n_groups):
-        rows = last_rows(g)
-        lastb.append(np.where(rows >= 0, b_off[L - 1] + np.maximum(rows, 0), -1))
+        for t in range(nt):
+            rows = last_rows(g, t)
+            lastb.append(np.where(rows >= 0, b_off[L - 1] + np.maximum(rows, 0), -1))
     bias_gather.append(np.concatenate(lastb))
+    if spline and lds_bytes(sum(len(b) for b in bias_gather), n_groups, features, context) > LDS_LIMIT:
+        return None
 
     # operand-split twin of the stream for the static shape: a block = (out tile, PAIR of in tiles) as three bf16 images; hidden layers
     # in steps of (4 out tiles, 1 in pair), the last layer group by group, pair by pair.  Every layer and every group fills whole chunks.
     split_gather, split_chunks, split_layer_blocks = None, 0, None
-    if nit == 8 and all(w == 512 for w in widths):
+    if nit == 8 and all(w == 512 for w in widths) and not spline:
         def block(l, rows, ip, in_w):
             lo, hi = image(l, rows, span(2 * ip, in_w)).reshape(64, 4), image(l, rows, span(2 * ip + 1, in_w)).reshape(64, 4)
             return np.concatenate([lo, hi], axis=1).reshape(-1)
@@ -160,24 +189,28 @@ def build_coupling_plan(shapes, idx_a, idx_b, features: int, context: int, chunk
     amap[: len(idx_a)] = idx_a
     for c in range(context):
         amap[len(idx_a) + c] = -(2 + c)
-    fmap = -np.ones(n_groups * 8, dtype=np.int64)
+    fmap = -np.ones(n_groups * (4 if spline else 8), dtype=np.int64)
     fmap[:moved] = idx_b
     return CouplingPlan(
         n_layers=L, din=din, nit=nit, widths=widths, tiles=tiles, moved=moved, n_groups=n_groups, gather=gather, n_blocks=len(blocks),
         n_chunks=len(blocks) // chunk, bias_gather=np.concatenate(bias_gather).astype(np.int32), bias_off=bias_off, amap=amap.astype(np.int32),
-        fmap=fmap.astype(np.int32), features=features, context=context, split_gather=split_gather, split_chunks=split_chunks, split_layer_blocks=split_layer_blocks,
+        fmap=fmap.astype(np.int32), features=features, context=context, split_gather=split_gather, split_chunks=split_chunks, split_layer_blocks=split_layer_blocks, total=total, nt=nt,
     )
 
 
 class FusedCoupling:
-    """Runs zk_coupling_forward for one GeneralCouplingTransform on one device."""
+    """Runs zk_coupling_forward for one GeneralCouplingTransform on one device.  uni = (kind, K, bound) of the univariate map: (0, 0, 0.0) the
+    affine map; (1, K, bound) the K-bin spline, which goes through zk_coupling_forward_v2 / _inverse_v2 on the f32 stream of a plan built with
+    total = 3 K - 1 (never the split / half streams)."""
 
-    def __init__(self, plan: CouplingPlan, device, act: int, slope: float) -> None:
+    def __init__(self, plan: CouplingPlan, device, act: int, slope: float, uni=(0, 0, 0.0)) -> None:
         import ctypes
 
         import torch
 
         self.plan, self.device, self.act, self.slope = plan, device, act, slope
+        self.uni_kind, self.bins, self.bound = int(uni[0]), int(uni[1]), float(uni[2])
+        assert (self.uni_kind == 0 and plan.total == 2) or (self.uni_kind == 1 and plan.total == 3 * self.bins - 1), "plan and univariate map disagree"
         self.gather = torch.from_numpy(plan.gather).to(device)
         self.bias_gather = torch.from_numpy(plan.bias_gather).to(device)
         self.amap = torch.from_numpy(plan.amap).to(device)
@@ -249,6 +282,14 @@ class FusedCoupling:
         N = x.shape[0]
         y = torch.empty((N, p.features), dtype=torch.float32, device=x.device)
         ladj = torch.empty(N, dtype=torch.float32, device=x.device)
+        if self.uni_kind == 1:
+            a = _C.args("zk_coupling_args_v2", N=N, D=p.features, C=p.context, **{"in": _ptr(x)}, ldx=x.stride(0), ctx=_ptr(ctx), ldc=0 if ctx is None else ctx.stride(0), out=_ptr(y),
+                        ldy=p.features, ladj=_ptr(ladj), accumulate=0, bias=_ptr(self.bias), bias_floats=self.bias.numel(), bias_off=self.bias_off,
+                        amap=_ptr(self.amap), nit=p.nit, fmap=_ptr(self.fmap), n_groups=p.n_groups, n_layers=p.n_layers, tiles=self.tiles, widths=self.widths,
+                        act=self.act, slope=self.slope, wstream=_ptr(self.stream), n_chunks=p.n_chunks, static_ok=0, uni_kind=1, bins=self.bins, bound=self.bound)
+            name = "zk_coupling_inverse_v2" if inverse else "zk_coupling_forward_v2"
+            _C.check(getattr(_C.lib(), name)(a, _stream()), name)
+            return y, ladj
         fn = _C.lib().zk_coupling_inverse if inverse else _C.lib().zk_coupling_forward
         from . import fused
 

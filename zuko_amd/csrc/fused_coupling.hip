@@ -865,6 +865,131 @@ template <int NIT, int HT> __global__ __launch_bounds__(256, 1) void coupling_ke
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
 }
 
+
+// ---- SPLINE twin of the generic kernel: the univariate map is the K-bin rational-quadratic spline (zuko/transforms.py:449-548) -------------------
+// The coupling form of neural spline flows: NICE(..., univariate=MonotonicRQSTransform, shapes=[(K,), (K,), (K - 1,)]).  Same data flow as
+// coupling_kernel up to the last hidden layer.  The last layer runs one group of FOUR moved features at a time: lane (j, q) owns slot 4 g + q of
+// sample j and accumulates that slot's TOTAL = 3 K - 1 parameters in NT = ceil(TOTAL / 4) accumulators — the plan orders the weight rows so that row
+// 4 q + r of out-tile t is parameter 4 t + r of slot 4 g + q (coupling_plan.py: last_rows with total = 3 K - 1), which is where the matrix instruction
+// leaves it, as in the autoregressive kernels.  The stream of a group is in-tile by in-tile, the NT out-tiles of one in-tile side by side: NT
+// independent accumulator chains.  rqs_lean then runs on the registers, forward or (a.inverse) inverse with the forward map's log-derivative at the
+// solution.  Non-finite inputs: the conditioner is dense, so a NaN / inf among its inputs reaches every parameter through the matrix instruction
+// itself (no skipped tiles, hence no flag as in ar_poison_of); all-NaN parameters give the reference's output (zk_ar_common.h: UniRqs::poison).
+// cp_activate with the padding test turned round: `4 q + r >= width - 16 t` has a wave-uniform right-hand side, so the loop-invariant part is the lane's
+// four unit offsets.  (Written as t * 16 + 4 * q + r >= width the compiler hoists all 128 left-hand sides out of the pass loop and keeps them in
+// registers for the whole kernel: beside 32 + 32 activation tiles they do not fit, and they were this kernel's scratch.)
+__device__ __forceinline__ void cp_activate_rqs(const CpAct& h, int n_out, int width, int act, int q) {
+#pragma unroll
+  for (int t = 0; t < CP_T; ++t) {
+    if (t < n_out) {
+      if (act == 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h[t][r] = h[t][r] < 0.f ? 0.f : h[t][r];  // NaN stays NaN, as torch.relu
+      } else if (act != 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h[t][r] = cp_act_slow(h[t][r], act);
+      }
+      // units beyond the layer's width are padding: keep them at exactly 0 (0 * non-finite would poison the next layer)
+      const int left = width - t * 16;  // units of this tile that exist
+      if (left < 16) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (4 * q + r >= left) h[t][r] = 0.f;
+      }
+    }
+  }
+}
+
+template <int K> __global__ __launch_bounds__(256, 1) void coupling_rqs_kernel(CpArgs a, RqsLeanConst lc) {
+  typedef UniRqs<K, false> Uni;
+  constexpr int NT = Uni::NT;
+  constexpr int STEP = NT < 6 ? NT : 6;  // out-tiles read from the ring at a time: 3 / 6 / 6 of NT = 3 / 6 / 12
+  static_assert(NT % STEP == 0 && CP_CH % STEP == 0, "a step never straddles two chunks");
+  const ArLane ln;
+  const int lane = ln.lane, wave = ln.wave, q = ln.q;
+  const CpLds lds(a, CP_CH, wave);  // (fmap: 4 slots per group used of the 8 the carve reserves)
+  if (ln.tid == 0) {
+#pragma unroll
+    for (int l = 0; l < CP_MAXL; ++l) { lds.lay[l] = a.wt[l]; lds.lay[CP_MAXL + l] = a.width[l]; lds.lay[2 * CP_MAXL + l] = a.bias_off[l]; }
+  }
+  for (int i = ln.tid; i < a.bias_floats; i += 256) lds.bias[i] = a.bias[i];
+  for (int i = ln.tid; i < a.nit * 16; i += 256) lds.amap[i] = a.amap[i];
+  for (int i = ln.tid; i < a.NG * 4; i += 256) lds.fmap[i] = a.fmap[i];
+
+  CpRing ring;
+  ring.lds = cp_lds; ring.stream = a.stream; ring.n_chunks = a.n_chunks; ring.wave = wave; ring.lane = lane;
+  ring.load_chunk = 0; ring.load_slot = 0;
+#pragma unroll
+  for (int i = 0; i < CP_NR - 1; ++i) ring.issue();
+  ring.slot = CP_NR - 1;
+  ring.pos = CP_CH;
+  __syncthreads();
+
+  float* const xw = lds.rows;
+  float* const xrow = xw + ln.j * a.xs;
+  for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
+    const int64_t n0 = tile * 64 + wave * 16;
+    cp_stage_rows(a, xw, a.xs, n0, lane);
+
+    f32x4 out_lo[16], out_hi[16], in_lo[16], in_hi[16];
+    const CpAct out{out_lo, out_hi}, in{in_lo, in_hi};
+#pragma unroll
+    for (int it = 0; it < CP_T; ++it) in[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int it = 0; it < CP_IT; ++it) {
+      if (it < a.nit) in[it] = cp_gather_inputs(a, lds.amap, xrow, it, q);
+    }
+    int n_prev = lds.tiles_of(0);
+    cp_layer<CP_IT>(ring, a.nit, n_prev, lds.bias_of(0, q), in, out);
+    cp_activate_rqs(out, n_prev, lds.width_of(0), a.act, q);
+    for (int l = 1; l < a.L - 1; ++l) {
+#pragma unroll
+      for (int t = 0; t < CP_T; ++t) in[t] = out[t];
+      const int n_out = lds.tiles_of(l);
+      cp_layer<CP_T>(ring, n_prev, n_out, lds.bias_of(l, q), in, out);
+      cp_activate_rqs(out, n_out, lds.width_of(l), a.act, q);
+      n_prev = n_out;
+    }
+    // ---- last layer + spline, one group of 4 moved features at a time (lane (j, q): slot 4 g + q) -----------------------------------------
+    const float* bias_last = lds.bias_of(a.L - 1, q);
+    float lacc = 0.f;
+    for (int g = 0; g < a.NG; ++g) {
+      const int f = lds.fmap[4 * g + q];
+      const float v = xrow[f < 0 ? 0 : f];
+      f32x4 acc[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] = *reinterpret_cast<const f32x4*>(bias_last + (g * NT + t) * 16);
+#pragma unroll
+      for (int it = 0; it < CP_T; ++it) {
+        if (it < n_prev) {
+#pragma unroll
+          for (int t0 = 0; t0 < NT; t0 += STEP) {
+            ring.template begin<STEP>();
+            f32x4 w[STEP];
+#pragma unroll
+            for (int t = 0; t < STEP; ++t) w[t] = ring.tile(t);
+            ring.template commit<STEP>();
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int t = 0; t < STEP; ++t) acc[t0 + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][r], out[it][r], acc[t0 + t], 0, 0, 0);
+          }
+        }
+      }
+      // parameter p of the lane's slot = acc[p / 4][p % 4]: widths [0, K), heights [K, 2 K), derivatives [2 K, 3 K - 1)
+      auto par = [&](int p) { return acc[p >> 2][p & 3]; };
+      float res, lj;
+      int bin;  // (unused: the three-flag form of rqs_lean returns it)
+      if (a.inverse) rqs_lean<K, true, true>([&](int j) { return par(j); }, [&](int j) { return par(K + j); }, [&](int j) { return par(2 * K + j); }, lc, v, res, lj, bin);
+      else rqs_lean<K, false>([&](int j) { return par(j); }, [&](int j) { return par(K + j); }, [&](int j) { return par(2 * K + j); }, lc, v, res, lj);
+      if (f >= 0) { xrow[f] = res; lacc += lj; }
+    }
+    ring.end_layer();
+    cp_finish_rows(a, xw, n0, ln, lacc);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // look-ahead DMAs must land before the LDS is released
+}
+
 }  // namespace zk
 
 using namespace zk;
@@ -879,7 +1004,7 @@ extern "C" {
 static int cp_launch(int inverse, int64_t N, int D, int C, const void* x, int64_t ldx, const void* ctx, int64_t ldc, void* y, int64_t ldy, void* ladj, int accumulate,
                         const void* wstream, const void* bias, int bias_floats, const int32_t* bias_off, const int32_t* amap, int nit, const int32_t* fmap,
                         int n_groups, int n_layers, const int32_t* tiles, const int32_t* widths, int n_chunks, int act, double slope, int static_ok, void* stream,
-                        const double* wdescale = nullptr) {
+                        const double* wdescale = nullptr, int bins = 0, double bound = 0.0) {
   if (N <= 0) return 0;
   if (n_layers < 2 || n_layers > CP_MAXL || nit < 1 || nit > CP_IT || n_groups < 1 || n_chunks < 1 || D < 2 || C < 0 || (C > 0 && !ctx)) return ZK_EINVAL;
   CpArgs a{};
@@ -920,10 +1045,16 @@ static int cp_launch(int inverse, int64_t N, int D, int C, const void* x, int64_
   } else if (same && static_ok) {
     fn = (const void*)coupling_kernel_static<8, 32>;
   }
+  // bins != 0 (zk_coupling_*_v2 with uni_kind = 1): the spline kernel; n_groups counts groups of 4 slots, the plan's stream is the f32 one
+  if (bins) {
+    if (static_ok) return ZK_EINVAL;
+    fn = bins == 4 ? (const void*)coupling_rqs_kernel<4> : bins == 8 ? (const void*)coupling_rqs_kernel<8> : (const void*)coupling_rqs_kernel<16>;
+  }
+  RqsLeanConst lc = rqs_lean_const(bound, log(slope));
   const int lds = CpLds::bytes(chunk, bias_floats, n_groups, a.xs);
   hipError_t e = grant_dyn_lds(fn, lds);
   if (e != hipSuccess) return (int)e;
-  void* kargs[] = {&a};
+  void* kargs[] = {&a, &lc};  // (lc: the spline kernels' second argument)
   e = hipLaunchKernel(fn, dim3((unsigned)(a.n_tiles < 256 ? a.n_tiles : 256)), dim3(256), kargs, lds, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   return ZK_LAUNCH_CHECK();
@@ -941,5 +1072,22 @@ int zk_coupling_forward(const zk_coupling_args_v1* args, void* stream) { return 
 // CouplingTransform._inverse (zuko/transforms.py:1050-1056): same launch with the affine map of the moved half inverted; ladj = the
 // FORWARD map's log-determinant at the solution.
 int zk_coupling_inverse(const zk_coupling_args_v1* args, void* stream) { return cp_launch_v1(1, args, stream); }
+
+// Version 2 of the block: the v1 fields + the univariate map.  uni_kind = 0 is the v1 launch; uni_kind = 1 the K-bin spline (coupling_rqs_kernel).
+// Everything is validated before the first HIP call.
+static int cp_launch_v2(int inverse, const zk_coupling_args_v2* p, void* stream) {
+  if (!p || p->struct_size != sizeof(zk_coupling_args_v2) || p->version != 2) return ZK_EINVAL;
+  if (p->uni_kind != 0 && p->uni_kind != 1) return ZK_EINVAL;
+  int bins = 0;
+  if (p->uni_kind == 1) {
+    if ((p->bins != 4 && p->bins != 8 && p->bins != 16) || p->static_ok != 0 || !(p->bound > 0.0) || !(p->bound < 1e30) || !(p->slope > 0.0) || !(p->slope < 1.0)) return ZK_EINVAL;
+    bins = p->bins;
+  }
+  return cp_launch(inverse, p->N, p->D, p->C, p->in, p->ldx, p->ctx, p->ldc, p->out, p->ldy, p->ladj, p->accumulate, p->wstream, p->bias, p->bias_floats, p->bias_off, p->amap,
+                   p->nit, p->fmap, p->n_groups, p->n_layers, p->tiles, p->widths, p->n_chunks, p->act, p->slope, p->static_ok, stream, &p->wdescale0, bins, p->bound);
+}
+
+int zk_coupling_forward_v2(const zk_coupling_args_v2* args, void* stream) { return cp_launch_v2(0, args, stream); }
+int zk_coupling_inverse_v2(const zk_coupling_args_v2* args, void* stream) { return cp_launch_v2(1, args, stream); }
 
 }  // extern "C"

@@ -38,6 +38,21 @@ def _univariate_name(univariate) -> str:
     return getattr(f, "__name__", repr(f))
 
 
+def rqs_spec(univariate, shapes):
+    """(K, bound, slope) when `univariate` is a plain MonotonicRQSTransform — or a partial of it with `bound` / `slope` keywords only and no
+    positional arguments — over packed (K, K, K - 1) parameters; None otherwise.  The recognition the fused autoregressive and coupling
+    kernels share."""
+    u = univariate
+    f, kw = (u.func, dict(u.keywords)) if isinstance(u, partial) else (u, {})
+    if (isinstance(u, partial) and u.args) or f is not MonotonicRQSTransform:
+        return None
+    shapes = [tuple(s) for s in shapes]
+    if not (len(shapes) == 3 and len(shapes[0]) == 1 and shapes[0] == shapes[1] and shapes[2] == (shapes[0][0] - 1,)):
+        return None
+    slope, bound = kw.pop("slope", 1e-3), kw.pop("bound", 5.0)
+    return None if kw else (shapes[0][0], bound, slope)
+
+
 def dag_diameter(adjacency: BoolTensor) -> int:
     """Number of topological generations of the DAG `adjacency[child, parent]`
     (= sequential passes the inverse needs); asserts acyclicity.  zuko/flows/autoregressive.py:154-185."""
@@ -265,15 +280,7 @@ class MaskedAutoregressiveTransform(LazyTransform):
 
     def _rqs_spec(self):
         """(K, bound, slope) when the univariate map is a plain MonotonicRQSTransform over packed (K, K, K-1) parameters."""
-        u = self.univariate
-        f, kw = (u.func, dict(u.keywords)) if isinstance(u, partial) else (u, {})
-        if (isinstance(u, partial) and u.args) or f is not MonotonicRQSTransform:
-            return None
-        shapes = [tuple(s) for s in self.shapes]
-        if not (len(shapes) == 3 and len(shapes[0]) == 1 and shapes[0] == shapes[1] and shapes[2] == (shapes[0][0] - 1,)):
-            return None
-        slope, bound = kw.pop("slope", 1e-3), kw.pop("bound", 5.0)
-        return None if kw else (shapes[0][0], bound, slope)
+        return rqs_spec(self.univariate, self.shapes)
 
     def incremental_state(self, device: torch.device):
         """Plan + device tables of the incremental inverse kernel (csrc/inc_inverse.hip), or None when the conditioner does

@@ -20,7 +20,7 @@ from ..lazy import Flow, LazyTransform, UnconditionalDistribution
 from ..nn import MLP
 from ..transforms import CouplingTransform, DependentTransform, MonotonicAffineTransform, MonotonicRQSTransform
 from ..utils import broadcast, unpack
-from .autoregressive import _univariate_name
+from .autoregressive import _univariate_name, rqs_spec
 from .elementwise import ElementWiseTransform
 
 __all__ = ["NICE", "GeneralCouplingTransform", "RealNVP"]
@@ -87,7 +87,8 @@ class GeneralCouplingTransform(LazyTransform):
 
     def fused_state(self, device: torch.device):
         """Plan + device tables of the fused coupling kernel (csrc/fused_coupling.hip), or None when the layer does not fit it
-        (affine univariate with default shapes, plain (Linear, activation)* conditioner, widths <= 512, inputs <= 256)."""
+        (affine univariate with default shapes, or a plain MonotonicRQSTransform over packed (K, K, K - 1) parameters with K = 4, 8, 16;
+        plain (Linear, activation)* conditioner, widths <= 512, inputs <= 256)."""
         from .. import coupling_plan as cp
         from ..nn import Linear, _act_code
 
@@ -104,14 +105,18 @@ class GeneralCouplingTransform(LazyTransform):
             lins, acts = mods[0::2], mods[1::2]
             simple = len(mods) == 2 * len(lins) - 1 and all(isinstance(m, Linear) for m in lins) and not any(isinstance(m, Linear) for m in acts)
             codes = {_act_code(m) for m in acts}
-            if (f is MonotonicAffineTransform and not kw and not (isinstance(u, partial) and u.args) and [tuple(s_) for s_ in self.shapes] == [(), ()]
-                    and simple and len(codes) == 1 and None not in codes and all(l.weight.dtype == torch.float32 for l in lins)):
+            affine = f is MonotonicAffineTransform and not kw and not (isinstance(u, partial) and u.args) and [tuple(s_) for s_ in self.shapes] == [(), ()]
+            spline = rqs_spec(u, self.shapes)  # (K, bound, slope) of a plain MonotonicRQSTransform: the spline kernel has K = 4, 8, 16
+            if spline is not None and (spline[0] not in cp.SPLINE_BINS or not (spline[1] > 0 and 0 < spline[2] < 1)):
+                spline = None
+            if (affine or spline is not None) and simple and len(codes) == 1 and None not in codes and all(l.weight.dtype == torch.float32 for l in lins):
                 idx_a = self.mask.nonzero().squeeze(-1).cpu().numpy()
                 idx_b = (~self.mask).nonzero().squeeze(-1).cpu().numpy()
                 context = lins[0].weight.shape[1] - len(idx_a)
-                plan = cp.build_coupling_plan([tuple(l.weight.shape) for l in lins], idx_a, idx_b, int(self.mask.numel()), context)
+                total = 2 if affine else 3 * spline[0] - 1
+                plan = cp.build_coupling_plan([tuple(l.weight.shape) for l in lins], idx_a, idx_b, int(self.mask.numel()), context, total=total)
                 if plan is not None:
-                    state = cp.FusedCoupling(plan, device, codes.pop(), slope)
+                    state = cp.FusedCoupling(plan, device, codes.pop(), slope if affine else spline[2], uni=(0, 0, 0.0) if affine else (1, spline[0], spline[1]))
             cache["state"] = state
         return cache["state"]
 
