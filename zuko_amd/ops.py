@@ -9,7 +9,8 @@ ON THE DEVICE outside its kernels' envelope (features or components above 64, sa
 continuous flow (cnf_integrate) hands every call its step kernel does not serve — gradients (CNF_ADJOINT off), float64, Hutchinson's estimator (CNF_HUTCHINSON
 off), other activations or shapes — to zuko_amd.utils.odeint, the reference's adaptive integration in torch ops.  The Gaussianization map (gauss_forward / gauss_inverse) runs the
 reference's expressions as torch ops ON THE DEVICE for more than 64 components (32 with gradients), for float64 calls that need gradients and under
-GAUSS_KERNEL = False.
+GAUSS_KERNEL = False.  The conditioner layer (linear) and the rational-quadratic spline (rqs_forward) evaluate the reference's expressions as torch ops ON THE DEVICE for
+float64 calls that need gradients (their adjoint kernels are float32): a float64 coupling or autoregressive spline flow trains layer by layer on them.
 """
 
 from __future__ import annotations
@@ -85,6 +86,53 @@ def _no_grad_only(*ts: Tensor) -> None:
             "zuko_amd: no backward kernel for this operation yet (autograd covers log_prob of affine / RQS "
             "flows, see zuko_amd/autograd.py); call it under torch.no_grad()."
         )
+
+
+def _f64_grad(*ts) -> bool:
+    """A call that needs gradients with a float64 operand: the adjoint kernels are float32, so it evaluates the reference's expressions as torch ops
+    ON THE DEVICE in float64 (the base density and the Gaussianization map do the same; float32 stays on the kernels, bfloat16 on float32 copies)."""
+    ts = [t for t in ts if isinstance(t, Tensor)]
+    return torch.is_grad_enabled() and any(t.dtype == torch.float64 for t in ts) and any(t.requires_grad for t in ts)
+
+
+_ACT_MODULE = {1: torch.nn.ReLU, 2: torch.nn.ELU, 3: torch.nn.Tanh, 4: torch.nn.SiLU, 5: torch.nn.GELU, 6: torch.nn.Sigmoid, 7: torch.nn.LeakyReLU}
+
+
+def _linear_torch(x: Tensor, weight: Tensor, bias: Tensor | None, mask: Tensor | None, act: int) -> Tensor:
+    """act(x @ (mask * weight).T + bias) as torch ops (zuko/nn.py:217-218)."""
+    w = weight if mask is None else weight * mask.to(weight.dtype)
+    y = torch.nn.functional.linear(x, w, bias)
+    return y if act == 0 else _ACT_MODULE[act]()(y)
+
+
+def _rqs_forward_torch(x: Tensor, widths: Tensor, heights: Tensor, derivatives: Tensor, bound: float, slope: float, reduce: bool):
+    """(y, ladj) of the monotonic rational-quadratic spline as torch ops (zuko/transforms.py:469-490, 499-526, 554-567): soft clip, softmax, cumulative
+    knots, strict-compare bin search, the rational-quadratic value and log-derivative; the identity outside [-bound, bound]."""
+    ls = math.log(slope)
+    K = widths.shape[-1]
+    w = torch.softmax(widths / (1 + abs(2 * widths / ls)), dim=-1)
+    h = torch.softmax(heights / (1 + abs(2 * heights / ls)), dim=-1)
+    d = derivatives / (1 + abs(derivatives / ls))
+    pad = torch.nn.functional.pad
+    hor = bound * (2 * torch.cumsum(pad(w, (1, 0), value=0), dim=-1) - 1)
+    ver = bound * (2 * torch.cumsum(pad(h, (1, 0), value=0), dim=-1) - 1)
+    der = torch.exp(pad(d, (1, 1), value=0))
+    k = torch.sum(hor < x[..., None], dim=-1) - 1
+    inside = torch.logical_and(0 <= k, k < K)
+    k = (k % K)[..., None]
+    shape = torch.broadcast_shapes(k.shape[:-1], hor.shape[:-1])
+    k = k.expand(shape + (1,))
+    hor, ver, der = (t.expand(shape + (K + 1,)) for t in (hor, ver, der))
+    x0, x1 = hor.gather(-1, k).squeeze(-1), hor.gather(-1, k + 1).squeeze(-1)
+    y0, y1 = ver.gather(-1, k).squeeze(-1), ver.gather(-1, k + 1).squeeze(-1)
+    d0, d1 = der.gather(-1, k).squeeze(-1), der.gather(-1, k + 1).squeeze(-1)
+    s = (y1 - y0) / (x1 - x0)
+    z = inside * (x - x0) / (x1 - x0)
+    den = s + (d0 + d1 - 2 * s) * z * (1 - z)
+    y = y0 + (y1 - y0) * (s * z**2 + d0 * z * (1 - z)) / den
+    jac = s**2 * (2 * s * z * (1 - z) + d0 * (1 - z) ** 2 + d1 * z**2) / den**2
+    y, ladj = torch.where(inside, y, x), inside * jac.log()
+    return y, (ladj.sum(-1) if reduce else ladj)
 
 
 def _stream() -> int:
@@ -183,6 +231,8 @@ def rqs_forward(x: Tensor, widths: Tensor, heights: Tensor, derivatives: Tensor,
 
     if not want_bins and AG.needs_grad(x, widths, heights, derivatives):
         _require_device(x, widths, heights, derivatives)
+        if _f64_grad(x, widths, heights, derivatives):
+            return _rqs_forward_torch(x, widths, heights, derivatives, bound, slope, reduce)
         if K > 64:
             raise NotImplementedError("zuko_amd: spline backward is built for up to 64 bins")
         if _packed_ok(x, packed, 3 * K - 1):
@@ -404,6 +454,8 @@ def linear(x: Tensor, weight: Tensor, bias: Tensor | None = None, mask: Tensor |
     from . import autograd as AG
 
     if AG.needs_grad(x, weight, bias):
+        if _f64_grad(x, weight, bias):
+            return _linear_torch(x, weight, bias, mask, act)
         if act not in AG.BACKWARD_ACTS:
             raise NotImplementedError("zuko_amd: this activation cannot be fused when gradients are required")
         return AG.LinearFn.apply(x, weight, bias, mask, act)
